@@ -1,6 +1,6 @@
 """Backend interface for the HIP path — mirror of cglb/backend/pytorch/interface.py restricted to what the CGLB
 path needs: configure_backend, set_default_float/jitter, get_default_float(_str), create_kernel,
-create_model(CGLBConfig), model_parameters, optimize (SciPy L-BFGS-B, four-round schedule :445-543), save, load,
+create_model (all five classes of SGPR_CONFIGS: cglb, cglbn2m, cglbnm2, sgpr, sgprn2m), model_parameters, optimize (SciPy L-BFGS-B, four-round schedule :445-543), save, load,
 metrics_fn (:607-658).  Exact-GP / Adam / MultiDeviceKernel branches are out of scope and raise NotImplementedError,
 like the reference's unregistered singledispatch defaults (:120-147).
 """
@@ -19,9 +19,10 @@ import torch
 
 from . import jsonio, metric
 from .callbacks import Logger
-from .config import CGLBConfig, KernelConfig, Matern32Config, ModelConfig, SGPRConfig, SquaredExponentialConfig
-from .models import (CGLB, GPR, BaseKernel, GaussianLikelihood, InducingPointKernel, LowerBoundCG, PredictCG, ScaleKernel,
-                     get_cholesky_jitter, log_density, set_cholesky_jitter)
+from .config import (CGLBConfig, CGLBN2MConfig, CGLBNM2Config, KernelConfig, Matern32Config, ModelConfig, SGPRConfig, SGPRN2MConfig,
+                     SquaredExponentialConfig)
+from .models import (CGLB, CGLBN2M, CGLBNM2, GPR, SGPR, SGPRN2M, BaseKernel, GaussianLikelihood, InducingPointKernel, LowerBoundCG,
+                     LowerBoundSGPR, PredictCG, PredictSGPR, ScaleKernel, get_cholesky_jitter, log_density, set_cholesky_jitter)
 from .optimizer import Scipy
 
 __all__ = ["create_kernel", "create_model", "optimize", "save", "load", "metrics_fn"]
@@ -196,6 +197,53 @@ def _create_model_cglb(model_cfg: CGLBConfig, data: Data):
     return model
 
 
+def _create_cglb_variant(cls, model_cfg: CGLBConfig, data: Data):
+    likelihood, kernel = _likelihood_and_kernel_for_sgpr(model_cfg, data)
+    extra = {}
+    if _STATE["config_semantics"] == "tf":
+        extra = dict(max_error=model_cfg.max_error, joint_optimization=model_cfg.joint_optimization, vzero=model_cfg.vzero)
+    return cls((np.asarray(data[0]), np.asarray(data[1]).reshape(-1)), likelihood, kernel, dtype=_STATE["dtype"], **extra)
+
+
+@create_model.register
+def _create_model_cglbn2m(model_cfg: CGLBN2MConfig, data: Data):
+    """CGLB with the N^2M log-det bound (tensorflow/interface.py:216-292 builds it from the same config fields).  One rank, fp64."""
+    _require_one_rank("cglbn2m")
+    return _create_cglb_variant(CGLBN2M, model_cfg, data)
+
+
+@create_model.register
+def _create_model_cglbnm2(model_cfg: CGLBNM2Config, data: Data):
+    """CGLB with the NM^2 log-det bound.  One rank."""
+    _require_one_rank("cglbnm2")
+    return _create_cglb_variant(CGLBNM2, model_cfg, data)
+
+
+@create_model.register
+def _create_model_sgpr(model_cfg: SGPRConfig, data: Data):
+    """SGPR (Titsias) on the same inducing-point initialisation as CGLB.  One rank."""
+    _require_one_rank("sgpr")
+    likelihood, kernel = _likelihood_and_kernel_for_sgpr(model_cfg, data)
+    return SGPR((np.asarray(data[0]), np.asarray(data[1]).reshape(-1)), likelihood, kernel, dtype=_STATE["dtype"])
+
+
+@create_model.register
+def _create_model_sgprn2m(model_cfg: SGPRN2MConfig, data: Data):
+    """SGPR with the N^2M log-det bound.  One rank, fp64."""
+    _require_one_rank("sgprn2m")
+    likelihood, kernel = _likelihood_and_kernel_for_sgpr(model_cfg, data)
+    return SGPRN2M((np.asarray(data[0]), np.asarray(data[1]).reshape(-1)), likelihood, kernel, dtype=_STATE["dtype"])
+
+
+def _require_one_rank(name: str):
+    """The bound variants run on one GPU: refused under a process group of more than one rank before any GPU work (the inducing-point
+    initialisation included)."""
+    import torch.distributed as dist
+    if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+        raise NotImplementedError(f"model class {name!r} is not available on more than one rank (only cglb runs row-sharded): "
+                                  f"run it as a single process")
+
+
 def _broadcast_parameters(model: CGLB):
     """N ranks: every rank built the model from the same data and config (the greedy inducing-point selection is deterministic); the
     initial parameters are broadcast from rank 0 all the same, so that the replicas start from identical bits by construction."""
@@ -323,6 +371,37 @@ def _optimize_cglb_impl(model: CGLB, dataset, num_steps: int, logger: Logger, op
     return results
 
 
+@optimize.register
+def _optimize_sgpr(model: SGPR, dataset, num_steps: int, logger: Logger, optimize: str = "scipy"):
+    """The same L-BFGS-B rounds as CGLB without the v bookkeeping (the TF backend trains every class this way,
+    tensorflow/interface.py:296-337)."""
+    assert optimize == "scipy"
+    with _narrow_host_pools():
+        lbfgs = Scipy()
+        bound = LowerBoundSGPR(model)
+
+        def closure() -> Tensor:
+            return -bound(None)
+
+        params = list(model.parameters())
+        with logger.no_recording():
+            torch.autograd.grad(closure(), params)
+            torch.cuda.synchronize()
+        logger.timer.reset()
+        logger.timer.start()
+        results, remaining = [], num_steps
+        for round_id in range(4):
+            if remaining <= 0:
+                break
+            if round_id == 2:
+                ips = model.covar_module.inducing_points
+                params = [p for p in model.parameters() if id(p) != id(ips)]
+            result = lbfgs.minimize(closure, params, options=dict(maxiter=remaining, ftol=0.0, gtol=0.0, disp=False), step_callback=logger)
+            remaining -= result.nit
+            results.append(result)
+        return results
+
+
 @save.register
 def _save(model: GPR, logdir: str):  # interface.py:546-551: json_tricks.dump(model_parameters(model)) -> same encoding (jsonio.py)
     os.makedirs(logdir, exist_ok=True)
@@ -382,6 +461,31 @@ def _compute_metrics_cglb(model: CGLB, dataset_bundle):
 
     rmse_lpd_metrics = metric.rmse_and_lpd_fn(error_and_logdensity)
     return lambda: metric.call_metric_fns(cglb_cg_params, cglb_metrics, rmse_lpd_metrics)
+
+
+@metrics_fn.register
+def _compute_metrics_sgpr(model: SGPR, dataset_bundle):
+    """tensorflow/interface.py:395-408 without titsias_upper_bound: loss = -elbo, and rmse / nlpd of the Titsias predictive."""
+    train, test = dataset_bundle
+
+    def sgpr_metrics():
+        with torch.no_grad():
+            elbo = _numpy(LowerBoundSGPR(model)(None))
+        return dict(elbo=elbo, loss=-elbo)
+
+    x_full = np.concatenate([np.asarray(train[0]), np.asarray(test[0])], axis=0)
+    y_full = np.concatenate([np.asarray(train[1]).reshape(-1), np.asarray(test[1]).reshape(-1)], axis=0).reshape(-1, 1)
+
+    def error_and_logdensity():
+        predict_f = PredictSGPR(model)
+        with torch.no_grad():
+            f_mean, f_var = predict_f(torch.as_tensor(x_full))
+            y = torch.as_tensor(y_full, dtype=f_mean.dtype, device=f_mean.device)
+            lpd, err = _numpy(log_density(model, y, f_mean, f_var)), _numpy(y - f_mean)
+        n = np.asarray(train[0]).shape[0]
+        return (err[:n], err[n:]), (lpd[:n], lpd[n:])
+
+    return lambda: metric.call_metric_fns(sgpr_metrics, metric.rmse_and_lpd_fn(error_and_logdensity))
 
 
 def _numpy(tensor) -> np.ndarray:

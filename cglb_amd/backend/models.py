@@ -139,37 +139,38 @@ class GPR(nn.Module):
         self.covar_module = kernel
 
 
+def _variant_context(model, data_x, data_y, num_inducing: int, kind: str, dtype, device, context):
+    """The HIP context of a model whose bound is not plain CGLB: one rank only (the N-rank path implements the Jensen / CG bound), with the
+    two bound options set on it (include/cglb_hip.h "logdet_bound", "quad_term")."""
+    name = type(model).__name__
+    if context is None:
+        import torch.distributed as dist
+        if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+            raise NotImplementedError(f"{name} is not available on more than one rank (only CGLB runs row-sharded); "
+                                      f"run it as a single process")
+        context = HipContext(data_x, data_y, num_inducing, kind, dtype=dtype, device=device)
+    elif getattr(context, "world", 1) > 1:
+        raise NotImplementedError(f"{name} is not available on more than one rank (only CGLB runs row-sharded)")
+    context.set_option("logdet_bound", model.LOGDET_BOUND)
+    context.set_option("quad_term", model.QUAD_TERM)
+    return context
+
+
 class SGPR(GPR):
-    ...
+    """Titsias' collapsed bound (tensorflow/models.py:353-413 with the NM^2 trace term): the exact quadratic term at v = 0 - no solve, no
+    N^2 work - and the log-det bound of option LOGDET_BOUND (1: NM^2, the SGPR ELBO; 2: N^2M, SGPRN2M).  Same module tree and parameter
+    keys as CGLB; no v_vec, no cg_stats."""
 
-
-class CGLB(SGPR):
-    """models.py:54-87: SGPR + the persistent warm-start vector v_vec (zeros[N,1], no grad) and cg_stats."""
+    LOGDET_BOUND = 1
+    QUAD_TERM = 1
 
     def __init__(self, data: Data, likelihood: GaussianLikelihood, kernel: InducingPointKernel, dtype: torch.dtype = torch.float64,
-                 device: Optional[torch.device] = None, max_error: Optional[float] = None, joint_optimization: bool = False,
-                 vzero: bool = False, context=None):
-        """`context`: the engine behind the model - by default `make_context` builds it: a `HipContext` in a single-process run, one rank
-        of a `DistHipContext` (rows of K_ff dealt over the ranks, collectives inside libcglb_hip.so) when a torch.distributed process
-        group with more than one rank is initialised; every rank then holds the full replicated `v_vec` and evaluates identical
-        (loss, gradient) pairs.  Tests inject `distributed.PyDistContext` here.
-        The three arguments before it are the TF twin's (tensorflow/models.py:31-51): the torch reference never passes them
-        (pytorch/interface.py:315-323) and neither does `create_model` unless `configure_backend(config_semantics="tf")`.
-        `max_error` becomes the default tolerance of `LowerBoundCG`; `joint_optimization` (without `vzero`) makes `v_vec` a trainable
-        parameter and skips CG; `vzero` keeps v = 0 and skips CG (tensorflow/models.py:161-164)."""
+                 device: Optional[torch.device] = None, context=None):
         super().__init__(data, likelihood, kernel)
         self.dtype = dtype
-        self.max_error, self.joint_optimization, self.vzero = max_error, bool(joint_optimization), bool(vzero)
         kind = kernel.base_kernel.base_kernel.kind
-        if context is None:
-            context = make_context(self.train_inputs[0], self.train_targets, kernel.inducing_points.shape[0], kind, dtype=dtype, device=device)
-        self.hip = context
-        if getattr(context, "world", 1) > 1 and self.joint_optimization and not self.vzero:
-            raise NotImplementedError("joint optimisation of v (the TF twin's opt-in) is not available on more than one rank")
-        v0 = self._build_v_vec()
-        # v0 trainable only under joint optimisation (tensorflow/models.py:47-48); otherwise a plain buffer without grad (models.py:59-68)
-        self._v_vec = nn.Parameter(v0) if (self.joint_optimization and not self.vzero) else v0
-        self._hyper_token = None
+        self.hip = _variant_context(self, self.train_inputs[0], self.train_targets, kernel.inducing_points.shape[0], kind, dtype, device, context)
+        self._zero_v = torch.zeros(self.hip.N, dtype=dtype, device=self.hip.device)  # the library treats v as 0 (quad_term 1); shape check only
 
     def check_same_data(self, data: Data) -> None:
         """ValueError unless (x, y) is the training set the HIP context was built on (same shapes and content).  The full comparison
@@ -198,6 +199,56 @@ class CGLB(SGPR):
         except TypeError:  # lists / scalars cannot be weakly referenced: compared in full every time
             self._accepted_data = None
 
+    # constrained hyper-parameters, as tensors attached to the raw parameters
+    def hyper_tensors(self):
+        k = self.covar_module
+        return (k.base_kernel.base_kernel.lengthscale.reshape(-1), k.base_kernel.outputscale.reshape(()),
+                self.likelihood.noise.reshape(()), self.mean_module.constant.reshape(()), k.inducing_points)
+
+    def push_hypers(self, jitter: float):
+        ls, var, noise, mean, Z = [t.detach() for t in self.hyper_tensors()]
+        self.hip.set_hypers(ls.cpu().numpy(), float(var), float(noise), float(mean), Z.cpu(), jitter)
+
+
+class SGPRN2M(SGPR):
+    """SGPR with the N^2M log-det bound (tensorflow/models.py:353-413): one N^2 M pass per evaluation (kernels_n2m.hip), fp64 only."""
+
+    LOGDET_BOUND = 2
+
+
+class CGLB(SGPR):
+    """models.py:54-87: SGPR + the persistent warm-start vector v_vec (zeros[N,1], no grad) and cg_stats."""
+
+    LOGDET_BOUND = 0   # Jensen (models.py:215-244); QUAD_TERM 0: the CG quadratic term.  Plain CGLB leaves the options untouched
+    QUAD_TERM = 0
+
+    def __init__(self, data: Data, likelihood: GaussianLikelihood, kernel: InducingPointKernel, dtype: torch.dtype = torch.float64,
+                 device: Optional[torch.device] = None, max_error: Optional[float] = None, joint_optimization: bool = False,
+                 vzero: bool = False, context=None):
+        """`context`: the engine behind the model - by default `make_context` builds it: a `HipContext` in a single-process run, one rank
+        of a `DistHipContext` (rows of K_ff dealt over the ranks, collectives inside libcglb_hip.so) when a torch.distributed process
+        group with more than one rank is initialised; every rank then holds the full replicated `v_vec` and evaluates identical
+        (loss, gradient) pairs.  Tests inject `distributed.PyDistContext` here.
+        The three arguments before it are the TF twin's (tensorflow/models.py:31-51): the torch reference never passes them
+        (pytorch/interface.py:315-323) and neither does `create_model` unless `configure_backend(config_semantics="tf")`.
+        `max_error` becomes the default tolerance of `LowerBoundCG`; `joint_optimization` (without `vzero`) makes `v_vec` a trainable
+        parameter and skips CG; `vzero` keeps v = 0 and skips CG (tensorflow/models.py:161-164)."""
+        GPR.__init__(self, data, likelihood, kernel)
+        self.dtype = dtype
+        self.max_error, self.joint_optimization, self.vzero = max_error, bool(joint_optimization), bool(vzero)
+        kind = kernel.base_kernel.base_kernel.kind
+        if self.LOGDET_BOUND != 0:   # a log-det ablation: one rank, the option set on the context
+            context = _variant_context(self, self.train_inputs[0], self.train_targets, kernel.inducing_points.shape[0], kind, dtype, device, context)
+        elif context is None:
+            context = make_context(self.train_inputs[0], self.train_targets, kernel.inducing_points.shape[0], kind, dtype=dtype, device=device)
+        self.hip = context
+        if getattr(context, "world", 1) > 1 and self.joint_optimization and not self.vzero:
+            raise NotImplementedError("joint optimisation of v (the TF twin's opt-in) is not available on more than one rank")
+        v0 = self._build_v_vec()
+        # v0 trainable only under joint optimisation (tensorflow/models.py:47-48); otherwise a plain buffer without grad (models.py:59-68)
+        self._v_vec = nn.Parameter(v0) if (self.joint_optimization and not self.vzero) else v0
+        self._hyper_token = None
+
     def _build_v_vec(self) -> Tensor:  # models.py:59-68
         return torch.zeros((self.hip.N, 1), dtype=self.dtype, device=self.hip.device, requires_grad=False)
 
@@ -218,15 +269,16 @@ class CGLB(SGPR):
             error = error.detach().cpu().numpy()
         self._cg_stats = ConjugateGradientStats(steps, error)
 
-    # constrained hyper-parameters, as tensors attached to the raw parameters
-    def hyper_tensors(self):
-        k = self.covar_module
-        return (k.base_kernel.base_kernel.lengthscale.reshape(-1), k.base_kernel.outputscale.reshape(()),
-                self.likelihood.noise.reshape(()), self.mean_module.constant.reshape(()), k.inducing_points)
+class CGLBN2M(CGLB):
+    """CGLB with the N^2M log-det bound (tensorflow/models.py:311-350): one N^2 M pass per setup, one more per gradient, fp64 only."""
 
-    def push_hypers(self, jitter: float):
-        ls, var, noise, mean, Z = [t.detach() for t in self.hyper_tensors()]
-        self.hip.set_hypers(ls.cpu().numpy(), float(var), float(noise), float(mean), Z.cpu(), jitter)
+    LOGDET_BOUND = 2
+
+
+class CGLBNM2(CGLB):
+    """CGLB with the NM^2 log-det bound log|Q_ff + s I| + tr(K_ff - Q_ff)/s (tensorflow/models.py:271-308)."""
+
+    LOGDET_BOUND = 1
 
 
 @dataclass
@@ -400,3 +452,63 @@ def gaussian(x, mu, var):  # models.py:375-379
     pi2 = math.log(2 * math.pi)
     x = x.reshape(*mu.shape)
     return -0.5 * (pi2 + torch.log(var) + (mu - x) ** 2 / var)
+
+
+class _SGPRBoundFunction(torch.autograd.Function):
+    """bound(lengthscales, variance, noise, mean, Z) of the SGPR family with the analytic gradient from the GPU (no v, no solve)."""
+
+    @staticmethod
+    def forward(ctx, model, ls, var, noise, mean, Z):
+        hip = model.hip
+        hip.set_hypers(ls.detach().cpu().numpy(), float(var), float(noise), float(mean), Z.detach().cpu(), get_cholesky_jitter())
+        res = hip.objective_and_grad(model._zero_v, False, with_grad=any(ctx.needs_input_grad[1:]))
+        model.last_bound = float(res.bound)
+        ctx.grads = res.grad
+        return torch.tensor(res.bound, dtype=torch.float64)
+
+    @staticmethod
+    def backward(ctx, gout):
+        g = ctx.grads
+        if g is None:
+            raise RuntimeError("gradient was not requested in forward")
+        gout = gout.to(torch.float64)
+        return (None, gout * torch.from_numpy(g["lengthscales"]), gout * g["variance"], gout * g["noise"], gout * g["mean"],
+                gout * torch.from_numpy(g["Z"]))
+
+
+class LowerBoundSGPR(nn.Module):
+    """`LowerBoundSGPR(model)(data)`: the collapsed bound of an SGPR / SGPRN2M model (tensorflow/models.py:353-413), the `elbo` of the TF
+    twin.  `data` must be None or the model's own training set, as for LowerBoundCG."""
+
+    def __init__(self, model: SGPR):
+        if not isinstance(model, SGPR) or isinstance(model, CGLB):
+            raise ValueError(f"SGPR model expected in the constructor of the {self.__class__}")
+        super().__init__()
+        object.__setattr__(self, "model", model)
+
+    def forward(self, data: Optional[Tuple[Tensor, Tensor]] = None) -> Tensor:
+        if data is not None:
+            self.model.check_same_data(data)
+        ls, var, noise, mean, Z = self.model.hyper_tensors()
+        return _SGPRBoundFunction.apply(self.model, ls, var, noise, mean, Z)
+
+
+class PredictSGPR(nn.Module):
+    """Titsias' predictive: PredictCG's formula (models.py:333-354) at v = 0, without a solve (cg_mean = 0, res = e)."""
+
+    def __init__(self, model: SGPR):
+        super().__init__()
+        object.__setattr__(self, "model", model)
+        self.cached = False
+
+    def forward(self, xnew: Tensor, full_cov: bool = False, full_output_cov: bool = False) -> Tuple[Tensor, Tensor]:
+        if full_cov:
+            raise NotImplementedError("The predict_f method currently  supports only `full_cov=False` option")
+        model, hip = self.model, self.model.hip
+        with torch.no_grad():
+            if not self.cached:
+                model.push_hypers(get_cholesky_jitter())
+                hip.setup()
+                self.cached = True
+            f_mean, f_var = hip.predict(model._zero_v, xnew)
+        return f_mean.reshape(-1, 1), f_var.reshape(-1, 1)

@@ -3,6 +3,9 @@ that exercise the hot path:
 
     python -m cglb_amd.cli -b hip -t fp64 -l LOGDIR -s SEED train -d DATASET -n STEPS cglb -k Matern32 -m cglb -i cv -M 1024
     python -m cglb_amd.cli -b hip -t fp64 -l LOGDIR metric -d DATASET cglb -k Matern32 -m cglb -i cv -M 1024 -p LOGDIR/model.json
+    python -m cglb_amd.cli -b hip -t fp64 -l LOGDIR train -d DATASET -n STEPS sgpr -k Matern32 -m sgpr -i cv -M 1024
+
+`cglb -m` takes cglb | cglbn2m | cglbnm2, `sgpr -m` takes sgpr | sgprn2m (cli.py:203-209, :304-310; these four run on one rank).
 
 Same option letters as cli.py:60-65, :141-152, :207-216; writes model.json / results.json / logs.json with the reference's keys
 (cli.py:100-109, pytorch/interface.py:546-551).  Datasets: the reference downloads UCI sets through robustgp_experiments
@@ -196,21 +199,50 @@ def _cglb_command(group):
     @click.pass_context
     def cglb(ctx, model_class, kernel, inducing_variable, num_inducing_variables, param_file, max_error, vjoint, vzero):
         """cli.py:259-273 (_execute_cb_cglb)"""
-        o = ctx.obj
+        if model_class not in CGLB_CLASSES:
+            raise click.UsageError(f"model class {model_class!r} takes no -e/--vjoint/--vzero: use the `sgpr` command "
+                                   f"(... {ctx.parent.info_name} sgpr -m {model_class} -k KERNEL -i IV -M M)", ctx=ctx)
         cfg = SGPR_CONFIGS[model_class](KERNEL_CONFIGS[kernel](), INDUCING_VARIABLE_CONFIGS[inducing_variable](num_inducing_variables),
                                         max_error, vjoint, vzero)
-        model = o["backend"].create_model(cfg, o["dataset"].train)
-        if param_file:
-            model = o["backend"].load(model, param_file)
-        results = o["callback"](model)
-        if _rank() == 0:
-            click.echo(json.dumps(_jsonable(results)))
+        _run_model(ctx, cfg, param_file)
 
     return cglb
 
 
+def _run_model(ctx, cfg, param_file):
+    o = ctx.obj
+    model = o["backend"].create_model(cfg, o["dataset"].train)
+    if param_file:
+        model = o["backend"].load(model, param_file)
+    results = o["callback"](model)
+    if _rank() == 0:
+        click.echo(json.dumps(_jsonable(results)))
+
+
+CGLB_CLASSES = ("cglb", "cglbn2m", "cglbnm2")   # SGPR_CONFIGS entries built from CGLBConfig (max_error, vjoint, vzero)
+SGPR_CLASSES = ("sgpr", "sgprn2m")
+
+
+def _sgpr_command(group):
+    @group.command("sgpr")
+    @click.option("-m", "--model-class", type=click.Choice(sorted(SGPR_CLASSES)), required=True)
+    @click.option("-k", "--kernel", type=click.Choice(sorted(KERNEL_CONFIGS)), required=True)
+    @click.option("-i", "--inducing-variable", type=click.Choice(sorted(INDUCING_VARIABLE_CONFIGS)), required=True)
+    @click.option("-M", "--num-inducing-variables", default=100, type=int)
+    @click.option("-p", "--param_file", type=click.Path(readable=True))
+    @click.pass_context
+    def sgpr(ctx, model_class, kernel, inducing_variable, num_inducing_variables, param_file):
+        """cli.py:203-209, :304-310 (_execute_cb_sgpr): SGPR / SGPRN2M on the same inducing-point initialisation as cglb"""
+        cfg = SGPR_CONFIGS[model_class](KERNEL_CONFIGS[kernel](), INDUCING_VARIABLE_CONFIGS[inducing_variable](num_inducing_variables))
+        _run_model(ctx, cfg, param_file)
+
+    return sgpr
+
+
 _cglb_command(train)
 _cglb_command(metric)
+_sgpr_command(train)
+_sgpr_command(metric)
 
 if __name__ == "__main__":
     main()

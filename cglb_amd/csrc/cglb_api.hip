@@ -94,6 +94,23 @@ __global__ void grad_scalar_terms_kernel(double* __restrict__ out, int D, const 
     out[D + 2] += sc[4];
 }
 
+// the same for the N^2M log-det bound (logdet_bound 2): -N/2 log(tau/N), tau = N (f + s) - T, T = tr(B^-1 A K~ A^T) (models: see n2m_setup).
+// The -N/2 log s of the Jensen and NM^2 forms is absent: it cancels against the N log s inside the log-trace (tensorflow/models.py:341-347).
+// k = N / tau:  d/df = -k N / 2 + (k/2) <B^-1, H> / f ;  d/ds = -k N / 2 + (k/2)(M - tr B^-1) - k tr(E) / (2 s)  (the last: A ~ s^-1/2)
+__global__ void grad_scalar_terms_n2m_kernel(double* __restrict__ out, int D, const double* __restrict__ sc, const double* __restrict__ trBinv,
+                                             const double* __restrict__ trE, double N, double M, double f, double s, double tau, double BH) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    const double k = N / tau;
+    out[D] += sc[5] / f - 0.5 * k * N + 0.5 * k * BH / f;
+    out[D + 1] += sc[2] + 0.5 * sc[3] + (M - trBinv[0]) / (2.0 * s) - 0.5 * k * N + 0.5 * k * (M - trBinv[0]) - k * trE[0] / (2.0 * s);
+    out[D + 2] += sc[4];
+}
+
+// out[d] += a * g[d] / l[d]   (kernel-hyper-parameter part of the N^2M gradient)
+__global__ void add_scaled_by_ls_kernel(double* __restrict__ out, int D, double a, const double* __restrict__ g, const double* __restrict__ ls) {
+    for (int d = threadIdx.x; d < D; d += blockDim.x) out[d] += a * g[d] / ls[d];
+}
+
 // prediction epilogue: per new point n
 //   mean[n] = cg_mean[n] + sum_m tmp2[m][n] c[m] + mu ; var[n] = f + sum tmp2^2 - sum tmp1^2    (models.py:347-351)
 template <typename T>
@@ -284,6 +301,7 @@ int setup_finish_impl(cglb_ctx* c) {
     if (info[1] != 0) return cglb_fail(c, CGLB_ERR_NOT_PD, "inverse of LB failed: zero pivot " + std::to_string(info[1]));
     c->trace_AAt = sc[0];
     c->sum_log_diag_LB = sc[1];
+    if (c->logdet_bound == 2) CGLB_TRY(n2m_setup(c));  // the N^2M bound needs tr(C K~ C^T) as part of its value (kernels_n2m.hip)
     c->have_terms = true;
     return CGLB_OK;
 }
@@ -401,6 +419,31 @@ int obj_phase1_reuse(cglb_ctx* c, void* u_partial) {
     return CGLB_OK;
 }
 
+// Phase 1 of the exact quadratic term (quad_term 1, tensorflow/models.py:393-402): v = 0, so K v = 0 and r = e without any N^2 work;
+// 1/2 r^T P r = |e|^2/(2 s) - |LB^-1 A e|^2/(2 s) is then the SGPR data term, P being the Woodbury inverse of Q_ff + s I.
+int obj_phase1_exact(cglb_ctx* c, void* u_partial) {
+    const char* y_loc = (const char*)c->y + (size_t)c->r0 * c->esz;
+    CGLB_TRY(launch_sub_scalar(c, c->w_e, y_loc, c->mean, c->nloc));
+    HIP_CHECK(c, hipMemsetAsync(c->w_Kv, 0, (size_t)c->nloc * c->esz, c->stream));
+    HIP_CHECK(c, hipMemcpyAsync(c->w_r, c->w_e, (size_t)c->nloc * c->esz, hipMemcpyDeviceToDevice, c->stream));
+    return precond_u_any(c, c->w_r, u_partial);
+}
+
+// the v of the exact quadratic term: a device vector of N zeros, made once
+int ensure_zero_vec(cglb_ctx* c) {
+    if (c->w_zero) return CGLB_OK;
+    CGLB_TRY(dalloc(c, &c->w_zero, (size_t)c->N * c->esz));
+    HIP_CHECK(c, hipMemsetAsync(c->w_zero, 0, (size_t)c->N * c->esz, c->stream));
+    return CGLB_OK;
+}
+
+// non-default bound options: one shard covering all rows, one rank
+int require_variant_ok(cglb_ctx* c) {
+    if (c->logdet_bound == 0 && c->quad_term == 0) return CGLB_OK;
+    if (c->par_world > 1 || c->comm) return cglb_fail(c, CGLB_ERR_BAD_ARG, "logdet_bound / quad_term other than 0 are not available on more than one rank");
+    return CGLB_OK;
+}
+
 int obj_phase2(cglb_ctx* c, const void* v_full, const void* u, double* sc_partial, void* aw_partial) {
     const char* v_loc = (const char*)v_full + (size_t)c->r0 * c->esz;
     CGLB_TRY(launch_tri_apply(c, u, c->w_t));
@@ -429,7 +472,10 @@ template <typename T>
 int obj_phase3_impl(cglb_ctx* c, const void* v_full, const double* sc, const void* aw, double* out, const void* u_full_cyclic = nullptr) {
     const int M = c->M, D = c->D;
     const size_t glen = (size_t)CGLB_GRAD_LEN(D, M);
-    const double s = c->noise, f = c->var, sigma = std::sqrt(s), tau = tau_of(c);
+    // tau: the Jensen factor 1 + t/N of the trace term; the NM^2 bound has the trace term itself, factor 1 (logdet_bound 1)
+    const double s = c->noise, f = c->var, sigma = std::sqrt(s), tau = c->logdet_bound == 1 ? 1.0 : tau_of(c);
+    const bool n2m = c->logdet_bound == 2;
+    const double kn = n2m ? (double)c->N / c->n2m_tau : 0.0;  // d logdet / dT = N / (2 tau) of the N^2M bound, times 2
     const T one = 1, zero = 0;
     HIP_CHECK(c, hipMemsetAsync(out, 0, glen * sizeof(double), c->stream));
     if (!c->Guf) CGLB_TRY(dalloc(c, &c->Guf, (size_t)M * c->lda * c->esz));
@@ -437,6 +483,7 @@ int obj_phase3_impl(cglb_ctx* c, const void* v_full, const double* sc, const voi
     BLAS_CHECK(c, xgemm(c->blas, rocblas_operation_transpose, rocblas_operation_none, M, M, M, &one, (const T*)c->LBinv, M, (const T*)c->LBinv, M,
                         &zero, (T*)c->Mtmp, M));
     hipLaunchKernelGGL((trace_kernel<T>), dim3(1), dim3(256), 0, c->stream, (const T*)c->Mtmp, M, c->scal + S_TRBINV);
+    if (n2m) CGLB_TRY(n2m_grad_terms(c, (const double*)c->Mtmp));  // E = B^-1 A K~ A^T B^-1 and sum_ij G_ij dK_ij/dl (kernels_n2m.hip)
     // c = Kuu^-1 Kuf w = sigma L^-T (A w); mhalf = -c/2
     // grad_trsm: 0 products with the explicit L^-1; 1 rocBLAS trsm / trsv; 2 (default) the products followed by ONE step of iterative
     // refinement against L itself (x += L^-1 (b - L x): two more M^3 GEMMs per solve, ~50 us each at M = 1024, against 270 us for a
@@ -463,8 +510,14 @@ int obj_phase3_impl(cglb_ctx* c, const void* v_full, const double* sc, const voi
     hipLaunchKernelGGL((scale2_kernel<T>), dim3(grid1d(M)), dim3(256), 0, c->stream, (const T*)c->w_t2, (int64_t)M, (T)sigma, (T*)c->w_t2,
                        (T)(-0.5 * sigma), (T*)c->w_t);
     // Guf = (1/sigma) L^-T (I/tau - B^-1) A   (+ c w^T applied on the fly)
-    hipLaunchKernelGGL((mat_combine_kernel<T>), dim3(grid1d_full((int64_t)M * M)), dim3(256), 0, c->stream, (T*)c->Mtmp2, M, (T)(1.0 / tau), (T)-1,
-                       (const T*)c->Mtmp, (T)0, (const T*)nullptr);
+    // N^2M: the A-adjoint of T = tr(B^-1 A K~ A^T) is 2 (B^-1 A K~ - E A) with A K~ = W^T + s A, so
+    //       Guf = (1/sigma) L^-T [(-B^-1 + k s B^-1 - k E) A + k B^-1 W^T],  k = N / tau  (the second product is added below)
+    if (n2m)
+        hipLaunchKernelGGL((mat_combine_kernel<T>), dim3(grid1d_full((int64_t)M * M)), dim3(256), 0, c->stream, (T*)c->Mtmp2, M, (T)0, (T)(kn * s - 1.0),
+                           (const T*)c->Mtmp, (T)(-kn), (const T*)c->n2m_E);
+    else
+        hipLaunchKernelGGL((mat_combine_kernel<T>), dim3(grid1d_full((int64_t)M * M)), dim3(256), 0, c->stream, (T*)c->Mtmp2, M, (T)(1.0 / tau), (T)-1,
+                           (const T*)c->Mtmp, (T)0, (const T*)nullptr);
     const T inv_sigma = (T)(1.0 / sigma);
     const T* Tuf = (const T*)c->Mtmp2;  // (1/sigma) L^-T (I/tau - B^-1)
     if (use_inv) {
@@ -486,8 +539,16 @@ int obj_phase3_impl(cglb_ctx* c, const void* v_full, const double* sc, const voi
     if (c->nloc > 0) {
         BLAS_CHECK(c, xgemm(c->blas, rocblas_operation_none, rocblas_operation_transpose, (int)c->nloc, M, M, &one, (const T*)c->At, (int)c->lda,
                             Tuf, M, &zero, (T*)c->Guf, (int)c->lda));
+        if (n2m) {  // + W (k/sigma) B^-1 L^-1 : the k B^-1 W^T part of Guf (fp64 only)
+            const double ks = kn / sigma, d_one = 1.0;
+            HIP_CHECK(c, hipMemcpyAsync(c->n2m_T, c->Mtmp, (size_t)M * M * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+            BLAS_CHECK(c, rocblas_dtrsm(c->blas, rocblas_side_left, rocblas_fill_lower, rocblas_operation_transpose, rocblas_diagonal_non_unit, M, M, &ks,
+                                        (const double*)c->Lc, M, c->n2m_T, M));
+            BLAS_CHECK(c, rocblas_dgemm(c->blas, rocblas_operation_none, rocblas_operation_transpose, (int)c->nloc, M, M, &d_one, c->n2m_Wt, (int)c->lda,
+                                        c->n2m_T, M, &d_one, (double*)c->Guf, (int)c->lda));
+        }
         CGLB_TRY(launch_grad_kuf(c, c->w_t2, c->w_z, out));
-        if (!u_full_cyclic) {
+        if (!u_full_cyclic && c->quad_term == 0) {  // the exact quadratic term sits at v = 0: -(w + v/2)^T dK v vanishes
             // u = w + v/2 ; N^2 bilinear pass over the local rows
             const T* v_loc = (const T*)v_full + c->r0;
             hipLaunchKernelGGL((axpby_kernel<T>), dim3(grid1d(c->nloc)), dim3(256), 0, c->stream, (T*)c->w_Ap, (T)1, (const T*)c->w_z, (T)0.5, v_loc,
@@ -504,8 +565,9 @@ int obj_phase3_impl(cglb_ctx* c, const void* v_full, const double* sc, const voi
     }
     if (c->r0 == 0) {
         // Guu = L^-T [ (I - B^-1)/2 - (AA^T)/(2 tau) ] L^-1  - c c^T/2
+        // N^2M: the trace part is -(k/2) E in place of -(AA^T)/(2 tau)  (A-adjoint Abar with A Abar^T = k E, symmetric)
         hipLaunchKernelGGL((mat_combine_kernel<T>), dim3(grid1d_full((int64_t)M * M)), dim3(256), 0, c->stream, (T*)c->Mtmp, M, (T)0.5, (T)-0.5,
-                           (const T*)c->Mtmp, (T)(-0.5 / tau), (const T*)c->AAt);
+                           (const T*)c->Mtmp, (T)(n2m ? -0.5 * kn : -0.5 / tau), n2m ? (const T*)c->n2m_E : (const T*)c->AAt);
         if (use_inv) {  // L^-T S L^-1 as two GEMMs (each followed by its refinement step)
             const size_t mm = (size_t)M * M * c->esz;
             BLAS_CHECK(c, xgemm(c->blas, rocblas_operation_transpose, rocblas_operation_none, M, M, M, &one, (const T*)c->Linv, M,
@@ -533,8 +595,15 @@ int obj_phase3_impl(cglb_ctx* c, const void* v_full, const double* sc, const voi
                                 (const T*)c->Lc, M, (T*)c->Mtmp, M));
         }
         CGLB_TRY(launch_grad_kuu(c, c->Mtmp, c->w_t2, c->w_t, out));
-        hipLaunchKernelGGL(grad_scalar_terms_kernel, dim3(1), dim3(64), 0, c->stream, out, D, sc, (const double*)(c->scal + S_TRBINV), (double)c->N,
-                           (double)M, f, s, tau, c->trace_AAt);
+        if (n2m) {
+            hipLaunchKernelGGL(grad_scalar_terms_n2m_kernel, dim3(1), dim3(64), 0, c->stream, out, D, sc, (const double*)(c->scal + S_TRBINV),
+                               (const double*)(c->n2m_scal + 3), (double)c->N, (double)M, f, s, c->n2m_tau, c->n2m_BH);
+            hipLaunchKernelGGL(add_scaled_by_ls_kernel, dim3(1), dim3(64), 0, c->stream, out, D, 0.5 * kn, (const double*)c->n2m_gacc,
+                               (const double*)c->n2m_ls);
+        } else {
+            hipLaunchKernelGGL(grad_scalar_terms_kernel, dim3(1), dim3(64), 0, c->stream, out, D, sc, (const double*)(c->scal + S_TRBINV), (double)c->N,
+                               (double)M, f, s, tau, c->trace_AAt);
+        }
     }
     CGLB_LAUNCH_CHECK(c);
     return CGLB_OK;
@@ -542,6 +611,10 @@ int obj_phase3_impl(cglb_ctx* c, const void* v_full, const double* sc, const voi
 
 double logdet_value(const cglb_ctx* c) {
     const double N = (double)c->N;
+    if (c->logdet_bound == 1)  // NM^2: -(log|Q_ff + s I|/2 + tr(K_ff - Q_ff)/(2 s))  (tensorflow/models.py:295-308)
+        return -c->sum_log_diag_LB - 0.5 * N * std::log(c->noise) - 0.5 * (N * c->var / c->noise - c->trace_AAt);
+    if (c->logdet_bound == 2)  // N^2M: -(sum log diag LB + N/2 log s + N/2 (log tau - log N - log s))  (tensorflow/models.py:339-350)
+        return -c->sum_log_diag_LB - 0.5 * N * std::log(c->n2m_tau / N);
     return -c->sum_log_diag_LB - 0.5 * N * std::log(c->noise) - 0.5 * N * std::log(tau_of(c));  // models.py:236-243
 }
 
@@ -645,6 +718,8 @@ void comm_free(cglb_ctx* c) {
 
 int comm_alloc(cglb_ctx* c, int world, int rank) {
     if (world < 1 || rank < 0 || rank >= world) return cglb_fail(c, CGLB_ERR_BAD_ARG, "bad world/rank");
+    if (c->logdet_bound != 0 || c->quad_term != 0)
+        return cglb_fail(c, CGLB_ERR_BAD_ARG, "logdet_bound / quad_term other than 0 are not available on more than one rank");
     const int64_t per = (c->N + world - 1) / world;
     const int64_t r0 = std::min<int64_t>((int64_t)rank * per, c->N), r1 = std::min<int64_t>((int64_t)(rank + 1) * per, c->N);
     if (c->r0 != r0 || c->r1 != r1)
@@ -847,9 +922,10 @@ int cglb_ctx_destroy(cglb_ctx* c) {
     if (c->stream) (void)hipStreamSynchronize(c->stream); else (void)hipDeviceSynchronize();
     comm_free(c);
     wide_free(c);
+    n2m_free(c);
     void* ptrs[] = {c->X, c->y, c->Z, c->Xs, c->xa, c->Zs, c->za, c->Xh, c->Xhsq, c->xah, c->wh, c->pwh, c->exp_tab, c->At, c->Lc, c->LBc, c->LBinv, c->LBinvT, c->AAt, c->Mtmp, c->Mtmp2, c->Mtmp3, c->Guf,
                     c->info_dev, c->w_r, c->w_z, c->w_p, c->w_Ap, c->w_Kv, c->w_e, c->w_pfull, c->w_u, c->w_t, c->w_t2, c->kpart, c->tpart,
-                    c->dotpart, c->scal, c->gpart, c->gradbuf, c->slabs, c->fragA, c->fragB, c->sym_items, c->Zh, c->zah, c->Linv, c->LinvT, c->w_q, c->ppart, c->chol_blk, c->uwh, c->Mtmp4};
+                    c->dotpart, c->scal, c->gpart, c->gradbuf, c->slabs, c->fragA, c->fragB, c->sym_items, c->Zh, c->zah, c->Linv, c->LinvT, c->w_q, c->ppart, c->chol_blk, c->uwh, c->Mtmp4, c->w_zero};
     for (void* p : ptrs) if (p) (void)hipFree(p);
     for (hipEvent_t ev : c->k1_events) (void)hipEventDestroy(ev);
     for (hipEvent_t ev : c->eval_events) (void)hipEventDestroy(ev);
@@ -891,7 +967,31 @@ int cglb_set_option(cglb_ctx* c, const char* name, int64_t value) {
     else if (!strcmp(name, "wide_reg")) { c->wide_reg = (int)value; c->pwh_src = nullptr; }
     else if (!strcmp(name, "chol_mode")) c->chol_mode = (int)value;
     else if (!strcmp(name, "grad_trsm")) c->grad_trsm = (int)value;
-    else if (!strcmp(name, "precond_mode")) { c->precond_mode = (int)value; c->have_local = c->have_terms = false; }
+    else if (!strcmp(name, "precond_mode")) {
+        if (value != 0 && c->logdet_bound == 2) return cglb_fail(c, CGLB_ERR_BAD_ARG, "logdet_bound 2 (N^2M) needs the stored panel A: precond_mode must stay 0");
+        c->precond_mode = (int)value; c->have_local = c->have_terms = false;
+    }
+    else if (!strcmp(name, "n2m_tile")) {  // edge of the K_ff tiles of the N^2M pass: a multiple of 64, 0 = the default (4096, or N if smaller)
+        if (value < 0 || value % 64 != 0 || value > 16384) return cglb_fail(c, CGLB_ERR_BAD_ARG, "n2m_tile must be a multiple of 64 up to 16384 (0: default)");
+        n2m_free(c);
+        c->n2m_tile = value;
+        c->have_terms = false;
+    }
+    else if (!strcmp(name, "logdet_bound") || !strcmp(name, "quad_term")) {
+        const bool ld = name[0] == 'l';
+        if (value < 0 || value > (ld ? 2 : 1))
+            return cglb_fail(c, CGLB_ERR_BAD_ARG, ld ? "logdet_bound must be 0 (Jensen), 1 (NM^2) or 2 (N^2M)" : "quad_term must be 0 (CG) or 1 (exact)");
+        if (value != 0 && (c->par_world > 1 || c->comm))
+            return cglb_fail(c, CGLB_ERR_BAD_ARG, std::string(name) + " other than 0 is not available on more than one rank");
+        if (ld && value == 2) {
+            if (c->dtype != CGLB_F64)  // tau is the difference of two traces of size N (f + s): fp32 cannot resolve it
+                return cglb_fail(c, CGLB_ERR_BAD_ARG, "logdet_bound 2 (N^2M) needs an fp64 context: tau = tr K~ - tr(C K~ C^T) cancels in fp32");
+            if (c->precond_mode != 0) return cglb_fail(c, CGLB_ERR_BAD_ARG, "logdet_bound 2 (N^2M) needs the stored panel A (precond_mode 0)");
+            if (c->r0 != 0 || c->r1 != c->N) return cglb_fail(c, CGLB_ERR_BAD_ARG, "logdet_bound 2 (N^2M) needs a single shard covering all rows");
+        }
+        if (ld) { if (c->logdet_bound != (int)value) c->have_terms = false; c->logdet_bound = (int)value; }
+        else c->quad_term = (int)value;
+    }
     else return cglb_fail(c, CGLB_ERR_BAD_ARG, std::string("unknown option ") + name);
     return CGLB_OK;
 }
@@ -1003,6 +1103,7 @@ int cglb_setup(cglb_ctx* c) {
 int cglb_logdet(cglb_ctx* c, double* logdet) {
     if (!c || !logdet) return CGLB_ERR_BAD_ARG;
     CGLB_TRY(require_terms(c));
+    CGLB_TRY(require_variant_ok(c));
     *logdet = logdet_value(c);
     return CGLB_OK;
 }
@@ -1123,6 +1224,8 @@ int cglb_shard_update_p(cglb_ctx* c, void* p_local, const void* z_local, const v
 // ---- cyclic-symmetric multi-GPU path (include/cglb_hip.h) ---------------------------------------------------------
 int cglb_set_parallel(cglb_ctx* c, int world, int rank) {
     if (!c || world < 1 || rank < 0 || rank >= world) return c ? cglb_fail(c, CGLB_ERR_BAD_ARG, "bad world/rank") : CGLB_ERR_BAD_ARG;
+    if (world > 1 && (c->logdet_bound != 0 || c->quad_term != 0))
+        return cglb_fail(c, CGLB_ERR_BAD_ARG, "logdet_bound / quad_term other than 0 are not available on more than one rank");
     c->par_world = world;
     c->par_rank = rank;
     return CGLB_OK;
@@ -1228,6 +1331,13 @@ int cglb_objective_and_grad(cglb_ctx* c, void* v_inout, int run_cg, double max_e
     if (!c || !v_inout || !out4) return c ? cglb_fail(c, CGLB_ERR_BAD_ARG, "NULL argument") : CGLB_ERR_BAD_ARG;
     c->obj_valid = false;
     CGLB_TRY(require_single(c));
+    CGLB_TRY(require_variant_ok(c));
+    const bool exact = c->quad_term == 1;
+    if (exact) {  // v = 0 and no solve (the caller's v is left as it is)
+        CGLB_TRY(ensure_zero_vec(c));
+        run_cg = 0;
+    }
+    void* v_eval = exact ? c->w_zero : v_inout;
     if (c->eval_profile && c->eval_events_used + 5 > 5 * 512) CGLB_TRY(eval_collect(c));  // bounded pool
     CGLB_TRY(eval_mark(c));
     CGLB_TRY(cglb_setup(c));                                                        // models.py:155
@@ -1241,12 +1351,13 @@ int cglb_objective_and_grad(cglb_ctx* c, void* v_inout, int run_cg, double max_e
     }
     CGLB_TRY(eval_mark(c));
     double* sc = c->scal + S_SC;
-    if (run_cg && !c->final_matvec) CGLB_TRY(obj_phase1_reuse(c, c->w_u));
-    else CGLB_TRY(obj_phase1(c, v_inout, c->w_u));
-    CGLB_TRY(obj_phase2(c, v_inout, c->w_u, sc, c->w_u));  // aw overwrites u after u has been consumed (stream order)
+    if (exact) CGLB_TRY(obj_phase1_exact(c, c->w_u));
+    else if (run_cg && !c->final_matvec) CGLB_TRY(obj_phase1_reuse(c, c->w_u));
+    else CGLB_TRY(obj_phase1(c, v_eval, c->w_u));
+    CGLB_TRY(obj_phase2(c, v_eval, c->w_u, sc, c->w_u));  // aw overwrites u after u has been consumed (stream order)
     CGLB_TRY(eval_mark(c));
     if (grad) {
-        CGLB_DISPATCH_T(c->dtype, CGLB_TRY(obj_phase3_impl<T>(c, v_inout, sc, c->w_u, c->gradbuf)));
+        CGLB_DISPATCH_T(c->dtype, CGLB_TRY(obj_phase3_impl<T>(c, v_eval, sc, c->w_u, c->gradbuf)));
         HIP_CHECK(c, hipMemcpyAsync(grad, c->gradbuf, (size_t)CGLB_GRAD_LEN(c->D, c->M) * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     }
     CGLB_TRY(eval_mark(c));
@@ -1324,7 +1435,8 @@ static int predict_rows(cglb_ctx* c, const void* v_full, const void* u, const vo
     auto body = [&]() -> int {
         HIP_CHECK(c, hipMemcpyAsync(xr, xnew, (size_t)n_new * c->D * c->esz, hipMemcpyDefault, c->stream));
         CGLB_TRY(launch_prep_scaled(c, xr, n_new, xs, xa, true));               // hot units for the pair kernel
-        CGLB_TRY(launch_cross_matvec(c, xs, xa, n_new, v_full, f_mean));       // cg_mean = ksf @ v   (models.py:334)
+        if (c->quad_term == 1) HIP_CHECK(c, hipMemsetAsync(f_mean, 0, (size_t)n_new * c->esz, c->stream));  // cg_mean = 0 at v = 0
+        else CGLB_TRY(launch_cross_matvec(c, xs, xa, n_new, v_full, f_mean));  // cg_mean = ksf @ v   (models.py:334)
         CGLB_TRY(launch_prep_scaled(c, xr, n_new, xs, xa, false));             // plain scaled units for the K_us panel
         if (u != c->w_u) HIP_CHECK(c, hipMemcpyAsync(c->w_u, u, (size_t)M * c->esz, hipMemcpyDeviceToDevice, c->stream));
         CGLB_DISPATCH_T(c->dtype, {
@@ -1362,9 +1474,11 @@ int cglb_predict(cglb_ctx* c, const void* v_full, const void* xnew, int64_t n_ne
     if (!c || !v_full || !xnew || !f_mean || !f_var || n_new < 0) return c ? cglb_fail(c, CGLB_ERR_BAD_ARG, "bad argument") : CGLB_ERR_BAD_ARG;
     CGLB_TRY(require_single(c));
     CGLB_TRY(require_terms(c));
+    CGLB_TRY(require_variant_ok(c));
     if (n_new == 0) return CGLB_OK;
     HIP_CHECK(c, hipSetDevice(c->device));
-    CGLB_TRY(launch_kff_matvec(c, v_full, c->w_Kv, nullptr));               // cov @ v            (:335)
+    if (c->quad_term == 1) HIP_CHECK(c, hipMemsetAsync(c->w_Kv, 0, (size_t)c->nloc * c->esz, c->stream));  // v = 0: the Titsias predictive
+    else CGLB_TRY(launch_kff_matvec(c, v_full, c->w_Kv, nullptr));          // cov @ v            (:335)
     CGLB_TRY(predict_u_local(c, c->w_Kv, c->w_u));                          // a_res = A @ res    (:340)
     return predict_rows(c, v_full, c->w_u, xnew, n_new, f_mean, f_var);
 }
@@ -1578,7 +1692,8 @@ int cglb_get_stat(cglb_ctx* c, const char* name, double* value) {
     if (!strcmp(name, "kpart_bytes")) { *value = (double)c->kpart_cap; return CGLB_OK; }     // partial-sum slabs of the mat-vec
     if (!strcmp(name, "comm_allreduce_calls")) { *value = c->comm ? (double)c->comm->n_allreduce : 0.0; return CGLB_OK; }
     if (!strcmp(name, "comm_allgather_calls")) { *value = c->comm ? (double)c->comm->n_allgather : 0.0; return CGLB_OK; }
-    if (!strcmp(name, "L_diag_ratio")) { *value = c->L_diag_ratio; return CGLB_OK; }         // of the last cglb_setup (chooses the gradient algebra)
+    if (!strcmp(name, "n2m_tau")) { *value = c->n2m_tau; return CGLB_OK; }     // tr K~ - tr(C K~ C^T) of the last setup with logdet_bound 2
+        if (!strcmp(name, "L_diag_ratio")) { *value = c->L_diag_ratio; return CGLB_OK; }         // of the last cglb_setup (chooses the gradient algebra)
     return cglb_fail(c, CGLB_ERR_BAD_ARG, std::string("unknown statistic ") + name);
 }
 

@@ -152,6 +152,17 @@ struct cglb_ctx {
     bool exp_clamp = false;         // scaled operands so large that 2^x needs the range clamp (set by set_hypers)
     double m32_bias = 0.0;          // Matern-3/2: positivity bias of the squared distance in hot units^2 (devmath.h CGLB_M32_BIAS_*; set by set_hypers)
     bool kff_skip_combine = false;  // timing only: launch the pair kernel without the slab combine
+    // bound variants (options "logdet_bound", "quad_term"; include/cglb_hip.h).  Both 0: the CGLB bound of models.py:215-286.
+    int logdet_bound = 0;  // 0 Jensen (cglb), 1 NM^2 (cglbnm2, sgpr), 2 N^2M (cglbn2m, sgprn2m; fp64, stored panel, one shard)
+    int quad_term = 0;     // 0 CG (v, PCG), 1 exact Woodbury quadratic term at v = 0 (sgpr, sgprn2m): no N^2 work
+    void* w_zero = nullptr;  // [N] zeros: the v of the exact quadratic term (allocated on first use)
+    // N^2M pass (kernels_n2m.hip), fp64, allocated on first use
+    double *n2m_Xn = nullptr, *n2m_Wt = nullptr, *n2m_Ct = nullptr, *n2m_K = nullptr, *n2m_G = nullptr;  // X/l; W = K_ff A^T and C^T (layout of At); tiles
+    double *n2m_H = nullptr, *n2m_E = nullptr, *n2m_T = nullptr;  // H = A W, E = B^-1 (H + s AA^T) B^-1, M x M scratch
+    double *n2m_ls = nullptr, *n2m_part = nullptr, *n2m_gacc = nullptr, *n2m_scal = nullptr;  // lengthscales, block partials, sum_ij G_ij dK_ij/dl_d, scalars
+    int64_t n2m_bt = 0;    // tile edge of the K / G panels
+    int64_t n2m_tile = 0;  // option "n2m_tile": requested tile edge (0: min(4096, N rounded up to 64))
+    double n2m_tau = 0, n2m_BH = 0, n2m_trBinv = 0;  // tau = tr K~ - tr(C K~ C^T), <B^-1, H>, tr B^-1 (of the last setup)
     std::string err;
 };
 
@@ -222,6 +233,10 @@ int wide_grad_kff(cglb_ctx* c, const void* v_full, const void* u_rows, int64_t r
 int wide_grad_panel(cglb_ctx* c, const void* G, int64_t ldg, const void* cvec, const void* wvec, const void* XsCol, const void* xaCol, const void* XsqCol,
                     int64_t ncols, double zfactor, double* out);
 void wide_free(cglb_ctx* c);
+// N^2M log-det bound (kernels_n2m.hip): the terms of the bound after setup, the kernel-hyper-parameter part of its gradient in phase 3
+int n2m_setup(cglb_ctx* c);  // W = K_ff A^T, H = A W, tau, <B^-1, H>, tr B^-1
+int n2m_grad_terms(cglb_ctx* c, const double* Binv);  // E (n2m_E, trace in n2m_scal[2]) and n2m_gacc[d] = sum_ij G_ij dK_ij/dl_d, G = C^T C
+void n2m_free(cglb_ctx* c);
 
 // ---- launchers implemented in the kernel translation units (all enqueue on ctx->stream) ----------
 // kernels_prep.hip

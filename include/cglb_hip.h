@@ -258,7 +258,18 @@ int cglb_get_stat(cglb_ctx* ctx, const char* name, double* value);
  * "wide_grad_sym" (tiled K_ff gradient pass of wide inputs: 1, default - tiles on and right of the diagonal only; 0 - every tile) |
  * "wide_reg" (inputs of 33 ... 96 dimensions, fp64: 1, default - the symmetric K_ff mat-vec and the K_ff gradient pass stay register-resident,
  *  column operands handed out by v_fmac_f64 row_newbcast; 0 - both go through the Gram tiles like every other product of a wide input) |
- * "drop_weighted_operand" (any value: forget the pre-weighted copy cglb_vec_update_p_seg made of its p - for callers that modify p before the next mat-vec);
+ * "drop_weighted_operand" (any value: forget the pre-weighted copy cglb_vec_update_p_seg made of its p - for callers that modify p before the next mat-vec) |
+ * "logdet_bound" (the log-det term of the bound; cglb_logdet, cglb_objective_and_grad and its gradient follow it.  e = y - mu, s = noise,
+ *  f = variance, A = L^-1 K_uf / sqrt(s), B = I + A A^T = LB LB^T, C = LB^-1 A, t = N f / s - tr A A^T:
+ *  0, default - Jensen (cglb, models.py:215-244): -sum log diag LB - N/2 log s - N/2 log(1 + t/N);
+ *  1 - NM^2 (cglbnm2 and the SGPR bound, tensorflow/models.py:271-308, :353-413): -sum log diag LB - N/2 log s - t/2;
+ *  2 - N^2M (cglbn2m, sgprn2m, tensorflow/models.py:311-350, :353-413): -sum log diag LB - N/2 log(tau/N), tau = tr(K_ff + s I) - tr(C (K_ff + s I) C^T),
+ *  one N^2 M pass per setup and one more per gradient; fp64 contexts with the stored panel (precond_mode 0) only) |
+ * "quad_term" (0, default - the CG quadratic term at the caller's v; 1 - the exact term 1/2 e^T (Q_ff + s I)^-1 e = |e|^2/(2s) - |LB^-1 A e|^2/(2s)
+ *  of SGPR (tensorflow/models.py:393-402): cglb_objective_and_grad and cglb_predict treat v as 0 (v_inout is neither read nor written, no
+ *  solve runs whatever run_cg says) and issue no N^2 work).  Both options at 0: every entry point behaves exactly as without them.  A
+ *  non-zero value is refused on a context with more than one rank (cglb_set_parallel / cglb_comm_init_*), and both of those refuse a context
+ *  that carries one;
  * returns CGLB_ERR_BAD_ARG if unknown. */
 int cglb_set_option(cglb_ctx* ctx, const char* name, int64_t value);
 
