@@ -341,6 +341,25 @@ def kernel_grad_factor(kind, d2: np.ndarray, var) -> np.ndarray:
     return 3.0 * var * np.exp(-SQRT3 * np.sqrt(d2))
 
 
+def kernel_adjoints(hyp: Hypers, terms: CommonTerms, w: np.ndarray, N: int):
+    """d bound / d Kuu (Guu, symmetric) and d bound / d Kuf (Guf) at w = P r (the inducing-point part of `objective_grad`), with
+    B^-1 and tau = 1 + f/s - tr(AA^T)/N."""
+    M = hyp.Z.shape[0]
+    s, f = hyp.noise, hyp.variance
+    sigma = math.sqrt(s)
+    A, LB, L, T = terms.A, terms.LB, terms.L, terms.AAt_diag_sum
+    tau = 1.0 + f / s - T / N
+    eyeM = np.eye(M, dtype=A.dtype)
+    LBinv = sla.solve_triangular(LB, eyeM, lower=True)
+    Binv = LBinv.T @ LBinv
+    Linv = sla.solve_triangular(L, eyeM, lower=True)
+    c = sigma * (Linv.T @ (A @ w))  # Kuu^-1 Kuf w
+    inner = 0.5 * (eyeM - Binv) - (0.5 / tau) * (A @ A.T)
+    Guu = -0.5 * np.outer(c, c) + Linv.T @ inner @ Linv
+    Guf = np.outer(c, w) + (Linv.T @ ((eyeM / tau - Binv) @ A)) / sigma
+    return Guu, Guf, Binv, tau
+
+
 def objective_grad(kind, X, hyp: Hypers, terms: CommonTerms, v: np.ndarray, w: np.ndarray, blocked=None, skip_kff: bool = False) -> Dict[str, np.ndarray]:
     """Gradient of ``bound`` wrt the constrained hypers with v held constant.
 
@@ -361,18 +380,8 @@ def objective_grad(kind, X, hyp: Hypers, terms: CommonTerms, v: np.ndarray, w: n
     s, f, ls = hyp.noise, hyp.variance, np.asarray(hyp.lengthscales, dtype=X.dtype)
     sigma = math.sqrt(s)
     A, LB, L, T = terms.A, terms.LB, terms.L, terms.AAt_diag_sum
-    tau = 1.0 + f / s - T / N
     u = w + 0.5 * v
-
-    eyeM = np.eye(M, dtype=X.dtype)
-    LBinv = sla.solve_triangular(LB, eyeM, lower=True)
-    Binv = LBinv.T @ LBinv
-    Linv = sla.solve_triangular(L, eyeM, lower=True)
-    c = sigma * (Linv.T @ (A @ w))  # Kuu^-1 Kuf w
-    # adjoints of Kuu and Kuf
-    inner = 0.5 * (eyeM - Binv) - (0.5 / tau) * (A @ A.T)
-    Guu = -0.5 * np.outer(c, c) + Linv.T @ inner @ Linv
-    Guf = np.outer(c, w) + (Linv.T @ ((eyeM / tau - Binv) @ A)) / sigma
+    Guu, Guf, Binv, tau = kernel_adjoints(hyp, terms, w, N)
 
     g_ls = np.zeros(D, dtype=X.dtype)
     g_Z = np.zeros((M, D), dtype=X.dtype)

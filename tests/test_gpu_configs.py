@@ -17,6 +17,7 @@ import numpy as np
 import pytest
 import torch
 
+import fp32_error_model as em
 from conftest import GOLDEN_DIR
 from oracle import cglb_oracle as orc
 from oracle import cglb_oracle_c as orcc
@@ -119,7 +120,13 @@ def test_c5_n1m_d16_rbf_m4096_fp32():
     """C5: N = 1 000 000, D = 16, RBF, M = 4096, fp32 (tolerances relaxed to fp32 round-off against the fp64 oracle)."""
     ctx, X, y, hyp = _ctx(1_000_000, 16, 4096, "rbf", dtype=torch.float32)
     ctx.setup()
-    _check_matvec_rows(ctx, X.astype(np.float32).astype(np.float64), hyp, "rbf", 3e-5)
+    X32 = X.astype(np.float32).astype(np.float64)
+    p, Ap = _check_matvec_rows(ctx, X32, hyp, "rbf", 3e-5)
+    # the deepest fp32 accumulation of the suite (1024-column chunks plus ~2000 slabs): per entry at the round-off model
+    p32 = p.to(ctx.dtype).double().numpy()
+    for start in (0, (ctx.N // 2 // 256) * 256 + 37, ctx.N - 256):
+        ref, s = em.matvec_rows("rbf", X32, hyp, p32, start, start + 256)
+        assert em.ratio(Ap[start:start + 256], ref, s) <= em.TAU["matvec"], start
     _check_woodbury(ctx, hyp, 5e-3)
     _check_short_pcg(ctx, hyp, 2, 2e-2)
     ctx.close()

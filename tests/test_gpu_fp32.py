@@ -1,9 +1,11 @@
 """fp32 path (config C5 "tolerance relaxed"): same kernels instantiated for float (hardware v_exp_f32), checked against the
-fp64 oracle at fp32-level tolerances."""
+fp64 oracle at fp32-level tolerances, and held entry by entry to the fp32 round-off model on the float32-rounded inputs
+(tests/fp32_error_model.py)."""
 import numpy as np
 import pytest
 import torch
 
+import fp32_error_model as em
 from oracle import cglb_oracle as orc
 
 pytestmark = pytest.mark.gpu
@@ -27,6 +29,9 @@ def test_fp32_matvec_and_objective(kind, variant, D):
     out = ctx.matvec(torch.from_numpy(p).float()).cpu().numpy().astype(np.float64)
     ref = orc.dense_cov(kind, X, hyp) @ p
     assert np.abs(out - ref).max() <= 2e-4 * np.abs(ref).max()
+    X32, p32, h32 = em.f32(X), em.f32(p), em.round_hypers(hyp)  # what the context holds: the kernel's arithmetic alone is left
+    case = em.matvec_case(kind, X32, h32, p32)
+    assert em.ratio(out, case.ref, case.s) <= em.TAU["matvec"]
     v = torch.zeros(N, dtype=torch.float32, device=ctx.device)
     res = ctx.objective_and_grad(v, True, 1.0)
     refo = orc.objective(kind, X, y, hyp, np.zeros(N), True, 1.0)
@@ -35,3 +40,9 @@ def test_fp32_matvec_and_objective(kind, variant, D):
     refg = orc.objective(kind, X, y, hyp, v.cpu().numpy().astype(np.float64), run_cg=False, with_grad=True).grad
     np.testing.assert_allclose(res.grad["lengthscales"], refg["lengthscales"], rtol=5e-2, atol=5e-2 * np.abs(refg["lengthscales"]).max())
     assert res.grad["noise"] == pytest.approx(refg["noise"], rel=5e-2)
+    # the same v again without the solve (w = P r from a recomputed K v): lengthscale and Z blocks at the model's round-off
+    v32 = v.cpu().numpy().astype(np.float64)
+    g, sg, _ = em.grad_case(kind, X32, em.f32(y), h32, v32)
+    res2 = ctx.objective_and_grad(v, run_cg=False, with_grad=True)
+    assert em.ratio(res2.grad["lengthscales"], g["lengthscales"], sg["lengthscales"]) <= em.TAU["grad_ls"]
+    assert em.ratio(res2.grad["Z"], g["Z"], sg["Z"]) <= em.TAU["grad_Z"]

@@ -10,6 +10,7 @@ import pytest
 import torch
 import torch.multiprocessing as mp
 
+import fp32_error_model as em
 from oracle import cglb_oracle as orc
 
 pytestmark = pytest.mark.gpu
@@ -179,6 +180,8 @@ def test_wide_inputs_in_fp32(kind):
     p = rng.standard_normal(N)
     Ap = ctx.matvec(torch.from_numpy(p).float()).double().cpu().numpy()
     np.testing.assert_allclose(Ap, cov @ p, rtol=0, atol=2e-5 * np.abs(cov @ p).max())
+    case = em.matvec_case(kind, em.f32(X), em.round_hypers(hyp), em.f32(p))  # per entry, on the rounded inputs
+    assert em.ratio(Ap, case.ref, case.s) <= em.TAU["matvec"]
     v = torch.zeros(N, dtype=torch.float32, device=ctx.device)
     res = ctx.objective_and_grad(v, True, 1.0, 100, 40)
     ref = orc.objective(kind, X, y, hyp, np.zeros(N), True, 1.0, 100, 40, cov=cov)
