@@ -347,51 +347,71 @@ int require_single(cglb_ctx* c) {
 inline double lookahead_factor(const cglb_ctx* c) { return c->pcg_lookahead >= 2 ? (double)c->pcg_lookahead : CGLB_LOOKAHEAD_FACTOR; }
 
 // ---- PCG (conjugate_gradient.py:41-86) ----------------------------------------------------------------------
-int pcg_impl(cglb_ctx* c, const void* b, void* v, double max_error, int max_iter, int restart_iter, int* steps, double* half_rz) {
+// What the one loop below is told about its caller: where the recurrence keeps its vectors and how the two operators are applied.
+//   fused (one GPU, one shard): the context's own work vectors; p.Ap comes out of the mat-vec's slab combine; z = P r in one piece
+//   N ranks: replicated full-length vectors of the communicator state; cyclic share + all-reduce, then a dot over the summed product
+//            (another summation order than the fused one, on purpose); z gathered in segments
+struct pcg_ops {
+    void *r, *p, *Ap, *Kv;  // [n]
+    int64_t n;
+    int (*matvec)(cglb_ctx* c, const void* x, void* out, double* pdot_slot);  // out = (K_ff + noise I) x; x.out into pdot_slot if it fuses the dot
+    bool dot_fused;         // false: pdot_slot is ignored and a launch_dot follows the mat-vec
+    int (*direction)(cglb_ctx* c, const pcg_ops& o, double* rz_new, const double* rz_old, int restart);  // z = P r, rz_new = r.z, p = z (+ p rz_new / rz_old)
+    bool rz_must_be_finite; // N ranks leave the loop together or not at all: a non-finite r^T P r is CGLB_ERR_COMM, not a quiet end
+};
+
+int fused_direction(cglb_ctx* c, const pcg_ops& o, double* rz_new, const double* rz_old, int restart) {
+    CGLB_TRY(precond_single(c, o.r, c->w_z, rz_new));                                               // :59 / :73
+    return launch_update_p(c, o.p, c->w_z, rz_new, rz_old, restart, -1, true);                      // :61 / :75 (+ the weighted copy for the next mat-vec)
+}
+inline pcg_ops fused_ops(cglb_ctx* c) { return {c->w_r, c->w_p, c->w_Ap, c->w_Kv, c->nloc, launch_kff_matvec, true, fused_direction, false}; }
+
+int pcg_solve(cglb_ctx* c, const pcg_ops& o, const void* b, void* v, double max_error, int max_iter, int restart_iter, int* steps, double* half_rz) {
     double* S = c->scal;
     // A weighted copy p o w left behind by the LAST update of an earlier solve (loop left without a look-ahead mat-vec) must not be
     // taken for the operand of this solve's first mat-vec: the direction vector is rewritten below.
     c->pwh_src = nullptr;
     // :57-61  Av = A v ; r = b - Av ; z, rz = P(r) ; p = z
     // A cold start (v == 0, models.py:59-68) gives Av == 0 and r == b exactly, so the mat-vec is skipped in that case;
-    // the result is bit-identical to computing it.
+    // the result is bit-identical to computing it.  (On N ranks v is replicated: every rank takes the same branch.)
     double vnorm = 0.0;
-    CGLB_TRY(launch_dot(c, v, v, c->nloc, S + S_TMP));
+    CGLB_TRY(launch_dot(c, v, v, o.n, S + S_TMP));
     CGLB_TRY(read_scalars(c, S + S_TMP, &vnorm, 1));
     if (vnorm == 0.0) {
-        HIP_CHECK(c, hipMemcpyAsync(c->w_r, b, (size_t)c->nloc * c->esz, hipMemcpyDeviceToDevice, c->stream));
+        HIP_CHECK(c, hipMemcpyAsync(o.r, b, (size_t)o.n * c->esz, hipMemcpyDeviceToDevice, c->stream));
     } else {
-        CGLB_TRY(launch_kff_matvec(c, v, c->w_Kv, nullptr));
-        CGLB_TRY(launch_residual(c, c->w_r, b, c->w_Kv));
+        CGLB_TRY(o.matvec(c, v, o.Kv, nullptr));
+        CGLB_TRY(launch_residual(c, o.r, b, o.Kv, o.n));
     }
     double *s_rz = S + S_RZ, *s_nrz = S + S_NRZ;  // the two slots swap roles every iteration (:76) instead of being copied
-    CGLB_TRY(precond_single(c, c->w_r, c->w_z, s_rz));
-    CGLB_TRY(launch_update_p(c, c->w_p, c->w_z, s_rz, s_rz, 1, -1, true));  // :61 p = z (+ the weighted copy for the first mat-vec)
+    CGLB_TRY(o.direction(c, o, s_rz, s_rz, 1));
     double rz = 0;
     CGLB_TRY(read_scalars(c, s_rz, &rz, 1));
+    if (o.rz_must_be_finite && !std::isfinite(rz)) return cglb_fail(c, CGLB_ERR_COMM, "r^T P r is not finite at the start of the solve");
     // The stop predicate (:65) is evaluated on the host, like the reference's (:80-81).  Look-ahead: while the residual is
     // still far above the tolerance (more than CGLB_LOOKAHEAD_FACTOR = 32x after the PREVIOUS iteration), the mat-vec of the next iteration is enqueued
-    // before the host waits for this iteration's scalar, so the GPU does not idle over the read-back.  If the predicate then
+    // (on N ranks with its all-reduce) before the host waits for this iteration's scalar, so the GPU does not idle over the read-back.  If the predicate then
     // says stop, that mat-vec was wasted (it only writes Ap and the p.Ap slot): results are identical either way.
     int i = 0;
     bool ahead = false;
     while (0.5 * rz > max_error && i < max_iter) {  // :65
-        if (!ahead) CGLB_TRY(launch_kff_matvec(c, c->w_p, c->w_Ap, S + S_PAP));                    // :66 and (p*Ap).sum()
+        if (!ahead) CGLB_TRY(o.matvec(c, o.p, o.Ap, S + S_PAP));                                    // :66 and (p*Ap).sum() where fused
+        if (!o.dot_fused) CGLB_TRY(launch_dot(c, o.p, o.Ap, o.n, S + S_PAP));                       // :67
         const int restart = (restart_iter > 0) && (i % restart_iter == restart_iter - 1);          // :70
-        CGLB_TRY(launch_update_v_r(c, v, c->w_r, c->w_p, c->w_Ap, s_rz, S + S_PAP, !restart));  // :67-68, :72
+        CGLB_TRY(launch_update_v_r(c, v, o.r, o.p, o.Ap, s_rz, S + S_PAP, !restart, o.n));          // :67-68, :72
         if (restart) {
-            CGLB_TRY(launch_kff_matvec(c, v, c->w_Kv, nullptr));
-            CGLB_TRY(launch_residual(c, c->w_r, b, c->w_Kv));
+            CGLB_TRY(o.matvec(c, v, o.Kv, nullptr));
+            CGLB_TRY(launch_residual(c, o.r, b, o.Kv, o.n));
         }
-        CGLB_TRY(precond_single(c, c->w_r, c->w_z, s_nrz));                                         // :73
-        CGLB_TRY(launch_update_p(c, c->w_p, c->w_z, s_nrz, s_rz, restart, -1, true));               // :75 (+ weighted copy for :66)
+        CGLB_TRY(o.direction(c, o, s_nrz, s_rz, restart));                                          // :73, :75
         std::swap(s_rz, s_nrz);                                                                     // :76
         HIP_CHECK(c, hipMemcpyAsync(c->host_scal, s_rz, sizeof(double), hipMemcpyDeviceToHost, c->stream));
         HIP_CHECK(c, hipEventRecord(c->scal_event, c->stream));
         ahead = c->pcg_lookahead && (i + 1 < max_iter) && (0.5 * rz > lookahead_factor(c) * max_error);  // rz: still the value of the previous iteration
-        if (ahead) CGLB_TRY(launch_kff_matvec(c, c->w_p, c->w_Ap, S + S_PAP));
+        if (ahead) CGLB_TRY(o.matvec(c, o.p, o.Ap, S + S_PAP));
         HIP_CHECK(c, hipEventSynchronize(c->scal_event));                                            // host test of :65 (and the sync of :80-81)
-        rz = c->host_scal[0];
+        rz = c->host_scal[0];  // N ranks: a function of all-gathered numbers only, so every rank reads the same value and leaves the loop together
+        if (o.rz_must_be_finite && !std::isfinite(rz)) return cglb_fail(c, CGLB_ERR_COMM, "r^T P r is not finite after iteration " + std::to_string(i));
         ++i;
     }
     if (steps) *steps = i;
@@ -400,23 +420,19 @@ int pcg_impl(cglb_ctx* c, const void* b, void* v, double max_error, int max_iter
 }
 
 // ---- objective phases -----------------------------------------------------------------------------------------
-int obj_phase1(cglb_ctx* c, const void* v_full, void* u_partial) {
+// Phase 1 for a given K v over the local rows: e = y - mean (models.py:253-254), r = e - K v (:281), u_partial = A_loc r (the first half of
+// precon(r), :282).  A rank without rows contributes a zero u.
+int obj_phase1_kv(cglb_ctx* c, const void* Kv_local, void* u_partial) {
     const char* y_loc = (const char*)c->y + (size_t)c->r0 * c->esz;
-    CGLB_TRY(launch_sub_scalar(c, c->w_e, y_loc, c->mean, c->nloc));       // models.py:253-254
-    CGLB_TRY(launch_kff_matvec(c, v_full, c->w_Kv, nullptr));              // :280
-    CGLB_TRY(launch_residual(c, c->w_r, c->w_e, c->w_Kv));                 // :281
-    CGLB_TRY(precond_u_any(c, c->w_r, u_partial));                         // first half of precon(r), :282
-    return CGLB_OK;
+    CGLB_TRY(launch_sub_scalar(c, c->w_e, y_loc, c->mean, c->nloc));
+    if (Kv_local != c->w_Kv) HIP_CHECK(c, hipMemcpyAsync(c->w_Kv, Kv_local, (size_t)c->nloc * c->esz, hipMemcpyDeviceToDevice, c->stream));
+    CGLB_TRY(launch_residual(c, c->w_r, c->w_e, c->w_Kv));
+    if (c->nloc == 0) { HIP_CHECK(c, hipMemsetAsync(u_partial, 0, (size_t)c->M * c->esz, c->stream)); return CGLB_OK; }
+    return precond_u_any(c, c->w_r, u_partial);
 }
-
-// Phase 1 without the mat-vec of models.py:280 (option "final_matvec" = 0): straight after a solve, w_r still holds the residual the
-// PCG recurrence carries, r = e - K v up to the rounding of its updates (exact at the start of the solve and after every restart step,
-// conjugate_gradient.py:58,72), so K v = e - r costs one vector kernel instead of N^2 pair evaluations.  The reference recomputes
-// `cov @ v`; the two differ at the level of the mat-vec's own rounding (measured: DESIGN.md section 5).
-int obj_phase1_reuse(cglb_ctx* c, void* u_partial) {
-    CGLB_TRY(launch_residual(c, c->w_Kv, c->w_e, c->w_r));                 // K v = e - r   (w_e = y - mean was the solve's right-hand side)
-    CGLB_TRY(precond_u_any(c, c->w_r, u_partial));
-    return CGLB_OK;
+int obj_phase1(cglb_ctx* c, const void* v_full, void* u_partial) {
+    CGLB_TRY(launch_kff_matvec(c, v_full, c->w_Kv, nullptr));              // models.py:280
+    return obj_phase1_kv(c, c->w_Kv, u_partial);
 }
 
 // Phase 1 of the exact quadratic term (quad_term 1, tensorflow/models.py:393-402): v = 0, so K v = 0 and r = e without any N^2 work;
@@ -639,10 +655,6 @@ int obj_finish(cglb_ctx* c, const double* sc_dev, double* out4) {
 }
 
 
-// ================================ N ranks inside the library (include/cglb_hip.h, "N ranks inside the library") ================================
-// Same scheme as cglb_amd/distributed.py: SymShardedCGLB (the host-driven twin that the gloo tests exercise with CPU local ops): the global
-// upper triangle of K_ff dealt to the ranks by cyclic row blocks, replicated full-length p, Ap, v, r, b, the Nystrom panel column-sharded over
-// contiguous rows, three collectives per PCG iteration - issued here on the context stream.
 // ---- phase timing of an evaluation (option "eval_profile") -------------------------------------------------------------------
 int eval_mark(cglb_ctx* c) {
     if (!c->eval_profile) return CGLB_OK;
@@ -668,6 +680,44 @@ int eval_collect(cglb_ctx* c) {
     return CGLB_OK;
 }
 
+// An evaluation that returns an error must leave no marks behind: eval_collect pairs them in groups of 5.
+struct eval_marks_guard {
+    cglb_ctx* c;
+    size_t used;  // eval_events_used on entry
+    bool done = false;
+    ~eval_marks_guard() { if (!done) c->eval_events_used = used; }
+};
+
+// The front half of an evaluation, the same on one GPU and on N ranks (o, b: where that path keeps the recurrence and its right-hand side):
+// the solve from e = y - mean (models.py:262-278), the third mark, K v, and phase 1 for that K v.
+// K v (option "final_matvec"): 1 recomputes it as the reference does (`cov @ v`, models.py:280).  0 (default), straight after a solve: o.r
+// still holds the residual the PCG recurrence carries, r = e - K v up to the rounding of its updates (exact at the start of the solve and after
+// every restart step, conjugate_gradient.py:58,72), so K v = e - r costs one vector kernel instead of N^2 pair evaluations.  The two differ
+// at the level of the mat-vec's own rounding (measured: DESIGN.md section 5).
+int eval_solve_phase1(cglb_ctx* c, const pcg_ops& o, void* b, void* v, int run_cg, double max_error, int max_iter, int restart_iter, int* steps,
+                      double* half_rz, void* u_partial) {
+    if (steps) *steps = 0;
+    if (half_rz) *half_rz = std::nan("");
+    if (run_cg) {
+        CGLB_TRY(launch_sub_scalar(c, b, c->y, c->mean, o.n));
+        CGLB_TRY(pcg_solve(c, o, b, v, max_error, max_iter, restart_iter, steps, half_rz));
+    }
+    CGLB_TRY(eval_mark(c));
+    if (c->quad_term == 1) return obj_phase1_exact(c, u_partial);  // v = 0: no K v at all (one rank only: require_variant_ok, comm_alloc)
+    if (!run_cg || c->final_matvec) {
+        CGLB_TRY(o.matvec(c, v, o.Kv, nullptr));
+    } else {
+        CGLB_TRY(launch_residual(c, o.Kv, b, o.r, o.n));
+        // fused: the recurrence ran in the evaluation's own work vectors, so e and r are in place already (and r stays the recurrence's)
+        if (o.r == c->w_r) return precond_u_any(c, c->w_r, u_partial);
+    }
+    return obj_phase1_kv(c, (const char*)o.Kv + (size_t)c->r0 * c->esz, u_partial);
+}
+
+// ================================ N ranks inside the library (include/cglb_hip.h, "N ranks inside the library") ================================
+// Same scheme as cglb_amd/distributed.py: SymShardedCGLB (the host-driven twin that the gloo tests exercise with CPU local ops): the global
+// upper triangle of K_ff dealt to the ranks by cyclic row blocks, replicated full-length p, Ap, v, r, b, the Nystrom panel column-sharded over
+// contiguous rows, three collectives per PCG iteration - issued here on the context stream.
 inline ncclDataType_t nccl_type(const cglb_ctx* c, bool as_double) { return (as_double || c->dtype == CGLB_F64) ? ncclDouble : ncclFloat; }
 
 int require_comm(cglb_ctx* c) {
@@ -707,6 +757,8 @@ int comm_allgather(cglb_ctx* c, void* buf, int64_t count) {
 
 void comm_free(cglb_ctx* c) {
     cglb_comm_state* m = c->comm;
+    c->par_world = 1;  // nobody (left) to sum a cyclic share with: the context computes whole mat-vecs again
+    c->par_rank = 0;
     if (!m) return;
     if (c->stream) (void)hipStreamSynchronize(c->stream); else (void)hipDeviceSynchronize();
     if (m->kind == 1 && m->nccl) (void)ncclCommDestroy((ncclComm_t)m->nccl);
@@ -777,57 +829,15 @@ int dist_precond_gather(cglb_ctx* c, const void* r_full) {
 }
 
 // ... then rz_new = r^T z from the gathered partials (rank order) and p = z + p rz_new / rz_old, or p = z (:75)
-int dist_precond_direction(cglb_ctx* c, double* rz_new, const double* rz_old, int restart) {
+int dist_direction(cglb_ctx* c, const pcg_ops& o, double* rz_new, const double* rz_old, int restart) {
     cglb_comm_state* m = c->comm;
-    CGLB_TRY(dist_precond_gather(c, m->r));
-    return launch_update_p_seg(c, m->p, m->zseg, c->N, m->per, m->world, rz_new, rz_old, restart);
+    CGLB_TRY(dist_precond_gather(c, o.r));
+    return launch_update_p_seg(c, o.p, m->zseg, c->N, m->per, m->world, rz_new, rz_old, restart);
 }
-
-// conjugate_gradient.py:41-86 on replicated full vectors - the N-rank twin of pcg_impl (same look-ahead, same stop rule)
-int dist_pcg_impl(cglb_ctx* c, const void* b, void* v, double max_error, int max_iter, int restart_iter, int* steps, double* half_rz) {
+// pcg_solve on replicated full vectors: three collectives per iteration (the mat-vec's all-reduce, u, the gather of z)
+inline pcg_ops dist_ops(cglb_ctx* c) {
     cglb_comm_state* m = c->comm;
-    double* S = c->scal;
-    const int64_t N = c->N;
-    c->pwh_src = nullptr;
-    double vnorm = 0.0;
-    CGLB_TRY(launch_dot(c, v, v, N, S + S_TMP));
-    CGLB_TRY(read_scalars(c, S + S_TMP, &vnorm, 1));
-    if (vnorm == 0.0) {  // cold start: A v == 0 and r == b exactly (v is replicated: every rank takes the same branch)
-        HIP_CHECK(c, hipMemcpyAsync(m->r, b, (size_t)N * c->esz, hipMemcpyDeviceToDevice, c->stream));
-    } else {
-        CGLB_TRY(dist_matvec(c, v, m->Kv));                                                        // :57
-        CGLB_TRY(launch_residual(c, m->r, b, m->Kv, N));                                           // :58
-    }
-    double *s_rz = S + S_RZ, *s_nrz = S + S_NRZ;
-    CGLB_TRY(dist_precond_direction(c, s_rz, s_rz, 1));                                            // :59, :61
-    double rz = 0;
-    CGLB_TRY(read_scalars(c, s_rz, &rz, 1));
-    if (!std::isfinite(rz)) return cglb_fail(c, CGLB_ERR_COMM, "r^T P r is not finite at the start of the solve");  // gathered numbers: same on every rank
-    int i = 0;
-    bool ahead = false;
-    while (0.5 * rz > max_error && i < max_iter) {                                                 // :65
-        if (!ahead) CGLB_TRY(dist_matvec(c, m->p, m->Ap));                                         // :66
-        CGLB_TRY(launch_dot(c, m->p, m->Ap, N, S + S_PAP));                                        // :67
-        const int restart = (restart_iter > 0) && (i % restart_iter == restart_iter - 1);          // :70
-        CGLB_TRY(launch_update_v_r(c, v, m->r, m->p, m->Ap, s_rz, S + S_PAP, !restart, N));        // :68, :72
-        if (restart) {
-            CGLB_TRY(dist_matvec(c, v, m->Kv));
-            CGLB_TRY(launch_residual(c, m->r, b, m->Kv, N));
-        }
-        CGLB_TRY(dist_precond_direction(c, s_nrz, s_rz, restart));                                 // :73, :75
-        std::swap(s_rz, s_nrz);                                                                    // :76
-        HIP_CHECK(c, hipMemcpyAsync(c->host_scal, s_rz, sizeof(double), hipMemcpyDeviceToHost, c->stream));
-        HIP_CHECK(c, hipEventRecord(c->scal_event, c->stream));
-        ahead = c->pcg_lookahead && (i + 1 < max_iter) && (0.5 * rz > lookahead_factor(c) * max_error);
-        if (ahead) CGLB_TRY(dist_matvec(c, m->p, m->Ap));                                          // kernel + all-reduce enqueued before the host waits
-        HIP_CHECK(c, hipEventSynchronize(c->scal_event));
-        rz = c->host_scal[0];  // a function of all-gathered numbers only: every rank reads the same value and leaves the loop together
-        if (!std::isfinite(rz)) return cglb_fail(c, CGLB_ERR_COMM, "r^T P r is not finite after iteration " + std::to_string(i));
-        ++i;
-    }
-    if (steps) *steps = i;
-    if (half_rz) *half_rz = 0.5 * rz;
-    return CGLB_OK;
+    return {m->r, m->p, m->Ap, m->Kv, c->N, [](cglb_ctx* cc, const void* x, void* out, double*) { return dist_matvec(cc, x, out); }, false, dist_direction, true};
 }
 
 template <typename T>
@@ -1272,11 +1282,7 @@ int cglb_shard_obj_phase1_kv(cglb_ctx* c, const void* Kv_local, void* u_partial)
     if (!c || !Kv_local || !u_partial) return c ? cglb_fail(c, CGLB_ERR_BAD_ARG, "NULL argument") : CGLB_ERR_BAD_ARG;
     CGLB_TRY(require_terms(c));
     HIP_CHECK(c, hipSetDevice(c->device));
-    const char* y_loc = (const char*)c->y + (size_t)c->r0 * c->esz;
-    CGLB_TRY(launch_sub_scalar(c, c->w_e, y_loc, c->mean, c->nloc));
-    HIP_CHECK(c, hipMemcpyAsync(c->w_Kv, Kv_local, (size_t)c->nloc * c->esz, hipMemcpyDeviceToDevice, c->stream));
-    CGLB_TRY(launch_residual(c, c->w_r, c->w_e, c->w_Kv));
-    return precond_u_any(c, c->w_r, u_partial);
+    return obj_phase1_kv(c, Kv_local, u_partial);
 }
 int cglb_shard_obj_w(cglb_ctx* c, void* w_local_out) {
     if (!c || !w_local_out) return c ? cglb_fail(c, CGLB_ERR_BAD_ARG, "NULL argument") : CGLB_ERR_BAD_ARG;
@@ -1297,7 +1303,7 @@ int cglb_pcg_solve(cglb_ctx* c, const void* b, void* v_inout, double max_error, 
     CGLB_TRY(require_single(c));
     CGLB_TRY(require_terms(c));
     HIP_CHECK(c, hipSetDevice(c->device));
-    return pcg_impl(c, b, v_inout, max_error, max_cg_iter, restart_cg_iter, steps, half_rz);
+    return pcg_solve(c, fused_ops(c), b, v_inout, max_error, max_cg_iter, restart_cg_iter, steps, half_rz);
 }
 
 int cglb_shard_obj_phase1(cglb_ctx* c, const void* v_full, void* u_partial) {
@@ -1339,21 +1345,13 @@ int cglb_objective_and_grad(cglb_ctx* c, void* v_inout, int run_cg, double max_e
     }
     void* v_eval = exact ? c->w_zero : v_inout;
     if (c->eval_profile && c->eval_events_used + 5 > 5 * 512) CGLB_TRY(eval_collect(c));  // bounded pool
+    eval_marks_guard marks{c, c->eval_events_used};
     CGLB_TRY(eval_mark(c));
     CGLB_TRY(cglb_setup(c));                                                        // models.py:155
     CGLB_TRY(eval_mark(c));
-    if (steps) *steps = 0;
-    if (half_rz) *half_rz = std::nan("");
-    if (run_cg) {                                                                   // models.py:262-278
-        CGLB_TRY(launch_sub_scalar(c, c->w_e, c->y, c->mean, c->nloc));
-        // w_e is reused by phase1, which recomputes it; pcg reads it as b
-        CGLB_TRY(pcg_impl(c, c->w_e, v_inout, max_error, max_cg_iter, restart_cg_iter, steps, half_rz));
-    }
-    CGLB_TRY(eval_mark(c));
+    // w_e: the solve reads it as b, phase 1 as e
+    CGLB_TRY(eval_solve_phase1(c, fused_ops(c), c->w_e, v_eval, run_cg, max_error, max_cg_iter, restart_cg_iter, steps, half_rz, c->w_u));
     double* sc = c->scal + S_SC;
-    if (exact) CGLB_TRY(obj_phase1_exact(c, c->w_u));
-    else if (run_cg && !c->final_matvec) CGLB_TRY(obj_phase1_reuse(c, c->w_u));
-    else CGLB_TRY(obj_phase1(c, v_eval, c->w_u));
     CGLB_TRY(obj_phase2(c, v_eval, c->w_u, sc, c->w_u));  // aw overwrites u after u has been consumed (stream order)
     CGLB_TRY(eval_mark(c));
     if (grad) {
@@ -1362,6 +1360,7 @@ int cglb_objective_and_grad(cglb_ctx* c, void* v_inout, int run_cg, double max_e
     }
     CGLB_TRY(eval_mark(c));
     CGLB_TRY(obj_finish(c, sc, out4));
+    marks.done = true;
     c->obj_valid = true;  // r = e - K v and w = P r of this evaluation stay in the work vectors (cglb_objective_grad_v)
     return CGLB_OK;
 }
@@ -1541,7 +1540,6 @@ int cglb_comm_destroy(cglb_ctx* c) {
     if (!c) return CGLB_ERR_BAD_ARG;
     (void)hipSetDevice(c->device);
     comm_free(c);
-    c->par_world = 1; c->par_rank = 0;
     return CGLB_OK;
 }
 
@@ -1581,7 +1579,7 @@ int cglb_dist_pcg_solve(cglb_ctx* c, const void* b_full, void* v_full_inout, dou
     CGLB_TRY(require_comm(c));
     CGLB_TRY(require_terms(c));
     HIP_CHECK(c, hipSetDevice(c->device));
-    return dist_pcg_impl(c, b_full, v_full_inout, max_error, max_cg_iter, restart_cg_iter, steps, half_rz);
+    return pcg_solve(c, dist_ops(c), b_full, v_full_inout, max_error, max_cg_iter, restart_cg_iter, steps, half_rz);
 }
 
 int cglb_dist_objective_and_grad(cglb_ctx* c, void* v, int run_cg, double max_error, int max_cg_iter, int restart_cg_iter, double* out4,
@@ -1591,25 +1589,16 @@ int cglb_dist_objective_and_grad(cglb_ctx* c, void* v, int run_cg, double max_er
     CGLB_TRY(require_comm(c));
     HIP_CHECK(c, hipSetDevice(c->device));
     cglb_comm_state* m = c->comm;
+    if (c->eval_profile && c->eval_events_used + 5 > 5 * 512) CGLB_TRY(eval_collect(c));  // bounded pool
+    eval_marks_guard marks{c, c->eval_events_used};
+    CGLB_TRY(eval_mark(c));
     CGLB_TRY(dist_setup(c));                                                        // models.py:155
-    if (steps) *steps = 0;
-    if (half_rz) *half_rz = std::nan("");
-    if (run_cg) {                                                                   // models.py:262-278
-        CGLB_TRY(launch_sub_scalar(c, m->b, c->y, c->mean, c->N));
-        CGLB_TRY(dist_pcg_impl(c, m->b, v, max_error, max_cg_iter, restart_cg_iter, steps, half_rz));
-    }
-    if (run_cg && !c->final_matvec) CGLB_TRY(launch_residual(c, m->Kv, m->b, m->r, c->N));  // K v = e - r of the recurrence (option "final_matvec")
-    else CGLB_TRY(dist_matvec(c, v, m->Kv));                                        // models.py:280
-    // phase 1 with K v given: r = e - K v on the local rows, u_partial = A_loc r
-    const char* y_loc = (const char*)c->y + (size_t)c->r0 * c->esz;
-    CGLB_TRY(launch_sub_scalar(c, c->w_e, y_loc, c->mean, c->nloc));
-    HIP_CHECK(c, hipMemcpyAsync(c->w_Kv, (const char*)m->Kv + (size_t)c->r0 * c->esz, (size_t)c->nloc * c->esz, hipMemcpyDeviceToDevice, c->stream));
-    CGLB_TRY(launch_residual(c, c->w_r, c->w_e, c->w_Kv));
-    if (c->nloc > 0) CGLB_TRY(launch_gemv_u(c, c->w_r, m->u));
-    else HIP_CHECK(c, hipMemsetAsync(m->u, 0, (size_t)c->M * c->esz, c->stream));
+    CGLB_TRY(eval_mark(c));
+    CGLB_TRY(eval_solve_phase1(c, dist_ops(c), m->b, v, run_cg, max_error, max_cg_iter, restart_cg_iter, steps, half_rz, m->u));
     CGLB_TRY(comm_allreduce(c, m->u, c->M));
     CGLB_TRY(obj_phase2(c, v, m->u, m->sc, m->aw));
     CGLB_TRY(comm_allreduce(c, m->sc, 8, true));
+    CGLB_TRY(eval_mark(c));
     if (grad) {
         CGLB_TRY(comm_allreduce(c, m->aw, c->M));
         // u = w + v/2 on the local rows, gathered: the cyclic share of the N^2 gradient form needs it in full
@@ -1621,7 +1610,10 @@ int cglb_dist_objective_and_grad(cglb_ctx* c, void* v, int run_cg, double max_er
         CGLB_TRY(comm_allreduce(c, m->grad, (int64_t)CGLB_GRAD_LEN(c->D, c->M), true));
         HIP_CHECK(c, hipMemcpyAsync(grad, m->grad, (size_t)CGLB_GRAD_LEN(c->D, c->M) * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     }
-    return obj_finish(c, m->sc, out4);
+    CGLB_TRY(eval_mark(c));
+    CGLB_TRY(obj_finish(c, m->sc, out4));
+    marks.done = true;
+    return CGLB_OK;
 }
 
 int cglb_dist_predict(cglb_ctx* c, const void* v_full, const void* xnew, int64_t n_new, void* f_mean, void* f_var) {

@@ -114,7 +114,7 @@ struct cglb_ctx {
     size_t k1_events_used = 0;
     double k1_ms_total = 0.0;
     long long k1_launches = 0;
-    // phase timing of cglb_objective_and_grad ("eval_profile"): 5 events per evaluation (start | common terms | PCG | final mat-vec +
+    // phase timing of cglb_objective_and_grad / cglb_dist_objective_and_grad ("eval_profile"): 5 events per completed evaluation (start | common terms | PCG | final mat-vec +
     // preconditioner + scalars | gradient), resolved lazily by cglb_get_stat "eval_*_ms"
     bool eval_profile = false;
     std::vector<hipEvent_t> eval_events;
@@ -142,7 +142,7 @@ struct cglb_ctx {
     double* host_scal = nullptr;   // pinned host mirror for the asynchronous read of the stop-test scalar
     hipEvent_t scal_event = nullptr;
     int final_matvec = 0;          // 1: K v recomputed after the solve (models.py:280); 0 (default): K v = e - r from the residual the PCG recurrence carries
-    int pcg_lookahead = 1;         // 1: enqueue the next mat-vec before waiting for the stop-test scalar (pcg_impl)
+    int pcg_lookahead = 1;         // 1: enqueue the next mat-vec before waiting for the stop-test scalar (cglb_api.hip: pcg_solve)
     double* gpart = nullptr;       // gradient partial buffers
     size_t gpart_cap = 0;
     double* gradbuf = nullptr;     // device packed gradient [GRAD_LEN]

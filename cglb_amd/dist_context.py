@@ -48,6 +48,13 @@ class DistHipContext(HipContext):
         n = len(X)
         self.per, parts = row_partition(n, self.world)
         super().__init__(X, y, num_inducing, kind, dtype=dtype, device=device, row_range=parts[self.rank])
+        try:
+            self._init_comm(group, collectives, force)
+        except BaseException:
+            super().close()  # or the N x D operands and this rank's panel stay allocated behind a half-made object
+            raise
+
+    def _init_comm(self, group, collectives, force):
         if collectives == "auto":
             collectives = os.environ.get("CGLB_COLLECTIVES") or ("rccl" if dist.get_backend(group) == "nccl" else "callbacks")
         self.collectives = collectives

@@ -430,7 +430,7 @@ class SymShardedCGLB:
         ops.vec_dot(N, self.v, self.v, self.scratch)
         if float(self.scratch.item()) == 0.0:
             # cold start (models.py:59-68): A v == 0 and r == b exactly, so the mat-vec and its all-reduce are skipped
-            # (bit-identical; v is replicated, every rank takes the same branch) - same rule as the fused pcg_impl
+            # (bit-identical; v is replicated, every rank takes the same branch) - same rule as the library's pcg_solve
             self.r.copy_(self.b)
         else:
             self.matvec(self.v, self.Kv)                           # :57
@@ -451,7 +451,7 @@ class SymShardedCGLB:
                 ops.vec_residual(N, self.r, self.b, self.Kv)
             self._precond_and_direction(self.rz_new, self.rz, restart)   # :73, :75
             self.rz, self.rz_new = self.rz_new, self.rz            # :76 (the two scalar slots swap roles: no copy kernel)
-            # Host test of :65 with look-ahead (same rule as the fused pcg_impl): while the residual is still far above the
+            # Host test of :65 with look-ahead (same rule as the library's pcg_solve): while the residual is still far above the
             # tolerance the next mat-vec (kernel + all-reduce) is enqueued before the host waits for this iteration's scalar;
             # if the test then says stop it was wasted work on Ap only.  rz comes from gathered partials -> same decision everywhere.
             pending = self._read_scalar_async(self.rz)

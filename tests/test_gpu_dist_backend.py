@@ -371,6 +371,36 @@ def test_a_rank_without_rows_takes_part_in_every_collective():
     assert abs(out[0][1] - conv.steps) <= 1 and out[0][2] == pytest.approx(conv.bound, rel=1e-8)
 
 
+# ------------------------------------------------------------------------------------- a context after its communicator is gone
+def _comm_destroy_worker(rank, world, port, q):
+    dist = _init(rank, world, port, "gloo")
+    try:
+        from cglb_amd.dist_context import DistHipContext
+        from cglb_amd.hip_context import HipContext
+        N, D, M = 700, 4, 16
+        X, y, Z = orc.synthetic_problem(N, D, M, seed=6)
+        hyp = orc.trained_like_hypers(D, Z)
+        xr = torch.from_numpy(np.random.default_rng(3).standard_normal(N))
+        ctx = DistHipContext(X, y, M, "rbf", collectives="callbacks")
+        ctx.set_hypers(hyp.lengthscales, hyp.variance, hyp.noise, hyp.mean, Z, hyp.jitter)
+        ctx.matvec(xr)                                   # the N-rank mat-vec: cyclic share + all-reduce
+        assert ctx.lib.cglb_comm_destroy(ctx._ctx) == 0  # the context itself stays alive
+        after = HipContext.matvec(ctx, xr).cpu().numpy()
+        fresh = HipContext(X, y, M, "rbf", row_range=(ctx.r0, ctx.r1))
+        fresh.set_hypers(hyp.lengthscales, hyp.variance, hyp.noise, hyp.mean, Z, hyp.jitter)
+        q.put((rank, after, fresh.matvec(xr).cpu().numpy()))
+        ctx.close(); fresh.close()
+    finally:
+        dist.destroy_process_group()
+
+
+def test_plain_matvec_after_comm_destroy_equals_a_fresh_single_rank_context():
+    """cglb_comm_destroy hands the context back as a plain one: no cyclic deal of the mat-vec is left behind with nobody to sum it with.
+    World size 1 here (one GPU); the same worker runs at any world size, each rank comparing over its own rows."""
+    for rank, after, fresh in _spawn(_comm_destroy_worker, 1, (), 1):
+        np.testing.assert_array_equal(after, fresh)
+
+
 # ------------------------------------------------------------------------- the backend API over the nccl (= RCCL) process group, world 1
 def _nccl_backend_worker(rank, world, port, path, tmp, q):
     os.environ["CGLB_FORCE_DIST"] = "1"        # take the N-rank path (DistHipContext, RCCL inside the library) at world size 1

@@ -78,6 +78,30 @@ def test_error_mapping():
         HipContext(X, y, 4, "periodic")
 
 
+def test_failed_evaluations_leave_no_marks_in_the_phase_timing():
+    """eval_profile pairs its HIP events in groups of 5 per evaluation.  An evaluation that returns an error after its first mark
+    (cglb_setup refuses: hypers not set) must leave none behind, or every later eval_*_ms / eval_count pairs events of different
+    evaluations: five stray marks plus the five of one good evaluation would read as two."""
+    from cglb_amd.hip_context import HipContext
+    X, y, Z = orc.synthetic_problem(300, 3, 8, seed=5)
+    hyp = orc.trained_like_hypers(3, Z)
+    ctx = HipContext(X, y, 8, "rbf")
+    ctx.set_option("eval_profile", 1)
+    v = torch.zeros(300, dtype=torch.float64, device=ctx.device)
+    for _ in range(5):
+        with pytest.raises(RuntimeError, match="set_data and set_hypers must precede setup"):
+            ctx.objective_and_grad(v, True, 1.0)
+    ctx.set_hypers(hyp.lengthscales, hyp.variance, hyp.noise, hyp.mean, Z, 1e-6)
+    res = ctx.objective_and_grad(v, True, 1.0)
+    assert np.isfinite(res.bound)
+    count = ctx.get_stat("eval_count")
+    ms = [ctx.get_stat(k) for k in ("eval_setup_ms", "eval_pcg_ms", "eval_final_ms", "eval_grad_ms")]
+    print("eval_count", count, "eval_*_ms", ms)
+    assert count == 1
+    assert all(np.isfinite(t) and t >= 0.0 for t in ms)
+    ctx.close()
+
+
 def test_warm_start_is_not_mutated_by_solver_and_reused_by_objective():
     from cglb_amd.hip_context import HipContext
     X, y, Z = orc.synthetic_problem(500, 3, 16, seed=2)
