@@ -160,24 +160,46 @@ inline int grid1d(int64_t n) {
     return (int)g;
 }
 
-// per-call device temporaries: freed on every exit path of the function that owns the holder
-struct DevTemps {
-    std::vector<void*> ptrs;
-    ~DevTemps() { for (void* p : ptrs) if (p) (void)hipFree(p); }
-    int alloc(cglb_ctx* c, void** out, size_t bytes) {
-        *out = nullptr;
-        hipError_t e = hipMalloc(out, bytes ? bytes : 16);
-        if (e != hipSuccess) return cglb_fail(c, CGLB_ERR_HIP, std::string("hipMalloc of a temporary: ") + hipGetErrorString(e));
-        ptrs.push_back(*out);
-        return CGLB_OK;
-    }
-};
+}  // namespace
 
-int dalloc(cglb_ctx* c, void** p, size_t bytes) {
-    if (bytes == 0) bytes = 16;
-    HIP_CHECK(c, hipMalloc(p, bytes));
+// ---- device memory of a context (cglb_internal.h) ---------------------------------------------------------------
+// a slot is listed once however often it is dropped and filled again
+static void pool_track(cglb_devpool* pool, void** slot, size_t* cap) {
+    for (const cglb_devpool::entry& e : pool->entries) if (e.slot == slot) return;
+    pool->entries.push_back({slot, cap});
+}
+
+int cglb_devpool::alloc(cglb_ctx* c, void** slot, size_t bytes) {
+    if (*slot) return CGLB_OK;
+    HIP_CHECK(c, hipMalloc(slot, bytes ? bytes : 16));  // a request of zero bytes still yields a pointer kernels may be handed
+    pool_track(this, slot, nullptr);
     return CGLB_OK;
 }
+
+// hipFree waits for the work in flight on the device, so growing a buffer that kernels already enqueued on the stream still read is safe.
+// A failed growth leaves *slot == nullptr with *cap == 0: the next call allocates again instead of launching on a null pointer.
+int cglb_devpool::reserve(cglb_ctx* c, void** slot, size_t* cap, size_t need) {
+    if (*slot && need <= *cap) return CGLB_OK;
+    HIP_CHECK(c, drop(slot, cap));
+    HIP_CHECK(c, hipMalloc(slot, need ? need : 16));
+    *cap = need;
+    pool_track(this, slot, cap);
+    return CGLB_OK;
+}
+
+hipError_t cglb_devpool::drop(void** slot, size_t* cap) {
+    const hipError_t e = *slot ? hipFree(*slot) : hipSuccess;
+    *slot = nullptr;
+    if (cap) *cap = 0;
+    return e;
+}
+
+void cglb_devpool::release() {
+    for (const entry& e : entries) (void)drop(e.slot, e.cap);
+    entries.clear();
+}
+
+namespace {
 
 int read_scalars(cglb_ctx* c, const double* dev, double* host, int n) {
     HIP_CHECK(c, hipMemcpyAsync(host, dev, sizeof(double) * n, hipMemcpyDeviceToHost, c->stream));
@@ -236,12 +258,7 @@ int setup_local_impl(cglb_ctx* c) {
         if (group > 64) group = 64;
         if (group > nslab_total) group = nslab_total;
         const size_t need = (size_t)group * M * M * c->esz;
-        if (need > c->slab_cap) {
-            if (c->slabs) HIP_CHECK(c, hipFree(c->slabs));
-            c->slabs = nullptr;
-            HIP_CHECK(c, hipMalloc(&c->slabs, need));
-            c->slab_cap = need;
-        }
+        CGLB_TRY(c->mem.reserve(c, &c->slabs, &c->slab_cap, need));
         T* slabs = (T*)c->slabs;
         const T* At = (const T*)c->At;
         // Only the lower block triangle is computed (the slab sum below reads i >= j and mirrors): with `bs`-wide blocks that is
@@ -448,7 +465,7 @@ int obj_phase1_exact(cglb_ctx* c, void* u_partial) {
 // the v of the exact quadratic term: a device vector of N zeros, made once
 int ensure_zero_vec(cglb_ctx* c) {
     if (c->w_zero) return CGLB_OK;
-    CGLB_TRY(dalloc(c, &c->w_zero, (size_t)c->N * c->esz));
+    CGLB_TRY(c->mem.alloc(c, &c->w_zero, (size_t)c->N * c->esz));
     HIP_CHECK(c, hipMemsetAsync(c->w_zero, 0, (size_t)c->N * c->esz, c->stream));
     return CGLB_OK;
 }
@@ -494,7 +511,7 @@ int obj_phase3_impl(cglb_ctx* c, const void* v_full, const double* sc, const voi
     const double kn = n2m ? (double)c->N / c->n2m_tau : 0.0;  // d logdet / dT = N / (2 tau) of the N^2M bound, times 2
     const T one = 1, zero = 0;
     HIP_CHECK(c, hipMemsetAsync(out, 0, glen * sizeof(double), c->stream));
-    if (!c->Guf) CGLB_TRY(dalloc(c, &c->Guf, (size_t)M * c->lda * c->esz));
+    CGLB_TRY(c->mem.alloc(c, &c->Guf, (size_t)M * c->lda * c->esz));
     // B^-1 = LB^-T LB^-1 and its trace
     BLAS_CHECK(c, xgemm(c->blas, rocblas_operation_transpose, rocblas_operation_none, M, M, M, &one, (const T*)c->LBinv, M, (const T*)c->LBinv, M,
                         &zero, (T*)c->Mtmp, M));
@@ -510,8 +527,8 @@ int obj_phase3_impl(cglb_ctx* c, const void* v_full, const double* sc, const voi
     const T minus_one = -1;
     if (use_inv) {
         CGLB_TRY(ensure_Linv<T>(c));
-        if (!c->Mtmp3) CGLB_TRY(dalloc(c, &c->Mtmp3, (size_t)M * M * c->esz));
-        if (refine && !c->Mtmp4) CGLB_TRY(dalloc(c, &c->Mtmp4, (size_t)M * M * c->esz));
+        CGLB_TRY(c->mem.alloc(c, &c->Mtmp3, (size_t)M * M * c->esz));
+        if (refine) CGLB_TRY(c->mem.alloc(c, &c->Mtmp4, (size_t)M * M * c->esz));
         CGLB_TRY(launch_tri_rowdot(c, c->Linv, aw, 0, c->w_t2));  // (L^-T x)_i = column i of L^-1 (contiguous) . x
         if (refine) {
             CGLB_TRY(launch_tri_rowdot(c, c->Lc, c->w_t2, 0, c->w_q));       // L^T x: column i of L (contiguous) . x
@@ -762,8 +779,7 @@ void comm_free(cglb_ctx* c) {
     if (!m) return;
     if (c->stream) (void)hipStreamSynchronize(c->stream); else (void)hipDeviceSynchronize();
     if (m->kind == 1 && m->nccl) (void)ncclCommDestroy((ncclComm_t)m->nccl);
-    void* ptrs[] = {m->p, m->r, m->Ap, m->Kv, m->b, m->zseg, m->ubuf, m->u, m->aw, m->sc, m->grad, m->gat};
-    for (void* q : ptrs) if (q) (void)hipFree(q);
+    m->mem.release();
     delete m;
     c->comm = nullptr;
 }
@@ -784,13 +800,13 @@ int comm_alloc(cglb_ctx* c, int world, int rank) {
     m->world = world; m->rank = rank; m->per = per;
     const size_t e = c->esz, N = (size_t)c->N, M = (size_t)c->M;
     void** vecs[] = {&m->p, &m->r, &m->Ap, &m->Kv, &m->b};
-    for (void** q : vecs) CGLB_TRY(dalloc(c, q, N * e));
-    CGLB_TRY(dalloc(c, &m->zseg, (size_t)world * (size_t)(per + 1) * e));
-    CGLB_TRY(dalloc(c, &m->ubuf, (size_t)world * (size_t)per * e));
-    CGLB_TRY(dalloc(c, &m->u, M * e));
-    CGLB_TRY(dalloc(c, &m->aw, M * e));
-    CGLB_TRY(dalloc(c, (void**)&m->sc, 8 * sizeof(double)));
-    CGLB_TRY(dalloc(c, (void**)&m->grad, (size_t)CGLB_GRAD_LEN(c->D, c->M) * sizeof(double)));
+    for (void** q : vecs) CGLB_TRY(m->mem.alloc(c, q, N * e));
+    CGLB_TRY(m->mem.alloc(c, &m->zseg, (size_t)world * (size_t)(per + 1) * e));
+    CGLB_TRY(m->mem.alloc(c, &m->ubuf, (size_t)world * (size_t)per * e));
+    CGLB_TRY(m->mem.alloc(c, &m->u, M * e));
+    CGLB_TRY(m->mem.alloc(c, &m->aw, M * e));
+    CGLB_TRY(m->mem.alloc(c, &m->sc, 8 * sizeof(double)));
+    CGLB_TRY(m->mem.alloc(c, &m->grad, (size_t)CGLB_GRAD_LEN(c->D, c->M) * sizeof(double)));
     HIP_CHECK(c, hipMemsetAsync(m->zseg, 0, (size_t)world * (size_t)(per + 1) * e, c->stream));
     HIP_CHECK(c, hipMemsetAsync(m->ubuf, 0, (size_t)world * (size_t)per * e, c->stream));
     c->par_world = world;  // cglb_set_parallel: the cyclic deal of the symmetric K_ff work
@@ -882,16 +898,17 @@ int cglb_ctx_create(cglb_ctx** out, int64_t n_total, int64_t row_begin, int64_t 
     c->esz = dtype == CGLB_F64 ? 8 : 4; c->stream = (hipStream_t)stream;
     auto fail = [&](int rc) { g_create_error = c->err; cglb_ctx_destroy(c); return rc; };
 #define CR(expr) do { int _rc = (expr); if (_rc != CGLB_OK) return fail(_rc); } while (0)
+#define CA(field, bytes) CR(c->mem.alloc(c, &c->field, bytes))  // the context's pool owns the buffer from here on
     { hipError_t e = hipSetDevice(device); if (e != hipSuccess) { c->err = std::string("hipSetDevice: ") + hipGetErrorString(e); return fail(CGLB_ERR_HIP); } }
     { rocblas_status s = rocblas_create_handle(&c->blas); if (s != rocblas_status_success) { c->err = "rocblas_create_handle failed"; c->blas = nullptr; return fail(CGLB_ERR_BLAS); } }
     { rocblas_status s = rocblas_set_stream(c->blas, c->stream); if (s != rocblas_status_success) { c->err = "rocblas_set_stream failed"; return fail(CGLB_ERR_BLAS); } }
     const size_t e = c->esz, N = (size_t)c->N, nl = (size_t)c->nloc, M = (size_t)m, Dp = (size_t)c->Dp;
-    CR(dalloc(c, &c->X, N * d * e)); CR(dalloc(c, &c->y, N * e)); CR(dalloc(c, &c->Z, M * d * e));
-    CR(dalloc(c, &c->Xs, N * Dp * e)); CR(dalloc(c, &c->xa, N * e)); CR(dalloc(c, &c->Zs, M * Dp * e)); CR(dalloc(c, &c->za, M * e));
-    CR(dalloc(c, &c->Zh, M * Dp * e)); CR(dalloc(c, &c->zah, M * e)); CR(dalloc(c, &c->Linv, M * M * e)); CR(dalloc(c, &c->LinvT, M * M * e));
-    CR(dalloc(c, &c->w_q, M * e));
+    CA(X, N * d * e); CA(y, N * e); CA(Z, M * d * e);
+    CA(Xs, N * Dp * e); CA(xa, N * e); CA(Zs, M * Dp * e); CA(za, M * e);
+    CA(Zh, M * Dp * e); CA(zah, M * e); CA(Linv, M * M * e); CA(LinvT, M * M * e);
+    CA(w_q, M * e);
     const size_t hotN = c->Dp > CGLB_MAX_D_NARROW ? 0 : N;  // the hot operand set exists for the register-resident pair kernels only
-    CR(dalloc(c, &c->Xh, c->Dh > 0 ? N * (size_t)c->Dh * e : hotN * Dp * e)); CR(dalloc(c, &c->Xhsq, hotN * Dp * e)); CR(dalloc(c, &c->xah, N * e)); CR(dalloc(c, &c->wh, N * e)); CR(dalloc(c, &c->pwh, N * e)); CR(dalloc(c, (void**)&c->exp_tab, CGLB_TAB_SIZE * sizeof(double)));
+    CA(Xh, c->Dh > 0 ? N * (size_t)c->Dh * e : hotN * Dp * e); CA(Xhsq, hotN * Dp * e); CA(xah, N * e); CA(wh, N * e); CA(pwh, N * e); CA(exp_tab, CGLB_TAB_SIZE * sizeof(double));
     {   // 2^x table of the pair kernels: 2^((k + 1/2)/T) for the floor/fract range reduction (devmath.h)
         std::vector<double> tab(CGLB_TAB_SIZE);
         for (int k = 0; k < CGLB_TAB_SIZE; ++k) {
@@ -904,23 +921,24 @@ int cglb_ctx_create(cglb_ctx** out, int64_t n_total, int64_t row_begin, int64_t 
         hipError_t e3 = hipMemcpy(c->exp_tab, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice);
         if (e3 != hipSuccess) { c->err = "exp table upload failed"; return fail(CGLB_ERR_HIP); }
     }
-    CR(dalloc(c, &c->At, M * (size_t)c->lda * e));
-    CR(dalloc(c, &c->Lc, M * M * e)); CR(dalloc(c, &c->LBc, M * M * e)); CR(dalloc(c, &c->LBinv, M * M * e)); CR(dalloc(c, &c->LBinvT, M * M * e));
-    CR(dalloc(c, &c->AAt, M * M * e)); CR(dalloc(c, &c->Mtmp, M * M * e)); CR(dalloc(c, &c->Mtmp2, M * M * e));
-    CR(dalloc(c, (void**)&c->info_dev, 4 * sizeof(rocblas_int)));
-    CR(dalloc(c, &c->w_r, nl * e)); CR(dalloc(c, &c->w_z, nl * e)); CR(dalloc(c, &c->w_p, nl * e)); CR(dalloc(c, &c->w_Ap, nl * e));
-    CR(dalloc(c, &c->w_Kv, nl * e)); CR(dalloc(c, &c->w_e, nl * e)); CR(dalloc(c, &c->w_pfull, N * e));
-    CR(dalloc(c, &c->w_u, M * e)); CR(dalloc(c, &c->w_t, M * e)); CR(dalloc(c, &c->w_t2, M * e));
-    CR(dalloc(c, &c->tpart, ((M + 63) / 64) * nl * e));
-    CR(dalloc(c, (void**)&c->dotpart, DOTPART_CAP * sizeof(double)));
-    CR(dalloc(c, (void**)&c->scal, 64 * sizeof(double)));
-    CR(dalloc(c, (void**)&c->gradbuf, (size_t)CGLB_GRAD_LEN(d, m) * sizeof(double)));
+    CA(At, M * (size_t)c->lda * e);
+    CA(Lc, M * M * e); CA(LBc, M * M * e); CA(LBinv, M * M * e); CA(LBinvT, M * M * e);
+    CA(AAt, M * M * e); CA(Mtmp, M * M * e); CA(Mtmp2, M * M * e);
+    CA(info_dev, 4 * sizeof(rocblas_int));
+    CA(w_r, nl * e); CA(w_z, nl * e); CA(w_p, nl * e); CA(w_Ap, nl * e);
+    CA(w_Kv, nl * e); CA(w_e, nl * e); CA(w_pfull, N * e);
+    CA(w_u, M * e); CA(w_t, M * e); CA(w_t2, M * e);
+    CA(tpart, ((M + 63) / 64) * nl * e);
+    CA(dotpart, DOTPART_CAP * sizeof(double));
+    CA(scal, 64 * sizeof(double));
+    CA(gradbuf, (size_t)CGLB_GRAD_LEN(d, m) * sizeof(double));
     { hipError_t e2 = hipMemsetAsync(c->scal, 0, 64 * sizeof(double), c->stream); if (e2 != hipSuccess) { c->err = "memset failed"; return fail(CGLB_ERR_HIP); } }
     {
         hipError_t e4 = hipHostMalloc((void**)&c->host_scal, 8 * sizeof(double), hipHostMallocDefault);
         if (e4 == hipSuccess) e4 = hipEventCreateWithFlags(&c->scal_event, hipEventDisableTiming);
         if (e4 != hipSuccess) { c->err = std::string("pinned scalar buffer: ") + hipGetErrorString(e4); return fail(CGLB_ERR_HIP); }
     }
+#undef CA
 #undef CR
     *out = c;
     return CGLB_OK;
@@ -931,12 +949,8 @@ int cglb_ctx_destroy(cglb_ctx* c) {
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream); else (void)hipDeviceSynchronize();
     comm_free(c);
-    wide_free(c);
     n2m_free(c);
-    void* ptrs[] = {c->X, c->y, c->Z, c->Xs, c->xa, c->Zs, c->za, c->Xh, c->Xhsq, c->xah, c->wh, c->pwh, c->exp_tab, c->At, c->Lc, c->LBc, c->LBinv, c->LBinvT, c->AAt, c->Mtmp, c->Mtmp2, c->Mtmp3, c->Guf,
-                    c->info_dev, c->w_r, c->w_z, c->w_p, c->w_Ap, c->w_Kv, c->w_e, c->w_pfull, c->w_u, c->w_t, c->w_t2, c->kpart, c->tpart,
-                    c->dotpart, c->scal, c->gpart, c->gradbuf, c->slabs, c->fragA, c->fragB, c->sym_items, c->Zh, c->zah, c->Linv, c->LinvT, c->w_q, c->ppart, c->chol_blk, c->uwh, c->Mtmp4, c->w_zero};
-    for (void* p : ptrs) if (p) (void)hipFree(p);
+    c->mem.release();
     for (hipEvent_t ev : c->k1_events) (void)hipEventDestroy(ev);
     for (hipEvent_t ev : c->eval_events) (void)hipEventDestroy(ev);
     if (c->host_scal) (void)hipHostFree(c->host_scal);
@@ -1631,12 +1645,7 @@ int cglb_dist_predict(cglb_ctx* c, const void* v_full, const void* xnew, int64_t
     const int64_t pern = (n_new + m->world - 1) / m->world;
     const int64_t a = std::min<int64_t>((int64_t)m->rank * pern, n_new), b = std::min<int64_t>((int64_t)(m->rank + 1) * pern, n_new);
     const size_t need = (size_t)m->world * 2 * (size_t)pern * c->esz;
-    if (need > m->gat_cap) {
-        if (m->gat) HIP_CHECK(c, hipFree(m->gat));
-        m->gat = nullptr; m->gat_cap = 0;
-        HIP_CHECK(c, hipMalloc(&m->gat, need));
-        m->gat_cap = need;
-    }
+    CGLB_TRY(m->mem.reserve(c, &m->gat, &m->gat_cap, need));
     char* mine = (char*)m->gat + (size_t)m->rank * 2 * (size_t)pern * c->esz;
     if (b > a) {
         // xnew may be host or device memory: element offsets are the same either way

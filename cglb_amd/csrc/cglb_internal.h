@@ -16,6 +16,21 @@
 #define CGLB_MAX_D_MID 96     // ... except the symmetric K_ff mat-vec (fp64): up to here it still runs register-resident, the Gram chain in 16-wide slices
 #define CGLB_WAVE 64
 
+// Device memory of a context.  A pool owns the device buffers whose pointers sit in fields ("slots") of cglb_ctx / cglb_comm_state: both are
+// heap objects that are never copied, so the pool keeps the addresses of the fields it has filled and release() frees exactly those.
+// A new buffer needs a field and one alloc / reserve call; nothing else names it.  Defined in cglb_api.hip.
+struct cglb_ctx;
+struct cglb_devpool {
+    struct entry { void** slot; size_t* cap; };
+    std::vector<entry> entries;
+    int alloc(cglb_ctx* c, void** slot, size_t bytes);                   // fixed size, eager or on first use: nothing if *slot is set
+    int reserve(cglb_ctx* c, void** slot, size_t* cap, size_t need);     // grow-only: nothing if *slot holds `need` bytes already
+    hipError_t drop(void** slot, size_t* cap = nullptr);                 // frees one buffer now: *slot = nullptr, *cap = 0
+    void release();                                                      // ... and every buffer the pool has handed out
+    template <typename P> int alloc(cglb_ctx* c, P** slot, size_t bytes) { return alloc(c, (void**)slot, bytes); }
+    template <typename P> int reserve(cglb_ctx* c, P** slot, size_t* cap, size_t need) { return reserve(c, (void**)slot, cap, need); }
+};
+
 // Collectives of the N-rank path inside the library (cglb_comm_init_*, cglb_dist_*; include/cglb_hip.h): RCCL on the context stream, or
 // host-provided callbacks (the same loop over another fabric, e.g. gloo in the tests).
 struct cglb_comm_state {
@@ -36,10 +51,13 @@ struct cglb_comm_state {
     void* gat = nullptr;    // prediction gather buffer
     size_t gat_cap = 0;
     long long n_allreduce = 0, n_allgather = 0;  // collectives issued since cglb_comm_init (cglb_get_stat)
+    cglb_devpool mem;      // owns every device buffer above; released by comm_free
 };
 
 struct cglb_ctx {
     cglb_comm_state* comm = nullptr;
+    cglb_devpool mem;      // owns every device buffer below but the n2m_* ones; released by cglb_ctx_destroy
+    cglb_devpool n2m_mem;  // owns the n2m_* buffers; released by n2m_free (a changed "n2m_tile" drops the tiles) and cglb_ctx_destroy
     // geometry
     int64_t N = 0, r0 = 0, r1 = 0, nloc = 0, lda = 0;  // lda: leading dimension of At/Guf (nloc rounded up to 8)
     int D = 0, Dp = 0, M = 0, dtype = CGLB_F64, kind = CGLB_RBF, device = 0;
@@ -75,8 +93,8 @@ struct cglb_ctx {
     // wide inputs (D > 32, kernels_wide.hip): element-wise squares of the scaled operands, tile / panel / moment scratch, device copies of
     // the per-dimension centre and scale
     void *Xsq = nullptr, *Zsq = nullptr;
-    void *wtile = nullptr, *wpart = nullptr, *wS1 = nullptr, *wVX = nullptr, *wR = nullptr, *wC = nullptr, *wones = nullptr, *wpanel = nullptr;
-    size_t wtile_cap = 0, wpart_cap = 0, wS1_cap = 0, wpanel_cap = 0, wvec_cap = 0;
+    void *wtile = nullptr, *wpart = nullptr, *wS1 = nullptr, *wR = nullptr, *wC = nullptr, *wones = nullptr, *wpanel = nullptr;
+    size_t wtile_cap = 0, wpart_cap = 0, wS1_cap = 0, wpanel_cap = 0;
     void* wlong = nullptr;   // slabs of a long-k GEMM cut into chunks (kernels_wide.hip: gemm_long_k)
     size_t wlong_cap = 0;
     double *wcenter = nullptr, *wscale = nullptr, *wsmall = nullptr;
@@ -102,7 +120,7 @@ struct cglb_ctx {
     double L_diag_ratio = 1.0;  // max diag(L) / min diag(L) of the current K_uu factor (cglb_get_stat "L_diag_ratio")
     void* Guf = nullptr;     // adjoint of Kuf, same layout as At (allocated on first gradient)
     void *fragA = nullptr, *fragB = nullptr;  // MFMA-ordered augmented operands (kernels_kff_mfma.hip)
-    size_t frag_cap = 0;
+    size_t fragA_cap = 0, fragB_cap = 0;
     bool frag_valid = false;  // fragA / fragB (operands of the experimental matrix-pipe variant) match the current hypers
     void* sym_items = nullptr;       // work list (row block, column chunk) of the symmetric mat-vec
     int64_t sym_n = -1, sym_chunk = 0, sym_chunk_opt = 0;
@@ -203,6 +221,19 @@ static inline int cglb_fail(cglb_ctx* ctx, int code, const std::string& msg) {
     return code;
 }
 
+// per-call device temporaries: freed on every exit path of the function that owns the holder
+struct DevTemps {
+    std::vector<void*> ptrs;
+    ~DevTemps() { for (void* p : ptrs) if (p) (void)hipFree(p); }
+    int alloc(cglb_ctx* c, void** out, size_t bytes) {
+        *out = nullptr;
+        hipError_t e = hipMalloc(out, bytes ? bytes : 16);
+        if (e != hipSuccess) return cglb_fail(c, CGLB_ERR_HIP, std::string("hipMalloc of a temporary: ") + hipGetErrorString(e));
+        ptrs.push_back(*out);
+        return CGLB_OK;
+    }
+};
+
 static inline int pad_dim(int d) {
     const int sizes[] = {1, 2, 3, 4, 6, 8, 10, 12, 16, 20, 24, 28, 32};  // 10, 20 and 28: the reference's own data sets have D = 9, 17, 18, 26, 27
     for (int s : sizes)
@@ -232,7 +263,6 @@ int wide_matvec(cglb_ctx* c, const void* XsRow, const void* xaRow, int64_t row0_
 int wide_grad_kff(cglb_ctx* c, const void* v_full, const void* u_rows, int64_t row0, int64_t nrows, int tile_stride, int tile_offset, double* out_dl);
 int wide_grad_panel(cglb_ctx* c, const void* G, int64_t ldg, const void* cvec, const void* wvec, const void* XsCol, const void* xaCol, const void* XsqCol,
                     int64_t ncols, double zfactor, double* out);
-void wide_free(cglb_ctx* c);
 // N^2M log-det bound (kernels_n2m.hip): the terms of the bound after setup, the kernel-hyper-parameter part of its gradient in phase 3
 int n2m_setup(cglb_ctx* c);  // W = K_ff A^T, H = A W, tau, <B^-1, H>, tr B^-1
 int n2m_grad_terms(cglb_ctx* c, const double* Binv);  // E (n2m_E, trace in n2m_scal[2]) and n2m_gacc[d] = sum_ij G_ij dK_ij/dl_d, G = C^T C
@@ -250,13 +280,12 @@ int launch_kff_matvec(cglb_ctx* c, const void* p_full, void* out_local, double* 
 int launch_cholesky_lower(cglb_ctx* c, void* A, int* info_slot);
 int launch_frag_prep(cglb_ctx* c);
 int launch_kff_sym(cglb_ctx* c, const void* p_full, void* out_local, double* pdot_slot);
-int launch_hot_weights(cglb_ctx* c);
+int launch_hot_weights(cglb_ctx* c);  // wh = 2^(xah/T) after set_hypers (RBF)
 int launch_kff_sym_mid(cglb_ctx* c, const void* p_full, void* out, double* pdot_slot, bool cyclic);  // 32 < D <= 96, fp64 (kernels_kff_sym.hip)
-int ensure_gpart(cglb_ctx* c, size_t need);   // partial-sum slab of the gradient passes (kernels_grad.hip)
 int grad_fold_operands(cglb_ctx* c, const void* v_full, const void* u, int64_t off, int64_t n_u, bool* fold);  // column-side copies u o w, v o w (folded column norm)
 int launch_grad_kff_mid(cglb_ctx* c, const void* v_full, const void* u_full, int world, int rank, double* out_dl);  // kernels_grad_mid.hip
 int launch_hot_squares(cglb_ctx* c);  // Xhsq = Xh .* Xh after set_hypers
-int k1_profile_collect(cglb_ctx* c);  // resolves the pending event pairs into k1_ms_total / k1_launches  // wh = 2^(xah/T) after set_hypers (RBF)
+int k1_profile_collect(cglb_ctx* c);  // resolves the pending event pairs into k1_ms_total / k1_launches
 int launch_kff_sym_cyclic(cglb_ctx* c, const void* p_full, void* out_full_partial);  // this rank's share of the global upper triangle
 int launch_grad_kff_cyclic(cglb_ctx* c, const void* v_full, const void* u_full, double* out_dl);
 int launch_kff_plain_range(cglb_ctx* c, const void* p_full, int64_t col0, int64_t col1, void* part, int64_t* nslots);

@@ -214,7 +214,7 @@ __global__ __launch_bounds__(256) void chol_update_kernel(T* __restrict__ A, int
 template <typename T>
 static int cholesky_impl(cglb_ctx* c, T* A, int* info_slot) {
     const int n = c->M;
-    if (!c->chol_blk) HIP_CHECK(c, hipMalloc(&c->chol_blk, (CHOL_NB * CHOL_NB + CHOL_NB) * sizeof(double)));
+    CGLB_TRY(c->mem.alloc(c, &c->chol_blk, (CHOL_NB * CHOL_NB + CHOL_NB) * sizeof(double)));
     T* Dblk = (T*)c->chol_blk;
     HIP_CHECK(c, hipMemsetAsync(info_slot, 0, sizeof(int), c->stream));
     for (int k0 = 0; k0 < n; k0 += CHOL_NB) {

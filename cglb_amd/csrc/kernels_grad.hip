@@ -303,16 +303,6 @@ __global__ __launch_bounds__(256) void grad_dl_finalize_kernel(const double* __r
     }
 }
 
-int ensure_gpart(cglb_ctx* c, size_t need) {
-    if (need > c->gpart_cap) {
-        if (c->gpart) HIP_CHECK(c, hipFree(c->gpart));
-        c->gpart = nullptr;
-        HIP_CHECK(c, hipMalloc((void**)&c->gpart, need));
-        c->gpart_cap = need;
-    }
-    return CGLB_OK;
-}
-
 // rows per lane of the Gram-form kernel when D <= 8 (4 rows - 204 VGPRs, 2 waves per SIMD - measured 6.28 ms against 5.55 ms)
 #ifndef CGLB_GRAM_R2_MAX_DP
 #define CGLB_GRAM_R2_MAX_DP 12  // widest padded row with CGLB_GRAM_ROWS rows per lane in the Gram-form kernel (DP = 12: 8.4 -> 7.2 ms at N = 100k against 1 row)
@@ -339,7 +329,7 @@ __global__ __launch_bounds__(256) void grad_weight_kernel(const T* __restrict__ 
 int grad_fold_operands(cglb_ctx* c, const void* v_full, const void* u, int64_t off, int64_t n_u, bool* fold) {
     *fold = c->kind == CGLB_RBF && !c->exp_clamp && c->dtype == CGLB_F64 && c->have_hypers;
     if (!*fold) return CGLB_OK;
-    if (!c->uwh) HIP_CHECK(c, hipMalloc(&c->uwh, (size_t)c->N * c->esz));
+    CGLB_TRY(c->mem.alloc(c, &c->uwh, (size_t)c->N * c->esz));
     c->pwh_src = nullptr;  // pwh no longer holds the weighted direction of the PCG loop
     const int64_t n = c->N > n_u ? c->N : n_u;
     hipLaunchKernelGGL((grad_weight_kernel<double>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, (const double*)v_full, c->N,
@@ -386,7 +376,7 @@ int launch_grad_kff(cglb_ctx* c, const void* v_full, const void* u_local, double
         r.jsplit = (r.ncols + r.jchunk - 1) / r.jchunk;
         nblk += bx * r.jsplit;
     }
-    CGLB_TRY(ensure_gpart(c, (size_t)nblk * c->Dp * sizeof(double)));
+    CGLB_TRY(c->mem.reserve(c, &c->gpart, &c->gpart_cap, (size_t)nblk * c->Dp * sizeof(double)));
     int64_t blk0 = 0;
     for (auto& r : rg) {
         if (r.ncols <= 0) continue;
@@ -448,7 +438,7 @@ int launch_grad_kff_cyclic(cglb_ctx* c, const void* v_full, const void* u_full, 
     const int64_t jchunk = (c->N + js - 1) / js;
     const int64_t jsplit = (c->N + jchunk - 1) / jchunk;
     const int64_t nblk = bx * jsplit;
-    CGLB_TRY(ensure_gpart(c, (size_t)nblk * c->Dp * sizeof(double)));
+    CGLB_TRY(c->mem.reserve(c, &c->gpart, &c->gpart_cap, (size_t)nblk * c->Dp * sizeof(double)));
     dim3 grid((unsigned)bx, (unsigned)jsplit);
 #define GKC_LAUNCH(RR)                                                                                                            \
     hipLaunchKernelGGL((grad_kff_kernel<T, KIND, DP, RR, true, PREC>), grid, dim3(256), 0, c->stream, (const T*)c->Xh, (const T*)u_full,  \
@@ -571,7 +561,7 @@ static int grad_panel(cglb_ctx* c, const void* G, int64_t ldg, const void* cvec,
     const int64_t chunk = (ncols + nsplit - 1) / nsplit;
     nsplit = (int)((ncols + chunk - 1) / chunk);
     const int W = 2 * c->Dp + 1;
-    CGLB_TRY(ensure_gpart(c, (size_t)c->M * nsplit * W * sizeof(double)));
+    CGLB_TRY(c->mem.reserve(c, &c->gpart, &c->gpart_cap, (size_t)c->M * nsplit * W * sizeof(double)));
     dim3 grid((unsigned)c->M, (unsigned)nsplit);
     CGLB_DISPATCH_ALL(c, hipLaunchKernelGGL((grad_panel_kernel<T, KIND, DP>), grid, dim3(256), 0, c->stream, (const T*)G, ldg,
                                             (const T*)cvec, (const T*)wvec, (const T*)c->Zs, (const T*)XsCol, ncols, chunk, c->gpart));

@@ -171,7 +171,7 @@ int launch_grad_kff_mid(cglb_ctx* c, const void* v_full, const void* u_full, int
     const int64_t jchunk = (c->N + js - 1) / js;
     const int64_t jsplit = (c->N + jchunk - 1) / jchunk;
     const int64_t nblk = bx * jsplit;
-    CGLB_TRY(ensure_gpart(c, (size_t)nblk * c->Dh * sizeof(double)));
+    CGLB_TRY(c->mem.reserve(c, &c->gpart, &c->gpart_cap, (size_t)nblk * c->Dh * sizeof(double)));
     dim3 grid((unsigned)bx, (unsigned)jsplit);
     const bool lowprec = c->precision != CGLB_PREC_EXACT;   // level 2 runs as level 1 here
 #define GM_LAUNCH1(DPV, PR, CL) do { if (DPV == 96 && split == 4) { GM_LAUNCH0(DPV, PR, CL, (DPV == 96 ? 4 : 2)); } else { GM_LAUNCH0(DPV, PR, CL, 2); } } while (0)

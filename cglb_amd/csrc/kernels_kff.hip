@@ -263,12 +263,7 @@ static int kff_generic(cglb_ctx* c, const T* XsRow, const T* xaRow, int64_t nrow
                        T noise, double* pdot_slot) {
     if (nrows == 0) return CGLB_OK;
     const size_t need = (size_t)512 * nrows * sizeof(T);
-    if (need > c->kpart_cap) {
-        if (c->kpart) HIP_CHECK(c, hipFree(c->kpart));
-        c->kpart = nullptr;
-        HIP_CHECK(c, hipMalloc(&c->kpart, need));
-        c->kpart_cap = need;
-    }
+    CGLB_TRY(c->mem.reserve(c, &c->kpart, &c->kpart_cap, need));
     int64_t jsplit = 1;
     CGLB_TRY((kff_pairs_range<T, KIND, DP>(c, XsRow, xaRow, nrows, p_full, 0, c->N, (T*)c->kpart, 512, &jsplit)));
     return kff_combine<T>(c, jsplit, nrows, out, pdiag, noise, pdot_slot);
@@ -292,12 +287,7 @@ static int kff_rect_generic(cglb_ctx* c, const T* XsRow, const T* xaRow, int64_t
     chunk = (chunk + 15) / 16 * 16;
     nchunk = (ncols + chunk - 1) / chunk;
     const size_t need = (size_t)nchunk * nrows * sizeof(T);
-    if (need > c->ppart_cap) {
-        if (c->ppart) HIP_CHECK(c, hipFree(c->ppart));
-        c->ppart = nullptr;
-        HIP_CHECK(c, hipMalloc(&c->ppart, need));
-        c->ppart_cap = need;
-    }
+    CGLB_TRY(c->mem.reserve(c, &c->ppart, &c->ppart_cap, need));
     const int64_t nitems = nrb * nchunk;
     const unsigned grid = (unsigned)((nitems + 3) / 4);
     CGLB_DISPATCH_PREC(c, hipLaunchKernelGGL((kff_rect_kernel<T, KIND, DP, R, PREC>), dim3(grid), dim3(256), 0, c->stream, XsRow, xaRow, nrows, XsCol, xaCol,

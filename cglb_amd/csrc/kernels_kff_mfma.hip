@@ -54,14 +54,8 @@ int launch_frag_prep(cglb_ctx* c) {
     const int KA = (c->D + 2 + 3) / 4;
     const int64_t nblk16 = (c->N + 15) / 16;
     const size_t need = (size_t)nblk16 * KA * 64 * sizeof(double);
-    if (need > c->frag_cap) {
-        if (c->fragA) HIP_CHECK(c, hipFree(c->fragA));
-        if (c->fragB) HIP_CHECK(c, hipFree(c->fragB));
-        c->fragA = c->fragB = nullptr;
-        HIP_CHECK(c, hipMalloc(&c->fragA, need));
-        HIP_CHECK(c, hipMalloc(&c->fragB, need));
-        c->frag_cap = need;
-    }
+    CGLB_TRY(c->mem.reserve(c, &c->fragA, &c->fragA_cap, need));
+    CGLB_TRY(c->mem.reserve(c, &c->fragB, &c->fragB_cap, need));
     const int64_t total = nblk16 * KA * 64;
     const int grid = (int)((total + 255) / 256);
     for (int side = 0; side < 2; ++side) {
@@ -194,12 +188,7 @@ int launch_kff_mfma_pairs(cglb_ctx* c, const double* p_full, int64_t* jsplit_out
     if (js > 512) js = 512;
     if (js > njt) js = njt;
     const size_t need = (size_t)js * nrows * sizeof(double);
-    if (need > c->kpart_cap) {
-        if (c->kpart) HIP_CHECK(c, hipFree(c->kpart));
-        c->kpart = nullptr;
-        HIP_CHECK(c, hipMalloc(&c->kpart, need));
-        c->kpart_cap = need;
-    }
+    CGLB_TRY(c->mem.reserve(c, &c->kpart, &c->kpart_cap, need));
     if (!c->frag_valid) {
         CGLB_TRY(launch_frag_prep(c));
         c->frag_valid = true;

@@ -545,11 +545,10 @@ static int ensure_sym_items(cglb_ctx* c, int64_t n, int rbrows, int64_t chunk, i
         }
     }
     c->sym_pairs = pairs;
-    if (c->sym_items) HIP_CHECK(c, hipFree(c->sym_items));
-    c->sym_items = nullptr;
+    HIP_CHECK(c, c->mem.drop(&c->sym_items));  // the list is replaced, at its new size
     if (order.empty()) { order.push_back(make_int2(-1, -1)); items.assign(4, make_int2(-1, -1)); }  // keep the allocation non-empty
     // one allocation: the items first, the groups behind them
-    HIP_CHECK(c, hipMalloc(&c->sym_items, (items.size() + order.size()) * sizeof(int2)));
+    CGLB_TRY(c->mem.alloc(c, &c->sym_items, (items.size() + order.size()) * sizeof(int2)));
     HIP_CHECK(c, hipMemcpyAsync(c->sym_items, items.data(), items.size() * sizeof(int2), hipMemcpyHostToDevice, c->stream));
     HIP_CHECK(c, hipMemcpyAsync((int2*)c->sym_items + items.size(), order.data(), order.size() * sizeof(int2), hipMemcpyHostToDevice, c->stream));
     HIP_CHECK(c, hipStreamSynchronize(c->stream));
@@ -591,17 +590,14 @@ static int kff_sym_generic(cglb_ctx* c, const T* p_full, T* out_local, double* p
     const int64_t prow_ld = (int64_t)ncslot * RBROWS;  // compact rows of this rank's row blocks
     const size_t need = (((size_t)plain_slots_max + ngslot) * n + (size_t)nchunk * prow_ld) * sizeof(T);
     if (need > c->kpart_cap) {
-        if (c->kpart) HIP_CHECK(c, hipFree(c->kpart));
-        c->kpart = nullptr;
-        c->kpart_cap = 0;
+        HIP_CHECK(c, c->mem.drop(&c->kpart, &c->kpart_cap));  // the old slabs count as free below
         size_t free_b = 0, total_b = 0;
         HIP_CHECK(c, hipMemGetInfo(&free_b, &total_b));
         if (need > free_b)  // the partial-sum slabs grow as N^2 / 256 elements per rank: say so instead of failing inside hipMalloc
             return cglb_fail(c, CGLB_ERR_HIP, "K_ff mat-vec needs " + std::to_string(need >> 20) + " MiB of partial-sum slabs (N^2/256 + N^2/chunk elements per rank) but only " +
                                                   std::to_string(free_b >> 20) + " MiB of device memory are free: shard the rows over more GPUs");
-        HIP_CHECK(c, hipMalloc(&c->kpart, need));
-        c->kpart_cap = need;
     }
+    CGLB_TRY(c->mem.reserve(c, &c->kpart, &c->kpart_cap, need));
     T* plain = (T*)c->kpart;
     int64_t nplain = 0;
     if (nleft > 0) {

@@ -154,11 +154,7 @@ __global__ __launch_bounds__(256) void n2m_add_kernel(const double* __restrict__
     if (k < n) out[k] = P[k] + a * Q[k];
 }
 
-int n2m_alloc(cglb_ctx* c, double** p, size_t elems) {
-    if (*p) return CGLB_OK;
-    HIP_CHECK(c, hipMalloc((void**)p, (elems ? elems : 2) * sizeof(double)));
-    return CGLB_OK;
-}
+inline int n2m_alloc(cglb_ctx* c, double** p, size_t elems) { return c->n2m_mem.alloc(c, p, elems * sizeof(double)); }
 
 inline int64_t n2m_tiles(const cglb_ctx* c) { return (c->N + c->n2m_bt - 1) / c->n2m_bt; }
 
@@ -268,7 +264,6 @@ int n2m_grad_terms(cglb_ctx* c, const double* Binv) {
 }
 
 void n2m_free(cglb_ctx* c) {
-    double** ptrs[] = {&c->n2m_Xn, &c->n2m_Wt, &c->n2m_Ct, &c->n2m_K, &c->n2m_G, &c->n2m_H, &c->n2m_E, &c->n2m_T, &c->n2m_ls, &c->n2m_part, &c->n2m_gacc, &c->n2m_scal};
-    for (double** p : ptrs) { if (*p) (void)hipFree(*p); *p = nullptr; }
+    c->n2m_mem.release();
     c->n2m_bt = 0;
 }

@@ -150,20 +150,13 @@ static int select_impl(cglb_ctx* c, double variance, double jitter, long long* c
     T *C = nullptr, *d = nullptr, *cjv = nullptr, *pval = nullptr;
     long long* pidx = nullptr;
     SelPivot* piv = nullptr;
-    auto cleanup = [&]() {
-        (void)hipFree(C); (void)hipFree(d); (void)hipFree(cjv); (void)hipFree(pval); (void)hipFree(pidx); (void)hipFree(piv);
-    };
-#define SEL_HIP(expr)                                                                   \
-    do {                                                                                \
-        hipError_t _e = (expr);                                                         \
-        if (_e != hipSuccess) { cleanup(); return cglb_fail(c, CGLB_ERR_HIP, hipGetErrorString(_e)); } \
-    } while (0)
-    SEL_HIP(hipMalloc(&C, (size_t)M * n * sizeof(T)));
-    SEL_HIP(hipMalloc(&d, (size_t)n * sizeof(T)));
-    SEL_HIP(hipMalloc(&cjv, (size_t)M * sizeof(T)));
-    SEL_HIP(hipMalloc(&pval, (size_t)nparts * sizeof(T)));
-    SEL_HIP(hipMalloc(&pidx, (size_t)nparts * sizeof(long long)));
-    SEL_HIP(hipMalloc(&piv, sizeof(SelPivot)));
+    DevTemps tmp;  // freed on every path below
+    CGLB_TRY(tmp.alloc(c, (void**)&C, (size_t)M * n * sizeof(T)));
+    CGLB_TRY(tmp.alloc(c, (void**)&d, (size_t)n * sizeof(T)));
+    CGLB_TRY(tmp.alloc(c, (void**)&cjv, (size_t)M * sizeof(T)));
+    CGLB_TRY(tmp.alloc(c, (void**)&pval, (size_t)nparts * sizeof(T)));
+    CGLB_TRY(tmp.alloc(c, (void**)&pidx, (size_t)nparts * sizeof(long long)));
+    CGLB_TRY(tmp.alloc(c, (void**)&piv, sizeof(SelPivot)));
     hipLaunchKernelGGL((select_init_kernel<T>), dim3(nparts), dim3(256), 0, c->stream, n, (T)variance, (T)jitter, d, pval, pidx);
     hipLaunchKernelGGL((select_pivot_kernel<T>), dim3(1), dim3(256), 0, c->stream, (const T*)pval, (const long long*)pidx, nparts, (const T*)C, n,
                        0, piv, cjv, chosen_dev, 0);
@@ -178,10 +171,8 @@ static int select_impl(cglb_ctx* c, double variance, double jitter, long long* c
         hipLaunchKernelGGL((select_gather_kernel<T, DP>), dim3((unsigned)((M * c->D + 255) / 256)), dim3(256), 0, c->stream, (const T*)c->X, c->D,
                            (const long long*)chosen_dev, M, (T*)Z_out);
     hipLaunchKernelGGL((select_trace_kernel<T>), dim3(1), dim3(256), 0, c->stream, (const T*)d, n, trace_dev);
-    SEL_HIP(hipGetLastError());
-    SEL_HIP(hipStreamSynchronize(c->stream));
-#undef SEL_HIP
-    cleanup();
+    HIP_CHECK(c, hipGetLastError());
+    HIP_CHECK(c, hipStreamSynchronize(c->stream));
     return CGLB_OK;
 }
 

@@ -265,12 +265,7 @@ int launch_gemv_u(cglb_ctx* c, const void* r_local, void* u_out) {
     nsplit = (int)((c->nloc + chunk - 1) / chunk);
     if (nsplit < 1) nsplit = 1;
     const size_t need = (size_t)c->M * nsplit * sizeof(double);
-    if (need > c->gpart_cap) {
-        if (c->gpart) HIP_CHECK(c, hipFree(c->gpart));
-        c->gpart = nullptr;
-        HIP_CHECK(c, hipMalloc((void**)&c->gpart, need));
-        c->gpart_cap = need;
-    }
+    CGLB_TRY(c->mem.reserve(c, &c->gpart, &c->gpart_cap, need));
     dim3 grid((unsigned)((c->M + GU_ROWS - 1) / GU_ROWS), (unsigned)nsplit);
     CGLB_DISPATCH_T(c->dtype, hipLaunchKernelGGL((gemv_u_kernel<T>), grid, dim3(256), 0, c->stream, (const T*)c->At, c->lda,
                                                  (const T*)r_local, c->nloc, c->M, chunk, c->gpart, nsplit == 1 ? (T*)u_out : (T*)nullptr));

@@ -50,16 +50,6 @@ inline rocblas_status wgemv(rocblas_handle h, rocblas_operation t, int m, int n,
     return rocblas_sgemv(h, t, m, n, &a, A, lda, x, 1, &b, y, 1);
 }
 
-int wensure(cglb_ctx* c, void** p, size_t* cap, size_t need) {
-    if (need <= *cap && *p) return CGLB_OK;
-    if (*p) HIP_CHECK(c, hipFree(*p));
-    *p = nullptr;
-    *cap = 0;
-    HIP_CHECK(c, hipMalloc(p, need ? need : 16));
-    *cap = need;
-    return CGLB_OK;
-}
-
 // ---- operand preparation: xs = (x - centre) * scale, a = norm term, xsq = xs o xs ---------------------------------------------------
 template <typename T, int KIND>
 __global__ __launch_bounds__(256) void wide_prep_kernel(const T* __restrict__ X, int64_t n, int D, const double* __restrict__ center,
@@ -310,11 +300,9 @@ inline double kscale_of(const cglb_ctx* c) { return (c->kind == CGLB_RBF) ? sqrt
 // device copies of centre / scale and the per-dimension gradient factors: wsmall = [sl (D): 1/(l ks^2) | sz (D): 1/(l ks) | 3 x D scratch]
 int upload_scales(cglb_ctx* c) {
     const int D = c->D;
-    if (!c->wcenter) {
-        HIP_CHECK(c, hipMalloc((void**)&c->wcenter, (size_t)D * sizeof(double)));
-        HIP_CHECK(c, hipMalloc((void**)&c->wscale, (size_t)D * sizeof(double)));
-        HIP_CHECK(c, hipMalloc((void**)&c->wsmall, (size_t)5 * D * sizeof(double)));
-    }
+    CGLB_TRY(c->mem.alloc(c, &c->wcenter, (size_t)D * sizeof(double)));
+    CGLB_TRY(c->mem.alloc(c, &c->wscale, (size_t)D * sizeof(double)));
+    CGLB_TRY(c->mem.alloc(c, &c->wsmall, (size_t)5 * D * sizeof(double)));
     std::vector<double> h(4 * (size_t)D);
     const double ks = kscale_of(c);
     for (int d = 0; d < D; ++d) {
@@ -333,9 +321,9 @@ int upload_scales(cglb_ctx* c) {
 int ensure_ones(cglb_ctx* c) {
     const int64_t n = std::max<int64_t>(c->N, c->M);
     if (c->wones) return CGLB_OK;
-    HIP_CHECK(c, hipMalloc(&c->wones, (size_t)n * c->esz));
-    HIP_CHECK(c, hipMalloc(&c->wR, (size_t)n * c->esz));
-    HIP_CHECK(c, hipMalloc(&c->wC, (size_t)n * c->esz));
+    CGLB_TRY(c->mem.alloc(c, &c->wones, (size_t)n * c->esz));
+    CGLB_TRY(c->mem.alloc(c, &c->wR, (size_t)n * c->esz));
+    CGLB_TRY(c->mem.alloc(c, &c->wC, (size_t)n * c->esz));
     CGLB_DISPATCH_T(c->dtype, hipLaunchKernelGGL((wide_fill_kernel<T>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, (T*)c->wones, n, (T)1));
     CGLB_LAUNCH_CHECK(c);
     return CGLB_OK;
@@ -352,9 +340,9 @@ template <typename T, int KIND>
 int matvec_impl(cglb_ctx* c, const T* XsRow, const T* xaRow, int64_t row0_global, int64_t nrows, const T* p_full, T* out, bool diag_noise,
                 double* pdot_slot, int tile_stride, int tile_offset) {
     const int64_t N = c->N;
-    CGLB_TRY(wensure(c, &c->wtile, &c->wtile_cap, (size_t)TILE * TILE * sizeof(T)));
+    CGLB_TRY(c->mem.reserve(c, &c->wtile, &c->wtile_cap, (size_t)TILE * TILE * sizeof(T)));
     // [row-sum partials: (TILE / CSLICE) x TILE | column-sum partials: (TILE / 64) x TILE]
-    CGLB_TRY(wensure(c, &c->wpart, &c->wpart_cap, (size_t)2 * (TILE / CSLICE) * TILE * sizeof(T)));
+    CGLB_TRY(c->mem.reserve(c, &c->wpart, &c->wpart_cap, (size_t)2 * (TILE / CSLICE) * TILE * sizeof(T)));
     T* G = (T*)c->wtile;
     T* part = (T*)c->wpart;
     T* pcpart = part + (size_t)(TILE / CSLICE) * TILE;
@@ -400,11 +388,6 @@ int matvec_impl(cglb_ctx* c, const T* XsRow, const T* xaRow, int64_t row0_global
 }  // namespace
 
 // =========================================================== launchers ===========================================================
-void wide_free(cglb_ctx* c) {
-    void* ptrs[] = {c->wlong, c->Xsq, c->Zsq, c->wtile, c->wpart, c->wS1, c->wVX, c->wR, c->wC, c->wones, c->wpanel, c->wcenter, c->wscale, c->wsmall};
-    for (void* p : ptrs) if (p) (void)hipFree(p);
-}
-
 // xs, a (and xs o xs when asked) of n raw rows; centre and scale come from the device copies refreshed by wide_after_hypers
 int wide_prep_scaled(cglb_ctx* c, const void* Xraw, int64_t n, void* Xs_out, void* xa_out, void* Xsq_out) {
     if (n == 0) return CGLB_OK;
@@ -418,8 +401,8 @@ int wide_prep_scaled(cglb_ctx* c, const void* Xraw, int64_t n, void* Xs_out, voi
 
 // after the lengthscales changed: device copies of the scales, scaled operands of X and Z with their squares
 int wide_after_hypers(cglb_ctx* c) {
-    if (!c->Xsq) HIP_CHECK(c, hipMalloc(&c->Xsq, (size_t)c->N * c->D * c->esz));
-    if (!c->Zsq) HIP_CHECK(c, hipMalloc(&c->Zsq, (size_t)c->M * c->D * c->esz));
+    CGLB_TRY(c->mem.alloc(c, &c->Xsq, (size_t)c->N * c->D * c->esz));
+    CGLB_TRY(c->mem.alloc(c, &c->Zsq, (size_t)c->M * c->D * c->esz));
     CGLB_TRY(ensure_ones(c));
     CGLB_TRY(wide_prep_scaled(c, c->X, c->N, c->Xs, c->xa, c->Xsq));
     CGLB_TRY(wide_prep_scaled(c, c->Z, c->M, c->Zs, c->za, c->Zsq));
@@ -486,13 +469,13 @@ int wide_grad_kff(cglb_ctx* c, const void* v_full_, const void* u_rows_, int64_t
     CGLB_TRY(ensure_ones(c));
     CGLB_DISPATCH_T(c->dtype, CGLB_DISPATCH_KIND(c->kind, {
         const T *v = (const T*)v_full_, *u = (const T*)u_rows_;
-        CGLB_TRY(wensure(c, &c->wtile, &c->wtile_cap, (size_t)TILE * TILE * sizeof(T)));
-        CGLB_TRY(wensure(c, &c->wS1, &c->wS1_cap, (size_t)2 * N * D * sizeof(T)));   // [T' (nrows x D) | VX (N x D)]
+        CGLB_TRY(c->mem.reserve(c, &c->wtile, &c->wtile_cap, (size_t)TILE * TILE * sizeof(T)));
+        CGLB_TRY(c->mem.reserve(c, &c->wS1, &c->wS1_cap, (size_t)2 * N * D * sizeof(T)));   // [T' (nrows x D) | VX (N x D)]
         T* G = (T*)c->wtile;
         T* Tp = (T*)c->wS1;
         T* VX = Tp + (size_t)N * D;
         T *R = (T*)c->wR, *C = (T*)c->wC;   // R: rows of this call, C: all columns
-        CGLB_TRY(wensure(c, &c->wpart, &c->wpart_cap, (size_t)4 * (TILE / CSLICE) * TILE * sizeof(T)));   // two row-partial and two column-partial slabs
+        CGLB_TRY(c->mem.reserve(c, &c->wpart, &c->wpart_cap, (size_t)4 * (TILE / CSLICE) * TILE * sizeof(T)));   // two row-partial and two column-partial slabs
         T* tmp = (T*)c->wpart;
         HIP_CHECK(c, hipMemsetAsync(Tp, 0, (size_t)nrows * D * sizeof(T), c->stream));
         HIP_CHECK(c, hipMemsetAsync(R, 0, (size_t)nrows * sizeof(T), c->stream));
@@ -576,7 +559,7 @@ int gemm_long_k(cglb_ctx* c, int m, int n, int64_t k, const T* A, int lda, const
         return CGLB_OK;
     }
     const int64_t count = (int64_t)m * n;
-    CGLB_TRY(wensure(c, &c->wlong, &c->wlong_cap, (size_t)nb * count * sizeof(T)));
+    CGLB_TRY(c->mem.reserve(c, &c->wlong, &c->wlong_cap, (size_t)nb * count * sizeof(T)));
     T* slabs = (T*)c->wlong;
     if (nfull > 0)
         BLAS_CHECK(c, wgemm_sb(c->blas, rocblas_operation_none, rocblas_operation_none, m, n, (int)kc, A, lda, (rocblas_stride)(kc * lda), B, ldb, (rocblas_stride)kc,
@@ -598,10 +581,10 @@ int wide_grad_panel(cglb_ctx* c, const void* G, int64_t ldg, const void* cvec, c
     CGLB_TRY(ensure_ones(c));
     const int64_t ld = (ncols + 7) & ~(int64_t)7;
     CGLB_DISPATCH_T(c->dtype, CGLB_DISPATCH_KIND(c->kind, {
-        CGLB_TRY(wensure(c, &c->wpanel, &c->wpanel_cap, (size_t)M * ld * sizeof(T)));
+        CGLB_TRY(c->mem.reserve(c, &c->wpanel, &c->wpanel_cap, (size_t)M * ld * sizeof(T)));
         T* S = (T*)c->wpanel;
         const int nbx = (int)((ncols + 255) / 256);
-        CGLB_TRY(wensure(c, &c->wS1, &c->wS1_cap, std::max((size_t)2 * c->N * D * sizeof(T), (size_t)M * D * sizeof(T) + (size_t)M * nbx * sizeof(double) + 64)));
+        CGLB_TRY(c->mem.reserve(c, &c->wS1, &c->wS1_cap, std::max((size_t)2 * c->N * D * sizeof(T), (size_t)M * D * sizeof(T) + (size_t)M * nbx * sizeof(double) + 64)));
         T* Tm = (T*)c->wS1;                                                     // [M][D]
         double* fpart = (double*)((char*)c->wS1 + (((size_t)M * D * sizeof(T) + 63) & ~(size_t)63));
         T *R = (T*)c->wR, *C = (T*)c->wC;
