@@ -965,7 +965,12 @@ int cglb_set_option(cglb_ctx* c, const char* name, int64_t value) {
     if (!strcmp(name, "kff_variant")) c->kff_variant = (int)value;
     else if (!strcmp(name, "kff_jsplit")) c->kff_jsplit = (int)value;
     else if (!strcmp(name, "kff_rows")) c->kff_rows = (int)value;
-    else if (!strcmp(name, "sym_chunk")) c->sym_chunk_opt = value;
+    else if (!strcmp(name, "sym_chunk")) {
+        // the launcher rounds the value up to the 16-column batch before it clamps it to SYM_CHUNK_MAX: a value next to INT64_MAX would
+        // wrap to a negative chunk there (negative chunk count, negative slab offsets)
+        if (value > ((int64_t)1 << 20)) return cglb_fail(c, CGLB_ERR_BAD_ARG, "sym_chunk must be at most 1048576 (0 or negative: the default rule; values above 1024 clamp to 1024)");
+        c->sym_chunk_opt = value;
+    }
     else if (!strcmp(name, "pcg_lookahead")) c->pcg_lookahead = (int)value;
     else if (!strcmp(name, "sym_order")) c->sym_order = (int)value;
     else if (!strcmp(name, "aat_block")) c->aat_block = (int)value;

@@ -142,15 +142,19 @@ def pad_dim(D: int) -> int:
     return D
 
 
-def rows_per_lane(D: int) -> int:
-    """fp32 instances of the symmetric kernel (kernels_kff_sym.hip: kff_sym_generic)."""
+def rows_per_lane(D: int, dtype: str = "fp32") -> int:
+    """Rows per lane of the symmetric kernel's instances (kernels_kff_sym.hip: kff_sym_generic): fp32 8 / 4 / 2 (the default here), fp64
+    8 / 4 (up to the padded width CGLB_SYM_R4_MAX_DP = 12) / 2 / 1 (every wider row, the mid-width instances of D = 33 ... 96 included)."""
     dp = pad_dim(D)
+    if dtype == "fp64":
+        return 8 if dp <= 4 else (4 if dp <= 12 else (2 if dp <= 16 else 1))
     return 8 if dp <= 4 else (4 if dp <= 16 else 2)
 
 
-def sym_chunk(n: int, D: int, world: int = 1, opt: int = 0) -> int:
-    """Column chunk of the fp32 symmetric mat-vec (kff_sym_generic: halve 1024 until a rank has >= 16k items; option sym_chunk)."""
-    rb = 64 * rows_per_lane(D)
+def sym_chunk(n: int, D: int, world: int = 1, opt: int = 0, dtype: str = "fp32") -> int:
+    """Column chunk of the symmetric mat-vec (kff_sym_generic: halve 1024 until a rank has >= 16k items; option sym_chunk, rounded up
+    to the 16-column batch and clamped to the 1024 columns staged in LDS)."""
+    rb = 64 * rows_per_lane(D, dtype)
     chunk = 1024
     nrb_rank = ((n + rb - 1) // rb) / world
     while chunk > 128 and nrb_rank * (n / chunk) * 0.5 < 16384.0:
@@ -279,8 +283,16 @@ def emulate_matvec(kind, X32, hyp, p32, chunk: int, r0=0, r1=None):
 
 
 # --------------------------------------------------------------------------- planted defects (what a plausible kernel bug does)
-def defect_drop_last_column(case: MatvecCase, p32, r0=0):
-    return case.ref - case.K[:, -1] * p32[-1]
+def defect_drop_last_column(case: MatvecCase, p32, r0=0, col=-1):
+    """Column `col` (default: the last one) missing from every row sum."""
+    return case.ref - case.K[:, col] * p32[col]
+
+
+def defect_drop_pair(case: MatvecCase, p32, i, j, r0=0):
+    """One kernel pair missing: row i (local) loses k_ij p_j."""
+    out = case.ref.copy()
+    out[i] -= case.K[i, j] * p32[j]
+    return out
 
 
 def defect_drop_tail_row(case: MatvecCase, p32, r0=0):

@@ -62,4 +62,12 @@ def test_dispatch_facts():
     assert [em.pad_dim(d) for d in (1, 5, 9, 17, 25, 29, 32, 33)] == [1, 6, 10, 20, 28, 32, 32, 33]
     assert [em.rows_per_lane(d) for d in (4, 5, 16, 17, 32)] == [8, 4, 4, 2, 2]
     assert em.sym_chunk(2999, 8) == 128 and em.sym_chunk(2999, 8, opt=100) == 112 and em.sym_chunk(1_000_000, 16) == 1024
+    # the fp64 instances (optional dtype argument; the defaults above stay fp32): 8 / 4 up to the padded width 12 / 2 / 1
+    assert [em.rows_per_lane(d, "fp64") for d in (3, 4, 5, 8, 12, 13, 16, 17, 20, 32, 50, 96)] == [8, 8, 4, 4, 4, 2, 2, 1, 1, 1, 1, 1]
+    assert [em.rows_per_lane(d, "fp32") for d in (3, 16, 24)] == [8, 4, 2]
+    # fp64, D = 8 (256-row blocks): 128 columns below ~46k rows, 1024 only above ~93k; the thresholds move with the rows per lane
+    assert [em.sym_chunk(n, 8, dtype="fp64") for n in (7000, 45_000, 48_000, 66_000, 92_000, 94_000)] == [128, 128, 256, 512, 512, 1024]
+    assert em.sym_chunk(48_000, 8, dtype="fp64") != em.sym_chunk(48_000, 20, dtype="fp64")
+    assert em.sym_chunk(94_000, 8, world=8, dtype="fp64") == 128
+    assert [em.sym_chunk(3000, 8, opt=o, dtype="fp64") for o in (16, 1000, 1024, 4096)] == [16, 1008, 1024, 1024]
     assert em.quantity("matvec_v2") == "matvec" and em.quantity("cross_n77") == "cross" and em.quantity("f_var") == "f_var"
