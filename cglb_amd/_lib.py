@@ -88,6 +88,14 @@ SIGNATURES = {
     "cglb_get_matrix": (c_int, [c_void_p, c_int, c_void_p]),
     "cglb_time_kernel": (c_int, [c_void_p, c_int, c_int, POINTER(c_double)]),
     "cglb_set_option": (c_int, [c_void_p, c_char_p, c_int64]),
+    "cglb_set_targets": (c_int, [c_void_p, c_void_p, c_int]),
+    "cglb_matmat": (c_int, [c_void_p, c_void_p, c_int, c_void_p]),
+    "cglb_pcg_solve_multi": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_double, c_int, c_int, POINTER(c_int), POINTER(c_double),
+                                     POINTER(c_double)]),
+    "cglb_objective_and_grad_multi": (c_int, [c_void_p, c_void_p, c_int, c_double, c_int, c_int, POINTER(c_double), POINTER(c_double),
+                                              POINTER(c_int), POINTER(c_double)]),
+    "cglb_predict_multi": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
+    "cglb_time_matmat": (c_int, [c_void_p, c_int, c_int, POINTER(c_double)]),
 }
 
 _lib = None

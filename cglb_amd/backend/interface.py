@@ -192,7 +192,7 @@ def _create_model_cglb(model_cfg: CGLBConfig, data: Data):
     extra = {}
     if _STATE["config_semantics"] == "tf":  # the TF twin's create_model hands these to the model (tensorflow/interface.py:244-258)
         extra = dict(max_error=model_cfg.max_error, joint_optimization=model_cfg.joint_optimization, vzero=model_cfg.vzero)
-    model = CGLB((np.asarray(data[0]), np.asarray(data[1]).reshape(-1)), likelihood, kernel, dtype=_STATE["dtype"], **extra)
+    model = CGLB((np.asarray(data[0]), _targets(data[1])), likelihood, kernel, dtype=_STATE["dtype"], **extra)
     _broadcast_parameters(model)
     return model
 
@@ -202,7 +202,7 @@ def _create_cglb_variant(cls, model_cfg: CGLBConfig, data: Data):
     extra = {}
     if _STATE["config_semantics"] == "tf":
         extra = dict(max_error=model_cfg.max_error, joint_optimization=model_cfg.joint_optimization, vzero=model_cfg.vzero)
-    return cls((np.asarray(data[0]), np.asarray(data[1]).reshape(-1)), likelihood, kernel, dtype=_STATE["dtype"], **extra)
+    return cls((np.asarray(data[0]), _targets(data[1])), likelihood, kernel, dtype=_STATE["dtype"], **extra)
 
 
 @create_model.register
@@ -224,7 +224,7 @@ def _create_model_sgpr(model_cfg: SGPRConfig, data: Data):
     """SGPR (Titsias) on the same inducing-point initialisation as CGLB.  One rank."""
     _require_one_rank("sgpr")
     likelihood, kernel = _likelihood_and_kernel_for_sgpr(model_cfg, data)
-    return SGPR((np.asarray(data[0]), np.asarray(data[1]).reshape(-1)), likelihood, kernel, dtype=_STATE["dtype"])
+    return SGPR((np.asarray(data[0]), _targets(data[1])), likelihood, kernel, dtype=_STATE["dtype"])
 
 
 @create_model.register
@@ -232,7 +232,18 @@ def _create_model_sgprn2m(model_cfg: SGPRN2MConfig, data: Data):
     """SGPR with the N^2M log-det bound.  One rank, fp64."""
     _require_one_rank("sgprn2m")
     likelihood, kernel = _likelihood_and_kernel_for_sgpr(model_cfg, data)
-    return SGPRN2M((np.asarray(data[0]), np.asarray(data[1]).reshape(-1)), likelihood, kernel, dtype=_STATE["dtype"])
+    return SGPRN2M((np.asarray(data[0]), _targets(data[1])), likelihood, kernel, dtype=_STATE["dtype"])
+
+
+def _targets(y) -> np.ndarray:
+    """Targets as the models take them: [N, P] stays 2-D for P > 1, a single column (either shape) is the flat vector it always was."""
+    y = np.asarray(y)
+    return y if (y.ndim == 2 and y.shape[1] > 1) else y.reshape(-1)
+
+
+def _targets_2d(y) -> np.ndarray:
+    y = np.asarray(y)
+    return y.reshape(y.shape[0], -1)
 
 
 def _require_one_rank(name: str):
@@ -442,7 +453,7 @@ def _compute_metrics_cglb(model: CGLB, dataset_bundle):
             return dict(loss=_numpy(loss))
 
     x_full = np.concatenate([np.asarray(train[0]), np.asarray(test[0])], axis=0)
-    y_full = np.concatenate([np.asarray(train[1]).reshape(-1), np.asarray(test[1]).reshape(-1)], axis=0).reshape(-1, 1)
+    y_full = np.concatenate([_targets_2d(train[1]), _targets_2d(test[1])], axis=0)  # [n, P]: rmse / lpd over all outputs
     total = int(x_full.shape[0])
 
     def error_and_logdensity():

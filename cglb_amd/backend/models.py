@@ -133,10 +133,16 @@ class GPR(nn.Module):
         super().__init__()
         x = torch.as_tensor(data[0])
         self.train_inputs = (x.reshape(x.shape[0], -1),)
-        self.train_targets = torch.as_tensor(data[1]).reshape(-1)
+        y = torch.as_tensor(data[1])
+        # [N, P] targets stay 2-D for P > 1 (one kernel, mean and noise shared by the outputs); a single column is the flat vector
+        self.train_targets = y if (y.dim() == 2 and y.shape[0] == x.shape[0] and y.shape[1] > 1) else y.reshape(-1)
         self.likelihood = likelihood
         self.mean_module = ConstantMean()
         self.covar_module = kernel
+
+    @property
+    def num_outputs(self) -> int:
+        return int(self.train_targets.shape[1]) if self.train_targets.dim() == 2 else 1
 
 
 def _variant_context(model, data_x, data_y, num_inducing: int, kind: str, dtype, device, context):
@@ -168,6 +174,8 @@ class SGPR(GPR):
                  device: Optional[torch.device] = None, context=None):
         super().__init__(data, likelihood, kernel)
         self.dtype = dtype
+        if self.num_outputs > 1:
+            raise NotImplementedError(f"{type(self).__name__} is not available for more than one target column (only CGLB takes [N, P] targets)")
         kind = kernel.base_kernel.base_kernel.kind
         self.hip = _variant_context(self, self.train_inputs[0], self.train_targets, kernel.inducing_points.shape[0], kind, dtype, device, context)
         self._zero_v = torch.zeros(self.hip.N, dtype=dtype, device=self.hip.device)  # the library treats v as 0 (quad_term 1); shape check only
@@ -185,10 +193,12 @@ class SGPR(GPR):
         x_in, y_in = x, y
         # everything on the host in fp64, whatever device the model or the caller keep their tensors on
         x = torch.as_tensor(x).detach().cpu().to(torch.float64)
-        y = torch.as_tensor(y).detach().cpu().to(torch.float64).reshape(-1)
+        y = torch.as_tensor(y).detach().cpu().to(torch.float64)
         x = x.reshape(x.shape[0], -1) if x.ndim else x.reshape(1, 1)
         tx = self.train_inputs[0].detach().cpu().to(torch.float64)
-        ty = self.train_targets.detach().cpu().to(torch.float64).reshape(-1)
+        ty = self.train_targets.detach().cpu().to(torch.float64)
+        if ty.dim() == 1:   # one output: [N] and [N, 1] are the same targets
+            y = y.reshape(-1)
         if x.shape != tx.shape or y.shape != ty.shape:
             raise ValueError(f"LowerBoundCG was given data of shape {tuple(x.shape)}/{tuple(y.shape)} but the model holds the training set "
                              f"{tuple(tx.shape)}/{tuple(ty.shape)}: the bound is only defined on the model's own training data")
@@ -237,6 +247,16 @@ class CGLB(SGPR):
         self.dtype = dtype
         self.max_error, self.joint_optimization, self.vzero = max_error, bool(joint_optimization), bool(vzero)
         kind = kernel.base_kernel.base_kernel.kind
+        if self.num_outputs > 1:
+            name = type(self).__name__
+            if self.LOGDET_BOUND != 0:
+                raise NotImplementedError(f"{name} is not available for more than one target column (only CGLB takes [N, P] targets)")
+            if self.joint_optimization and not self.vzero:
+                raise NotImplementedError("joint optimisation of v (the TF twin's opt-in) is not available for more than one target column")
+            import torch.distributed as dist
+            if getattr(context, "world", 1) > 1 or (context is None and dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1):
+                raise NotImplementedError(f"{name} with more than one target column is not available on more than one rank; "
+                                          f"run it as a single process")
         if self.LOGDET_BOUND != 0:   # a log-det ablation: one rank, the option set on the context
             context = _variant_context(self, self.train_inputs[0], self.train_targets, kernel.inducing_points.shape[0], kind, dtype, device, context)
         elif context is None:
@@ -250,7 +270,7 @@ class CGLB(SGPR):
         self._hyper_token = None
 
     def _build_v_vec(self) -> Tensor:  # models.py:59-68
-        return torch.zeros((self.hip.N, 1), dtype=self.dtype, device=self.hip.device, requires_grad=False)
+        return torch.zeros((self.hip.N, self.num_outputs), dtype=self.dtype, device=self.hip.device, requires_grad=False)
 
     @property
     def v_vec(self) -> Tensor:
@@ -307,11 +327,14 @@ class _BoundFunction(torch.autograd.Function):
         hip = model.hip
         hip.set_hypers(ls.detach().cpu().numpy(), float(var), float(noise), float(mean), Z.detach().cpu(), get_cholesky_jitter())
         need_grad = any(ctx.needs_input_grad[1:])
-        v = model.v_vec.detach().reshape(-1)
+        multi = getattr(model, "num_outputs", 1) > 1
+        v = model.v_vec.detach() if multi else model.v_vec.detach().reshape(-1)   # [N, P] as it is; one output: the flat vector
         run_cg = not (owner._use_cache and owner.cached_v_vec)          # models.py:263
         if model.joint_optimization or model.vzero:                     # tensorflow/models.py:161-164: v0 is used as it stands
             run_cg = False
         cg = owner.cg_opt
+        if run_cg and multi and type(cg) is not ConjugateGradient:
+            raise NotImplementedError("a plug-in solver is not available for more than one target column (the batched PCG runs in the library)")
         if run_cg and type(cg) is not ConjugateGradient:
             # foreign plug-in solver through the seam (models.py:266-271): cg_opt(A, b, v, precond)
             hip.setup()
@@ -423,10 +446,19 @@ class PredictCG(LowerBoundCG):
                 model.push_hypers(get_cholesky_jitter())
                 hip.setup()                                                            # models.py:327
                 ls, var, noise, mean, Z = model.hyper_tensors()
-                err = (hip.y - float(mean)).reshape(-1, 1)
-                new_v, _stats = self.cg_opt(KernelOperator(hip), err, self.v_vec, NystromPreconditioner(hip))  # :329
+                if getattr(model, "num_outputs", 1) > 1:   # P columns: the batched PCG of the library, one shared K_ff product per step
+                    cg = self.cg_opt
+                    if type(cg) is not ConjugateGradient:
+                        raise NotImplementedError("a plug-in solver is not available for more than one target column")
+                    new_v, _steps, _half, _cols = hip.pcg_multi(hip.y - float(mean), self.v_vec, cg.max_error, cg.max_cg_iter, cg.restart_cg_iter)
+                else:
+                    err = (hip.y - float(mean)).reshape(-1, 1)
+                    new_v, _stats = self.cg_opt(KernelOperator(hip), err, self.v_vec, NystromPreconditioner(hip))  # :329
                 self.v_vec.data.copy_(new_v.reshape(self.v_vec.shape))
                 self.cached = True
+            if getattr(model, "num_outputs", 1) > 1:
+                f_mean, f_var = hip.predict_multi(self.v_vec, xnew)                    # f_mean [n_new, P]; one variance for all outputs
+                return f_mean, f_var.reshape(-1, 1).repeat(1, f_mean.shape[1])         # tiled over the outputs (tensorflow/models.py:245)
             f_mean, f_var = hip.predict(self.v_vec.reshape(-1), xnew)                  # models.py:334-352
         return f_mean.reshape(-1, 1), f_var.reshape(-1, 1)
 

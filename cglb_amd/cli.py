@@ -9,7 +9,7 @@ that exercise the hot path:
 
 Same option letters as cli.py:60-65, :141-152, :207-216; writes model.json / results.json / logs.json with the reference's keys
 (cli.py:100-109, pytorch/interface.py:546-551).  Datasets: the reference downloads UCI sets through robustgp_experiments
-(datasets.py:47-76; no network here), so DATASET is either `synthetic-N-D` (e.g. synthetic-2000-3, the generator of
+(datasets.py:47-76; no network here), so DATASET is either `synthetic-N-D[-P]` (e.g. synthetic-2000-3, or synthetic-400-3-2 for two target columns; the generator of
 cglb_amd/data.py) / `snelson-like` (N=200, D=1 stand-in for snelson1d), or a path to an .npz with arrays X, y; all are
 z-normalised and split 67/33 with the seed, as datasets.py:35-39,:60-70 does.
 
@@ -57,8 +57,11 @@ def _norm(x):  # datasets.py:35-39
 
 def get_dataset(name: str, seed: int = 0) -> DatasetBundle:
     if name.startswith("synthetic-"):
-        _, n, d = name.split("-")
-        X, y, _ = synthetic_problem(int(n), int(d), 1, seed=1234)
+        parts = name.split("-")  # synthetic-N-D or synthetic-N-D-P (P target columns)
+        if len(parts) not in (3, 4):
+            raise click.BadParameter(f"dataset {name!r}: expected synthetic-N-D or synthetic-N-D-P")
+        n, d, p = int(parts[1]), int(parts[2]), (int(parts[3]) if len(parts) == 4 else 1)
+        X, y, _ = synthetic_problem(n, d, 1, seed=1234, P=p)
     elif name in ("snelson-like", "snelson1d"):
         rng = np.random.default_rng(1234)
         X = np.sort(rng.uniform(0.0, 6.0, size=(200, 1)), axis=0)
@@ -68,7 +71,8 @@ def get_dataset(name: str, seed: int = 0) -> DatasetBundle:
         X, y = np.asarray(data["X"], dtype=np.float64), np.asarray(data["y"], dtype=np.float64).reshape(-1)
     else:
         raise click.BadParameter(f"unknown dataset {name!r} (no network: use synthetic-N-D, snelson-like or an .npz path)")
-    X, y = _norm(X.reshape(len(X), -1)), _norm(y.reshape(-1, 1)).reshape(-1)
+    y = _norm(y.reshape(len(y), -1))                     # [N, P] stays 2-D for P > 1, one column is the flat vector
+    X, y = _norm(X.reshape(len(X), -1)), (y if y.shape[1] > 1 else y.reshape(-1))
     perm = np.random.default_rng(seed).permutation(len(X))
     n_train = int(len(X) * 0.67)
     tr, te = perm[:n_train], perm[n_train:]

@@ -788,6 +788,7 @@ int comm_alloc(cglb_ctx* c, int world, int rank) {
     if (world < 1 || rank < 0 || rank >= world) return cglb_fail(c, CGLB_ERR_BAD_ARG, "bad world/rank");
     if (c->logdet_bound != 0 || c->quad_term != 0)
         return cglb_fail(c, CGLB_ERR_BAD_ARG, "logdet_bound / quad_term other than 0 are not available on more than one rank");
+    if (c->p > 1) return cglb_fail(c, CGLB_ERR_BAD_ARG, "more than one target column is not available on more than one rank");
     const int64_t per = (c->N + world - 1) / world;
     const int64_t r0 = std::min<int64_t>((int64_t)rank * per, c->N), r1 = std::min<int64_t>((int64_t)(rank + 1) * per, c->N);
     if (c->r0 != r0 || c->r1 != r1)
@@ -865,12 +866,124 @@ __global__ __launch_bounds__(256) void unpack_pairs_kernel(const T* __restrict__
     b[i] = gat[g * 2 * pern + pern + k];
 }
 
+// ================================ multi-output targets: P columns, one shared K_ff product ================================
+// Column b of every [P][N] array is a contiguous vector; the batched PCG advances P independent recurrences (conjugate_gradient.py:41-86
+// per column, each with its own gamma_b and beta_b) in lockstep over one mat-mat product per iteration (kernels_kff_multi.hip).
+struct multi_work {
+    char *r, *z, *p, *Ap, *Kv, *b;      // [s][N]
+    double *rz, *nrz, *pap, *tmp;       // [s] device scalars
+};
+
+int multi_reserve(cglb_ctx* c, int s, multi_work* w) {
+    const size_t vec = (size_t)s * c->N * c->esz;
+    CGLB_TRY(c->mem.reserve(c, &c->mw, &c->mw_cap, 6 * vec));
+    CGLB_TRY(c->mem.reserve(c, &c->mscal, &c->mscal_cap, (size_t)4 * s * sizeof(double)));
+    if (c->mhost_cap < s) {
+        if (c->mhost) (void)hipHostFree(c->mhost);
+        c->mhost = nullptr; c->mhost_cap = 0;
+        HIP_CHECK(c, hipHostMalloc((void**)&c->mhost, (size_t)s * sizeof(double), hipHostMallocDefault));
+        c->mhost_cap = s;
+    }
+    char* base = (char*)c->mw;
+    w->r = base; w->z = base + vec; w->p = base + 2 * vec; w->Ap = base + 3 * vec; w->Kv = base + 4 * vec; w->b = base + 5 * vec;
+    w->rz = c->mscal; w->nrz = c->mscal + s; w->pap = c->mscal + 2 * s; w->tmp = c->mscal + 3 * s;
+    return CGLB_OK;
+}
+
+// more than one column needs one shard covering all rows on one rank with the default bound
+int require_multi_ok(cglb_ctx* c) {
+    CGLB_TRY(require_single(c));
+    if (c->par_world > 1 || c->comm) return cglb_fail(c, CGLB_ERR_BAD_ARG, "more than one target column is not available on more than one rank");
+    if (c->logdet_bound != 0 || c->quad_term != 0) return cglb_fail(c, CGLB_ERR_BAD_ARG, "more than one target column needs logdet_bound 0 and quad_term 0");
+    return CGLB_OK;
+}
+
+// z_b = P r_b column by column through the single launches (a batched panel pass is a follow-up), rz_new[b] = r_b . z_b, then the
+// direction update of all columns in one launch
+int multi_direction(cglb_ctx* c, const multi_work& w, int s, double* rz_new, const double* rz_old, int restart) {
+    const size_t stride = (size_t)c->N * c->esz;
+    for (int b = 0; b < s; ++b) CGLB_TRY(precond_single(c, w.r + b * stride, w.z + b * stride, rz_new + b));
+    return launch_update_p_multi(c, w.p, w.z, rz_new, rz_old, restart, c->N, s);
+}
+
+// sum of s device scalars read back in column order; the values stay in c->mhost
+int multi_read_sum(cglb_ctx* c, const double* dev, int s, double* sum) {
+    HIP_CHECK(c, hipMemcpyAsync(c->mhost, dev, sizeof(double) * s, hipMemcpyDeviceToHost, c->stream));
+    HIP_CHECK(c, hipStreamSynchronize(c->stream));
+    double t = 0.0;
+    for (int b = 0; b < s; ++b) t += c->mhost[b];
+    *sum = t;
+    return CGLB_OK;
+}
+
+// One stop test before every iteration on 1/2 sum_b r_b^T P r_b (the gap upper - lower of the summed bound); the restart rule applies to
+// all columns at once; look-ahead as in pcg_solve, on the summed statistic.
+int pcg_solve_multi(cglb_ctx* c, const multi_work& w, const void* B, void* V, int s, double max_error, int max_iter, int restart_iter, int* steps,
+                    double* half_rz_total, double* half_rz_cols) {
+    const int64_t n = c->N, sn = (int64_t)s * c->N;
+    c->pwh_src = nullptr;
+    double vnorm = 0.0;
+    CGLB_TRY(launch_dot(c, V, V, sn, c->scal + S_TMP));
+    CGLB_TRY(read_scalars(c, c->scal + S_TMP, &vnorm, 1));
+    if (vnorm == 0.0) {
+        HIP_CHECK(c, hipMemcpyAsync(w.r, B, (size_t)sn * c->esz, hipMemcpyDeviceToDevice, c->stream));
+    } else {
+        CGLB_TRY(launch_kff_matmat(c, V, s, w.Kv));
+        CGLB_TRY(launch_residual(c, w.r, B, w.Kv, sn));
+    }
+    double *s_rz = w.rz, *s_nrz = w.nrz;
+    CGLB_TRY(multi_direction(c, w, s, s_rz, s_rz, 1));
+    double rz = 0.0;
+    CGLB_TRY(multi_read_sum(c, s_rz, s, &rz));
+    int i = 0;
+    bool ahead = false;
+    while (0.5 * rz > max_error && i < max_iter) {
+        if (!ahead) CGLB_TRY(launch_kff_matmat(c, w.p, s, w.Ap));
+        CGLB_TRY(launch_dot_multi(c, w.p, w.Ap, n, s, w.pap));
+        const int restart = (restart_iter > 0) && (i % restart_iter == restart_iter - 1);
+        CGLB_TRY(launch_update_v_r_multi(c, V, w.r, w.p, w.Ap, s_rz, w.pap, !restart, n, s));
+        if (restart) {
+            CGLB_TRY(launch_kff_matmat(c, V, s, w.Kv));
+            CGLB_TRY(launch_residual(c, w.r, B, w.Kv, sn));
+        }
+        CGLB_TRY(multi_direction(c, w, s, s_nrz, s_rz, restart));
+        std::swap(s_rz, s_nrz);
+        HIP_CHECK(c, hipMemcpyAsync(c->mhost, s_rz, sizeof(double) * s, hipMemcpyDeviceToHost, c->stream));
+        HIP_CHECK(c, hipEventRecord(c->scal_event, c->stream));
+        ahead = c->pcg_lookahead && (i + 1 < max_iter) && (0.5 * rz > lookahead_factor(c) * max_error);
+        if (ahead) CGLB_TRY(launch_kff_matmat(c, w.p, s, w.Ap));
+        HIP_CHECK(c, hipEventSynchronize(c->scal_event));
+        rz = 0.0;
+        for (int b = 0; b < s; ++b) rz += c->mhost[b];
+        ++i;
+    }
+    if (steps) *steps = i;
+    if (half_rz_total) *half_rz_total = 0.5 * rz;
+    if (half_rz_cols)
+        for (int b = 0; b < s; ++b) half_rz_cols[b] = 0.5 * c->mhost[b];
+    return CGLB_OK;
+}
+
+// the single-column phases read the targets through c->y: point it at column b for the duration of a scope
+struct target_column_guard {
+    cglb_ctx* c;
+    void* saved;
+    explicit target_column_guard(cglb_ctx* cc) : c(cc), saved(cc->y) {}
+    void select(int b) { c->y = (char*)c->Ym + (size_t)b * c->N * c->esz; }
+    ~target_column_guard() { c->y = saved; }
+};
+
+__global__ void grad_accumulate_kernel(double* __restrict__ sum, const double* __restrict__ g, int64_t n, int first) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) sum[i] = first ? g[i] : sum[i] + g[i];
+}
+
 }  // namespace
 
 // =================================================== C ABI ====================================================
 extern "C" {
 
-int cglb_version(void) { return 100; }
+int cglb_version(void) { return 101; }
 
 const char* cglb_last_error(const cglb_ctx* ctx) { return ctx ? ctx->err.c_str() : g_create_error.c_str(); }
 
@@ -954,6 +1067,7 @@ int cglb_ctx_destroy(cglb_ctx* c) {
     for (hipEvent_t ev : c->k1_events) (void)hipEventDestroy(ev);
     for (hipEvent_t ev : c->eval_events) (void)hipEventDestroy(ev);
     if (c->host_scal) (void)hipHostFree(c->host_scal);
+    if (c->mhost) (void)hipHostFree(c->mhost);
     if (c->scal_event) (void)hipEventDestroy(c->scal_event);
     if (c->blas) (void)rocblas_destroy_handle(c->blas);
     delete c;
@@ -1012,6 +1126,8 @@ int cglb_set_option(cglb_ctx* c, const char* name, int64_t value) {
             return cglb_fail(c, CGLB_ERR_BAD_ARG, ld ? "logdet_bound must be 0 (Jensen), 1 (NM^2) or 2 (N^2M)" : "quad_term must be 0 (CG) or 1 (exact)");
         if (value != 0 && (c->par_world > 1 || c->comm))
             return cglb_fail(c, CGLB_ERR_BAD_ARG, std::string(name) + " other than 0 is not available on more than one rank");
+        if (value != 0 && c->p > 1)
+            return cglb_fail(c, CGLB_ERR_BAD_ARG, std::string(name) + " other than 0 is not available with more than one target column");
         if (ld && value == 2) {
             if (c->dtype != CGLB_F64)  // tau is the difference of two traces of size N (f + s): fp32 cannot resolve it
                 return cglb_fail(c, CGLB_ERR_BAD_ARG, "logdet_bound 2 (N^2M) needs an fp64 context: tau = tr K~ - tr(C K~ C^T) cancels in fp32");
@@ -1053,6 +1169,7 @@ int cglb_set_data(cglb_ctx* c, const void* X, const void* y) {
         c->xradius2 = std::fmax(c->xradius2, r2);
     }
     c->have_data = true;
+    c->p = 1;  // one target column again (cglb_set_targets)
     c->have_local = c->have_terms = false;
     return CGLB_OK;
 }
@@ -1255,6 +1372,7 @@ int cglb_set_parallel(cglb_ctx* c, int world, int rank) {
     if (!c || world < 1 || rank < 0 || rank >= world) return c ? cglb_fail(c, CGLB_ERR_BAD_ARG, "bad world/rank") : CGLB_ERR_BAD_ARG;
     if (world > 1 && (c->logdet_bound != 0 || c->quad_term != 0))
         return cglb_fail(c, CGLB_ERR_BAD_ARG, "logdet_bound / quad_term other than 0 are not available on more than one rank");
+    if (world > 1 && c->p > 1) return cglb_fail(c, CGLB_ERR_BAD_ARG, "more than one target column is not available on more than one rank");
     c->par_world = world;
     c->par_rank = rank;
     return CGLB_OK;
@@ -1738,6 +1856,154 @@ int cglb_time_kernel(cglb_ctx* c, int which, int reps, double* ms_avg) {
         return cglb_fail(c, CGLB_ERR_BAD_ARG, "unknown kernel id");
     };
     rc = once();  // warm-up (also sizes the work buffers)
+    if (rc == CGLB_OK) {
+        (void)hipEventRecord(e0, c->stream);
+        for (int i = 0; i < reps && rc == CGLB_OK; ++i) rc = once();
+        (void)hipEventRecord(e1, c->stream);
+        (void)hipEventSynchronize(e1);
+        float ms = 0;
+        (void)hipEventElapsedTime(&ms, e0, e1);
+        *ms_avg = (double)ms / reps;
+    }
+    (void)hipEventDestroy(e0);
+    (void)hipEventDestroy(e1);
+    return rc;
+}
+
+// ---- multi-output targets (include/cglb_hip.h) ------------------------------------------------------------------------
+int cglb_set_targets(cglb_ctx* c, const void* Y, int p) {
+    if (c) c->obj_valid = false;
+    if (!c || !Y || p < 1) return c ? cglb_fail(c, CGLB_ERR_BAD_ARG, "bad argument") : CGLB_ERR_BAD_ARG;
+    if (!c->have_data) return cglb_fail(c, CGLB_ERR_STATE, "set_data must precede set_targets");
+    if (c->par_world > 1 || c->comm) return cglb_fail(c, CGLB_ERR_BAD_ARG, "set_targets is not available on more than one rank");
+    if (c->logdet_bound != 0 || c->quad_term != 0) return cglb_fail(c, CGLB_ERR_BAD_ARG, "set_targets needs logdet_bound 0 and quad_term 0");
+    if (p > 1 && (c->r0 != 0 || c->r1 != c->N)) return cglb_fail(c, CGLB_ERR_BAD_ARG, "more than one target column needs a single shard covering all rows");
+    HIP_CHECK(c, hipSetDevice(c->device));
+    const size_t col = (size_t)c->N * c->esz;
+    if (p > 1) {
+        CGLB_TRY(c->mem.reserve(c, &c->Ym, &c->Ym_cap, (size_t)p * col));
+        HIP_CHECK(c, hipMemcpyAsync(c->Ym, Y, (size_t)p * col, hipMemcpyDefault, c->stream));
+    }
+    HIP_CHECK(c, hipMemcpyAsync(c->y, Y, col, hipMemcpyDefault, c->stream));  // column 0: what the single-column entry points see
+    HIP_CHECK(c, hipStreamSynchronize(c->stream));                             // the caller owns Y again
+    c->p = p;
+    return CGLB_OK;
+}
+
+int cglb_matmat(cglb_ctx* c, const void* V, int s, void* Out) {
+    if (!c || !V || !Out || s < 1) return c ? cglb_fail(c, CGLB_ERR_BAD_ARG, "bad argument") : CGLB_ERR_BAD_ARG;
+    if (!c->have_hypers) return cglb_fail(c, CGLB_ERR_STATE, "set_hypers must precede matmat");
+    HIP_CHECK(c, hipSetDevice(c->device));
+    if (s == 1) return launch_kff_matvec(c, V, Out, nullptr);
+    return launch_kff_matmat(c, V, s, Out);
+}
+
+int cglb_pcg_solve_multi(cglb_ctx* c, const void* B, void* V_inout, int s, double max_error, int max_cg_iter, int restart_cg_iter, int* steps,
+                         double* half_rz_total, double* half_rz_cols) {
+    if (c) c->obj_valid = false;
+    if (!c || !B || !V_inout || s < 1) return c ? cglb_fail(c, CGLB_ERR_BAD_ARG, "bad argument") : CGLB_ERR_BAD_ARG;
+    if (s == 1) {
+        double h = 0.0;
+        CGLB_TRY(cglb_pcg_solve(c, B, V_inout, max_error, max_cg_iter, restart_cg_iter, steps, &h));
+        if (half_rz_total) *half_rz_total = h;
+        if (half_rz_cols) half_rz_cols[0] = h;
+        return CGLB_OK;
+    }
+    CGLB_TRY(require_multi_ok(c));
+    CGLB_TRY(require_terms(c));
+    HIP_CHECK(c, hipSetDevice(c->device));
+    multi_work w;
+    CGLB_TRY(multi_reserve(c, s, &w));
+    return pcg_solve_multi(c, w, B, V_inout, s, max_error, max_cg_iter, restart_cg_iter, steps, half_rz_total, half_rz_cols);
+}
+
+int cglb_objective_and_grad_multi(cglb_ctx* c, void* V_inout, int run_cg, double max_error, int max_cg_iter, int restart_cg_iter, double* out4,
+                                  double* grad, int* steps, double* half_rz) {
+    if (!c || !V_inout || !out4) return c ? cglb_fail(c, CGLB_ERR_BAD_ARG, "NULL argument") : CGLB_ERR_BAD_ARG;
+    if (c->p == 1) return cglb_objective_and_grad(c, V_inout, run_cg, max_error, max_cg_iter, restart_cg_iter, out4, grad, steps, half_rz);
+    c->obj_valid = false;
+    CGLB_TRY(require_multi_ok(c));
+    const int P = c->p;
+    const int64_t pn = (int64_t)P * c->N;
+    const size_t col = (size_t)c->N * c->esz, glen = (size_t)CGLB_GRAD_LEN(c->D, c->M);
+    CGLB_TRY(cglb_setup(c));                                                        // models.py:155, shared by the columns
+    multi_work w;
+    CGLB_TRY(multi_reserve(c, P, &w));
+    if (steps) *steps = 0;
+    if (half_rz) *half_rz = std::nan("");
+    CGLB_TRY(launch_sub_scalar(c, w.b, c->Ym, c->mean, pn));                        // e_b = y_b - mean (one shared mean)
+    if (run_cg) CGLB_TRY(pcg_solve_multi(c, w, w.b, V_inout, P, max_error, max_cg_iter, restart_cg_iter, steps, half_rz, nullptr));
+    // K v for all columns: one shared-kernel product, or e - r from the residuals the recurrences carry (option "final_matvec", per column)
+    if (!run_cg || c->final_matvec) CGLB_TRY(launch_kff_matmat(c, V_inout, P, w.Kv));
+    else CGLB_TRY(launch_residual(c, w.Kv, w.b, w.r, pn));
+    // the rest column by column through the single-output phases (a fused multi-column gradient pass is a follow-up); every column's
+    // bound carries one log-det term and one constant, so the sums are the P-fold terms of the multi-output bound
+    if (grad) CGLB_TRY(c->mem.alloc(c, &c->mgrad, glen * sizeof(double)));
+    double* sc = c->scal + S_SC;
+    for (int k = 0; k < 4; ++k) out4[k] = 0.0;
+    target_column_guard yb(c);
+    for (int b = 0; b < P; ++b) {
+        yb.select(b);
+        char* vb = (char*)V_inout + b * col;
+        CGLB_TRY(obj_phase1_kv(c, w.Kv + b * col, c->w_u));
+        CGLB_TRY(obj_phase2(c, vb, c->w_u, sc, c->w_u));
+        if (grad) {
+            CGLB_DISPATCH_T(c->dtype, CGLB_TRY(obj_phase3_impl<T>(c, vb, sc, c->w_u, c->gradbuf)));
+            hipLaunchKernelGGL(grad_accumulate_kernel, dim3(grid1d_full((int64_t)glen)), dim3(256), 0, c->stream, c->mgrad, (const double*)c->gradbuf,
+                               (int64_t)glen, b == 0 ? 1 : 0);
+            CGLB_LAUNCH_CHECK(c);
+        }
+        double o4[4];
+        CGLB_TRY(obj_finish(c, sc, o4));
+        for (int k = 0; k < 4; ++k) out4[k] += o4[k];
+    }
+    if (grad) {
+        HIP_CHECK(c, hipMemcpyAsync(grad, c->mgrad, glen * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        HIP_CHECK(c, hipStreamSynchronize(c->stream));
+    }
+    return CGLB_OK;
+}
+
+int cglb_predict_multi(cglb_ctx* c, const void* V, const void* xnew, int64_t n_new, void* f_mean, void* f_var) {
+    if (c) c->obj_valid = false;
+    if (!c || !V || !xnew || !f_mean || !f_var || n_new < 0) return c ? cglb_fail(c, CGLB_ERR_BAD_ARG, "bad argument") : CGLB_ERR_BAD_ARG;
+    if (c->p == 1) return cglb_predict(c, V, xnew, n_new, f_mean, f_var);
+    CGLB_TRY(require_multi_ok(c));
+    CGLB_TRY(require_terms(c));
+    if (n_new == 0) return CGLB_OK;
+    HIP_CHECK(c, hipSetDevice(c->device));
+    const int P = c->p;
+    const size_t col = (size_t)c->N * c->esz;
+    multi_work w;
+    CGLB_TRY(multi_reserve(c, P, &w));
+    CGLB_TRY(launch_kff_matmat(c, V, P, w.Kv));                                    // cov @ v for every column (models.py:335)
+    target_column_guard yb(c);
+    for (int b = 0; b < P; ++b) {  // the variance does not depend on the column: every pass writes the same values
+        yb.select(b);
+        CGLB_TRY(predict_u_local(c, w.Kv + b * col, c->w_u));
+        CGLB_TRY(predict_rows(c, (const char*)V + b * col, c->w_u, xnew, n_new, (char*)f_mean + (size_t)b * n_new * c->esz, f_var));
+    }
+    return CGLB_OK;
+}
+
+int cglb_time_matmat(cglb_ctx* c, int s, int reps, double* ms_avg) {
+    if (c) c->obj_valid = false;
+    if (!c || !ms_avg || reps <= 0 || s < 1) return c ? cglb_fail(c, CGLB_ERR_BAD_ARG, "bad argument") : CGLB_ERR_BAD_ARG;
+    if (!c->have_hypers) return cglb_fail(c, CGLB_ERR_STATE, "set_hypers must precede timing");
+    CGLB_TRY(require_single(c));
+    HIP_CHECK(c, hipSetDevice(c->device));
+    multi_work w;
+    CGLB_TRY(multi_reserve(c, s, &w));
+    // operands: s copies of y (values do not change the instruction stream)
+    for (int b = 0; b < s; ++b) HIP_CHECK(c, hipMemcpyAsync(w.p + (size_t)b * c->N * c->esz, c->y, (size_t)c->N * c->esz, hipMemcpyDeviceToDevice, c->stream));
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    HIP_CHECK(c, hipEventCreate(&e0));
+    {
+        const hipError_t e = hipEventCreate(&e1);
+        if (e != hipSuccess) { (void)hipEventDestroy(e0); return cglb_fail(c, CGLB_ERR_HIP, std::string("hipEventCreate: ") + hipGetErrorString(e)); }
+    }
+    auto once = [&]() -> int { return s == 1 ? launch_kff_matvec(c, w.p, w.Ap, nullptr) : launch_kff_matmat(c, w.p, s, w.Ap); };
+    int rc = once();  // warm-up (also sizes the slabs)
     if (rc == CGLB_OK) {
         (void)hipEventRecord(e0, c->stream);
         for (int i = 0; i < reps && rc == CGLB_OK; ++i) rc = once();

@@ -174,6 +174,24 @@ struct cglb_ctx {
     int logdet_bound = 0;  // 0 Jensen (cglb), 1 NM^2 (cglbnm2, sgpr), 2 N^2M (cglbn2m, sgprn2m; fp64, stored panel, one shard)
     int quad_term = 0;     // 0 CG (v, PCG), 1 exact Woodbury quadratic term at v = 0 (sgpr, sgprn2m): no N^2 work
     void* w_zero = nullptr;  // [N] zeros: the v of the exact quadratic term (allocated on first use)
+    // multi-output targets (cglb_set_targets) and the shared-kernel product K_ff V (kernels_kff_multi.hip); all allocated on first use
+    int p = 1;               // number of target columns; column 0 is always mirrored in y, so every single-column entry point sees it
+    void* Ym = nullptr;      // [p][N] targets, column b contiguous (p > 1 only)
+    size_t Ym_cap = 0;
+    void* mw = nullptr;      // [6][s][N] work vectors of the batched PCG / evaluation: r, z, p, Ap, Kv, b
+    size_t mw_cap = 0;
+    double* mscal = nullptr; // [4][s] device scalars per column: rz, new rz, p.Ap, scratch
+    size_t mscal_cap = 0;
+    double* mhost = nullptr; // pinned host mirror of one row of mscal (asynchronous read of the stop statistics)
+    int mhost_cap = 0;
+    double* mgrad = nullptr; // [GRAD_LEN] device sum of the per-column gradients
+    void* mm_items = nullptr;   // work list (group of four row blocks, column span) of the multi-column pair kernel
+    int64_t mm_n = -1, mm_span = 0;
+    int mm_rbrows = 0, mm_nwg = 0, mm_order_built = -1;
+    void* mm_part = nullptr;    // its partial-sum slabs
+    size_t mm_part_cap = 0;
+    void* mm_vi = nullptr;      // [N][8] interleaved (and pre-weighted) column-side operand
+    size_t mm_vi_cap = 0;
     // N^2M pass (kernels_n2m.hip), fp64, allocated on first use
     double *n2m_Xn = nullptr, *n2m_Wt = nullptr, *n2m_Ct = nullptr, *n2m_K = nullptr, *n2m_G = nullptr;  // X/l; W = K_ff A^T and C^T (layout of At); tiles
     double *n2m_H = nullptr, *n2m_E = nullptr, *n2m_T = nullptr;  // H = A W, E = B^-1 (H + s AA^T) B^-1, M x M scratch
@@ -288,6 +306,10 @@ int launch_hot_squares(cglb_ctx* c);  // Xhsq = Xh .* Xh after set_hypers
 int k1_profile_collect(cglb_ctx* c);  // resolves the pending event pairs into k1_ms_total / k1_launches
 int launch_kff_sym_cyclic(cglb_ctx* c, const void* p_full, void* out_full_partial);  // this rank's share of the global upper triangle
 int launch_grad_kff_cyclic(cglb_ctx* c, const void* v_full, const void* u_full, double* out_dl);
+// kernels_kff_multi.hip: Out[b] = (K_ff + noise I) V[b], b < s; V [s][N], Out [s][nloc].  One evaluation of every kernel value for up to 8
+// columns where kff_multi_native(c), s single mat-vecs elsewhere.
+bool kff_multi_native(const cglb_ctx* c);
+int launch_kff_matmat(cglb_ctx* c, const void* V, int s, void* Out);
 int launch_kff_plain_range(cglb_ctx* c, const void* p_full, int64_t col0, int64_t col1, void* part, int64_t* nslots);
 int launch_kff_mfma_pairs(cglb_ctx* c, const double* p_full, int64_t* jsplit_out);
 int launch_pairs_rect(cglb_ctx* c, const void* XsRow, const void* xaRow, int64_t nrows, const void* XsCol, const void* xaCol, const void* pcol,
@@ -302,6 +324,10 @@ int launch_update_v_r(cglb_ctx* c, void* v, void* r, const void* p, const void* 
 int launch_residual(cglb_ctx* c, void* r, const void* b, const void* Kv, int64_t n = -1);
 int launch_axpy(cglb_ctx* c, void* y, double alpha, const void* x, int64_t n);
 int launch_update_p(cglb_ctx* c, void* p, const void* z, const double* new_rz, const double* rz, int restart, int64_t n = -1, bool fuse = false);
+// batched forms over s columns of length n ([s][n], one launch each; per-column device scalars [s]); a zero denominator gives a zero factor
+int launch_dot_multi(cglb_ctx* c, const void* a, const void* b, int64_t n, int s, double* out_slots);
+int launch_update_v_r_multi(cglb_ctx* c, void* v, void* r, const void* p, const void* Ap, const double* rz, const double* pAp, int update_r, int64_t n, int s);
+int launch_update_p_multi(cglb_ctx* c, void* p, const void* z, const double* new_rz, const double* rz, int restart, int64_t n, int s);
 int launch_gemv_u(cglb_ctx* c, const void* r_local, void* u_out);               // u = A_loc r
 int launch_tri_apply(cglb_ctx* c, const void* u, void* t_out);                  // t = LB^-T LB^-1 u
 int launch_precond_z(cglb_ctx* c, const void* r_local, const void* t, void* z_local, double* rz_slot, void* rz_slot_T = nullptr);

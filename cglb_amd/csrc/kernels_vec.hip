@@ -150,6 +150,71 @@ int launch_update_p_seg(cglb_ctx* c, void* p, const void* zseg, int64_t n, int64
     return CGLB_OK;
 }
 
+// ---- the same three primitives for s independent recurrences in lockstep (cglb_pcg_solve_multi): blockIdx.y = column ----------------
+// gamma_b = rz_b / pAp_b and beta_b = new_rz_b / rz_b; a zero denominator (a column that has converged exactly, or an all-zero
+// right-hand side) gives a zero factor, so that column stays where it is and stays finite.
+template <typename T>
+__global__ __launch_bounds__(256) void dot_multi_kernel(const T* __restrict__ a, const T* __restrict__ b, int64_t n, double* __restrict__ dotpart) {
+    __shared__ double smem[16];
+    const T* __restrict__ ab = a + (int64_t)blockIdx.y * n;
+    const T* __restrict__ bb = b + (int64_t)blockIdx.y * n;
+    double s = 0.0;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) s += (double)ab[i] * (double)bb[i];
+    s = block_sum(s, smem);
+    if (threadIdx.x == 0) dotpart[(int64_t)blockIdx.y * gridDim.x + blockIdx.x] = s;
+}
+__global__ __launch_bounds__(256) void finalize_sum_multi_kernel(const double* __restrict__ partials, int n, double* __restrict__ out) {
+    __shared__ double smem[16];
+    double s = 0.0;
+    for (int i = threadIdx.x; i < n; i += blockDim.x) s += partials[(int64_t)blockIdx.x * n + i];
+    s = block_sum(s, smem);
+    if (threadIdx.x == 0) out[blockIdx.x] = s;
+}
+int launch_dot_multi(cglb_ctx* c, const void* a, const void* b, int64_t n, int s, double* out_slots) {
+    int grid = vec_grid(n);
+    if (grid > DOTPART_CAP / s) grid = DOTPART_CAP / s;
+    if (grid < 1) return cglb_fail(c, CGLB_ERR_BAD_ARG, "too many columns for the dot partials");
+    CGLB_DISPATCH_T(c->dtype, hipLaunchKernelGGL((dot_multi_kernel<T>), dim3(grid, s), dim3(256), 0, c->stream, (const T*)a, (const T*)b, n, c->dotpart));
+    CGLB_LAUNCH_CHECK(c);
+    hipLaunchKernelGGL(finalize_sum_multi_kernel, dim3(s), dim3(256), 0, c->stream, (const double*)c->dotpart, grid, out_slots);
+    CGLB_LAUNCH_CHECK(c);
+    return CGLB_OK;
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void update_v_r_multi_kernel(T* __restrict__ v, T* __restrict__ r, const T* __restrict__ p, const T* __restrict__ Ap, int64_t n,
+                                                               const double* __restrict__ rz, const double* __restrict__ pAp, int update_r) {
+    const int64_t off = (int64_t)blockIdx.y * n;
+    const double den = pAp[blockIdx.y];
+    const T gamma = den == 0.0 ? T(0) : (T)(rz[blockIdx.y] / den);
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        v[off + i] = tfma<T>(gamma, p[off + i], v[off + i]);
+        if (update_r) r[off + i] = tfma<T>(-gamma, Ap[off + i], r[off + i]);
+    }
+}
+int launch_update_v_r_multi(cglb_ctx* c, void* v, void* r, const void* p, const void* Ap, const double* rz, const double* pAp, int update_r, int64_t n, int s) {
+    CGLB_DISPATCH_T(c->dtype, hipLaunchKernelGGL((update_v_r_multi_kernel<T>), dim3(vec_grid(n, 256), s), dim3(256), 0, c->stream, (T*)v, (T*)r, (const T*)p,
+                                                 (const T*)Ap, n, rz, pAp, update_r));
+    CGLB_LAUNCH_CHECK(c);
+    return CGLB_OK;
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void update_p_multi_kernel(T* __restrict__ p, const T* __restrict__ z, int64_t n, const double* __restrict__ new_rz,
+                                                             const double* __restrict__ rz, int restart) {
+    const int64_t off = (int64_t)blockIdx.y * n;
+    const double den = rz[blockIdx.y];
+    const T beta = (restart || den == 0.0) ? T(0) : (T)(new_rz[blockIdx.y] / den);
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
+        p[off + i] = restart ? z[off + i] : tfma<T>(beta, p[off + i], z[off + i]);
+}
+int launch_update_p_multi(cglb_ctx* c, void* p, const void* z, const double* new_rz, const double* rz, int restart, int64_t n, int s) {
+    CGLB_DISPATCH_T(c->dtype, hipLaunchKernelGGL((update_p_multi_kernel<T>), dim3(vec_grid(n, 256), s), dim3(256), 0, c->stream, (T*)p, (const T*)z, n, new_rz,
+                                                 rz, restart));
+    CGLB_LAUNCH_CHECK(c);
+    return CGLB_OK;
+}
+
 // ---- y += alpha x  (adds the noise * p diagonal term to an all-reduced K_ff p) ----------------------------------
 template <typename T>
 __global__ __launch_bounds__(256) void axpy_kernel(T* __restrict__ y, T alpha, const T* __restrict__ x, int64_t n) {

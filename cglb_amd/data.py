@@ -12,7 +12,9 @@ import math
 import numpy as np
 
 
-def synthetic_problem(N: int, D: int, M: int, seed: int = 0, dtype=np.float64):
+def synthetic_problem(N: int, D: int, M: int, seed: int = 0, dtype=np.float64, P: int = 1):
+    """P = 1: y [N].  P > 1: Y [N, P]; column 0, X and Z are exactly the P = 1 arrays, the further columns sin(X a_b + phase_b) + noise
+    come from one generator per column, so that they do not disturb that stream and column b is the same whatever P."""
     rng = np.random.default_rng(seed)
     X = rng.standard_normal((N, D))
     a = rng.standard_normal(D) / math.sqrt(D)
@@ -20,6 +22,14 @@ def synthetic_problem(N: int, D: int, M: int, seed: int = 0, dtype=np.float64):
     y = (y - y.mean()) / y.std()
     perm = rng.permutation(N)
     Z = X[perm[:M]].copy()
+    if P > 1:
+        cols = [y]
+        for b in range(1, P):
+            rng_p = np.random.default_rng([seed, b])   # per column: the sets are nested, column b is the same for every P > b
+            ab = rng_p.standard_normal(D) / math.sqrt(D)
+            yb = np.sin(X @ ab + rng_p.uniform(0.0, math.pi)) + 0.1 * rng_p.standard_normal(N)
+            cols.append((yb - yb.mean()) / yb.std())
+        y = np.stack(cols, axis=1)
     return X.astype(dtype), y.astype(dtype), Z.astype(dtype)
 
 

@@ -47,10 +47,13 @@ class HipContext:
         self.dtype = dtype
         self.kind = KINDS[kind]
         X = torch.as_tensor(X, dtype=dtype).reshape(len(X), -1).contiguous()
-        y = torch.as_tensor(y, dtype=dtype).reshape(-1).contiguous()
+        y = torch.as_tensor(y, dtype=dtype)
         self.N, self.D = int(X.shape[0]), int(X.shape[1])
+        # targets: [N] or [N, P]; one column (either shape) is the single-output model, P > 1 goes through cglb_set_targets below
+        y = y.reshape(self.N, -1) if (y.dim() == 2 and y.shape[0] == self.N and y.shape[1] > 1) else y.reshape(-1)
         if y.shape[0] != self.N:
             raise ValueError("X and y disagree on the number of rows")
+        self.P = 1
         self.M = int(num_inducing)
         self.r0, self.r1 = (0, self.N) if row_range is None else (int(row_range[0]), int(row_range[1]))
         self.nloc = self.r1 - self.r0
@@ -62,9 +65,12 @@ class HipContext:
                                           self.device.index or 0, c_void_p(stream))
         _lib.check(rc, None)
         Xd, yd = X.to(self.device), y.to(self.device)
-        _lib.check(self.lib.cglb_set_data(self._ctx, _ptr(Xd), _ptr(yd)), self._ctx)
+        y0 = yd if yd.dim() == 1 else yd[:, 0].contiguous()
+        _lib.check(self.lib.cglb_set_data(self._ctx, _ptr(Xd), _ptr(y0)), self._ctx)
         torch.cuda.synchronize(self.device)
         self.y = yd
+        if yd.dim() == 2:
+            self.set_targets(yd)
 
     # -- lifetime ------------------------------------------------------------------------------------
     def close(self):
@@ -157,9 +163,75 @@ class HipContext:
         _lib.check(rc, self._ctx)
         return v, steps.value, half.value
 
+    # -- multi-output targets: tensors are [N, P] on this side, [P, N] (column b contiguous) in the library ----------------
+    def _cols(self, t, s=None) -> torch.Tensor:
+        """[N, S] (or [N]) tensor -> contiguous [S, N] device tensor (always a copy for S > 1)."""
+        t = torch.as_tensor(t, dtype=self.dtype, device=self.device)
+        t = t.reshape(self.N, -1)
+        if s is not None and t.shape[1] != s:
+            raise ValueError(f"expected {s} columns, got {t.shape[1]}")
+        return t.t().contiguous()
+
+    def set_targets(self, Y):
+        """Replace the targets by Y [N, P] (or [N]): cglb_set_targets."""
+        Yt = self._cols(Y)
+        _lib.check(self.lib.cglb_set_targets(self._ctx, _ptr(Yt), int(Yt.shape[0])), self._ctx)
+        self.P = int(Yt.shape[0])
+        self.y = Yt[0].clone() if self.P == 1 else Yt.t().contiguous()
+
+    def matmat(self, V) -> torch.Tensor:
+        """(K_ff + noise I) V for V [N, S]: one evaluation of every kernel value for up to 8 columns (cglb_matmat)."""
+        Vt = self._cols(V)
+        out = torch.empty((Vt.shape[0], self.nloc), dtype=self.dtype, device=self.device)
+        _lib.check(self.lib.cglb_matmat(self._ctx, _ptr(Vt), int(Vt.shape[0]), _ptr(out)), self._ctx)
+        return out.t().contiguous()
+
+    def pcg_multi(self, B, V0, max_error=1.0, max_cg_iter=100, restart_cg_iter=40):
+        """Batched PCG on B, V0 [N, S]: returns (V [N, S], steps, 1/2 sum_b r_b^T P r_b, per-column terms [S])."""
+        Bt = self._cols(B)
+        Vt = self._cols(V0, Bt.shape[0]).clone()
+        s = int(Bt.shape[0])
+        steps, half = c_int(), c_double()
+        cols = np.empty(s, dtype=np.float64)
+        rc = self.lib.cglb_pcg_solve_multi(self._ctx, _ptr(Bt), _ptr(Vt), s, float(max_error), int(max_cg_iter), int(restart_cg_iter),
+                                           byref(steps), byref(half), cols.ctypes.data_as(ctypes.POINTER(c_double)))
+        _lib.check(rc, self._ctx)
+        return Vt.t().contiguous(), steps.value, half.value, cols
+
+    def predict_multi(self, V, xnew) -> Tuple[torch.Tensor, torch.Tensor]:
+        """f_mean [n_new, P] for the P target columns and the shared f_var [n_new] (cglb_predict_multi)."""
+        xn = torch.as_tensor(xnew, dtype=self.dtype).reshape(-1, self.D).contiguous().to(self.device)
+        Vt = self._cols(V, self.P)
+        mean = torch.empty((self.P, xn.shape[0]), dtype=self.dtype, device=self.device)
+        var = self.empty(xn.shape[0])
+        _lib.check(self.lib.cglb_predict_multi(self._ctx, _ptr(Vt), _ptr(xn), xn.shape[0], _ptr(mean), _ptr(var)), self._ctx)
+        return mean.t().contiguous(), var
+
+    def time_matmat(self, s: int, reps: int) -> float:
+        ms = c_double()
+        _lib.check(self.lib.cglb_time_matmat(self._ctx, int(s), int(reps), byref(ms)), self._ctx)
+        return ms.value
+
+    def _objective_and_grad_multi(self, v_inout, run_cg, max_error, max_cg_iter, restart_cg_iter, with_grad) -> ObjectiveResult:
+        if v_inout.device != self.device or v_inout.dtype != self.dtype or tuple(v_inout.shape) != (self.N, self.P):
+            raise ValueError("v_inout must be a device tensor of shape [N, P] in the context dtype")
+        Vt = v_inout.t().contiguous()
+        out4 = (c_double * 4)()
+        g = np.empty(grad_len(self.D, self.M), dtype=np.float64) if with_grad else None
+        steps, half = c_int(), c_double()
+        rc = self.lib.cglb_objective_and_grad_multi(
+            self._ctx, _ptr(Vt), int(bool(run_cg)), float(max_error), int(max_cg_iter), int(restart_cg_iter), out4,
+            g.ctypes.data_as(ctypes.POINTER(c_double)) if with_grad else None, byref(steps), byref(half))
+        _lib.check(rc, self._ctx)
+        if run_cg:
+            v_inout.copy_(Vt.t())  # the persistent warm start, in the caller's layout
+        return ObjectiveResult(out4[0], out4[1], out4[2], out4[3], steps.value, half.value, self.unpack_grad(g) if with_grad else None)
+
     def objective_and_grad(self, v_inout: torch.Tensor, run_cg=True, max_error=1.0, max_cg_iter=100, restart_cg_iter=40,
                            with_grad=True) -> ObjectiveResult:
-        """v_inout (device, length N) is the persistent warm-start vector: updated in place when run_cg."""
+        """v_inout (device, length N; [N, P] for P > 1 target columns) is the persistent warm-start vector: updated in place when run_cg."""
+        if self.P > 1:
+            return self._objective_and_grad_multi(v_inout, run_cg, max_error, max_cg_iter, restart_cg_iter, with_grad)
         if v_inout.device != self.device or v_inout.dtype != self.dtype or v_inout.numel() != self.N or not v_inout.is_contiguous():
             raise ValueError("v_inout must be a contiguous device vector of length N in the context dtype")
         out4 = (c_double * 4)()

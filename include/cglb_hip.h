@@ -216,6 +216,35 @@ int cglb_dist_objective_and_grad(cglb_ctx* ctx, void* v_full_inout, int run_cg, 
                                  double* out4, double* grad, int* steps, double* half_rz);
 int cglb_dist_predict(cglb_ctx* ctx, const void* v_full, const void* xnew, int64_t n_new, void* f_mean, void* f_var);
 
+/* ---- multi-output targets: Y[N, P] with one shared kernel, mean and noise (tensorflow/models.py:45-47 v0 as [B, N], :90-104 the log-det
+ *      term times output_dim, :183-187 the constant -N P/2 log 2 pi, :245 the variance tiled over the outputs) ------------------------------
+ * Every multi-column array is [P, N]: column b is a contiguous length-N vector at offset b * N, so every single-vector entry point works
+ * on one column by pointer offset.  One shard covering all rows, one rank, logdet_bound 0 and quad_term 0.  With s = 1 / p = 1 each of
+ * these calls the single-column code (bit-identical results).
+ * Batched PCG: the P columns are P independent recurrences (conjugate_gradient.py:41-86 per column) with their own
+ * gamma_b = rz_b / pAp_b and beta_b = rz_b' / rz_b, advancing in lockstep over ONE product K_ff P[N, P] per iteration that evaluates every
+ * kernel value once for up to 8 columns (fp64, d <= 32, unclamped exponent range, kff_variant 2; otherwise s single mat-vecs).  One
+ * stop test before every iteration: 1/2 sum_b r_b^T P r_b <= max_error or steps == max_cg_iter (the sum is the gap upper - lower of the
+ * summed bound); the restart rule applies to all columns at once; pAp_b == 0 gives gamma_b = 0 and rz_b == 0 gives beta_b = 0 (a column
+ * that is exactly converged or all zero stays finite and leaves the others unchanged). */
+/* replaces the targets: Y any [p, n_total].  After cglb_set_data p = 1.  CGLB_ERR_BAD_ARG on a context with more than one rank or with
+ * logdet_bound / quad_term other than 0; cglb_set_parallel, cglb_comm_init_* and those two options refuse a context with p > 1. */
+int cglb_set_targets(cglb_ctx* ctx, const void* Y, int p);
+/* Out[b] = (K_ff + noise I) V[b].  V: dev [s, n_total]; Out: dev [s, n_local]. */
+int cglb_matmat(cglb_ctx* ctx, const void* V, int s, void* Out);
+/* B, V_inout: dev [s, n].  half_rz_total = 1/2 sum_b r_b^T P r_b; half_rz_cols: host [s] (the terms of that sum) or NULL. */
+int cglb_pcg_solve_multi(cglb_ctx* ctx, const void* B, void* V_inout, int s, double max_error, int max_cg_iter, int restart_cg_iter, int* steps,
+                         double* half_rz_total, double* half_rz_cols);
+/* V_inout: dev [p, n] for the p columns of cglb_set_targets.  bound = sum_b (-upper_b) + p logdet - n p / 2 log 2 pi;
+ * out4 = {bound, sum_b lower_b, sum_b upper_b, p logdet}; grad (packed layout unchanged, one shared mean) = the sum over b of the
+ * single-output gradients at v_b, the log-det part taken p times. */
+int cglb_objective_and_grad_multi(cglb_ctx* ctx, void* V_inout, int run_cg, double max_error, int max_cg_iter, int restart_cg_iter, double* out4,
+                                  double* grad, int* steps, double* half_rz);
+/* f_mean: dev [p, n_new]; f_var: dev [n_new] (the variance does not depend on the column). */
+int cglb_predict_multi(cglb_ctx* ctx, const void* V, const void* xnew, int64_t n_new, void* f_mean, void* f_var);
+/* average duration (ms) of `reps` back-to-back products with s columns (pair kernel + slab combine), in the style of cglb_time_kernel(which = 0) */
+int cglb_time_matmat(cglb_ctx* ctx, int s, int reps, double* ms_avg);
+
 /* ---- inducing-point initialisation: InducingVariableConfig.init, config.py:55-65 ------------------------
  * The reference calls robustgp.ConditionalVariance(sample=False) (third-party): greedy maximisation of the conditional
  * variance under the INITIAL kernel (pivoted Cholesky of K_ff, lowest index on ties).  Needs set_data only; works on all n rows
