@@ -364,27 +364,40 @@ int require_single(cglb_ctx* c) {
 inline double lookahead_factor(const cglb_ctx* c) { return c->pcg_lookahead >= 2 ? (double)c->pcg_lookahead : CGLB_LOOKAHEAD_FACTOR; }
 
 // ---- PCG (conjugate_gradient.py:41-86) ----------------------------------------------------------------------
-// What the one loop below is told about its caller: where the recurrence keeps its vectors and how the two operators are applied.
+// What the one loop below is told about its caller: where the recurrence keeps its vectors and scalars, how many columns it advances and
+// how the two operators are applied.
 //   fused (one GPU, one shard): the context's own work vectors; p.Ap comes out of the mat-vec's slab combine; z = P r in one piece
 //   N ranks: replicated full-length vectors of the communicator state; cyclic share + all-reduce, then a dot over the summed product
 //            (another summation order than the fused one, on purpose); z gathered in segments
+//   s columns (multi-output targets): s independent recurrences, each with its own gamma_b and beta_b, in lockstep over one mat-mat
+//            product per iteration (kernels_kff_multi.hip); vectors [s][n], column b contiguous
 struct pcg_ops {
-    void *r, *p, *Ap, *Kv;  // [n]
+    void *r, *z, *p, *Ap, *Kv;  // [s][n]; z is the direction's scratch (unused on N ranks, which gather z in segments)
     int64_t n;
-    int (*matvec)(cglb_ctx* c, const void* x, void* out, double* pdot_slot);  // out = (K_ff + noise I) x; x.out into pdot_slot if it fuses the dot
+    int s;                      // columns
+    double *rz, *nrz, *pap;     // [s] device scalars; rz and nrz swap roles every iteration
+    double* host;               // [s] pinned host mirror of the stop-test scalars
+    int (*matvec)(cglb_ctx* c, const pcg_ops& o, const void* x, void* out, double* pdot_slot);  // out_b = (K_ff + noise I) x_b; x.out into pdot_slot if it fuses the dot
     bool dot_fused;         // false: pdot_slot is ignored and a launch_dot follows the mat-vec
     int (*direction)(cglb_ctx* c, const pcg_ops& o, double* rz_new, const double* rz_old, int restart);  // z = P r, rz_new = r.z, p = z (+ p rz_new / rz_old)
     bool rz_must_be_finite; // N ranks leave the loop together or not at all: a non-finite r^T P r is CGLB_ERR_COMM, not a quiet end
 };
 
 int fused_direction(cglb_ctx* c, const pcg_ops& o, double* rz_new, const double* rz_old, int restart) {
-    CGLB_TRY(precond_single(c, o.r, c->w_z, rz_new));                                               // :59 / :73
-    return launch_update_p(c, o.p, c->w_z, rz_new, rz_old, restart, -1, true);                      // :61 / :75 (+ the weighted copy for the next mat-vec)
+    CGLB_TRY(precond_single(c, o.r, o.z, rz_new));                                                  // :59 / :73
+    return launch_update_p(c, o.p, o.z, rz_new, rz_old, restart, -1, true);                         // :61 / :75 (+ the weighted copy for the next mat-vec)
 }
-inline pcg_ops fused_ops(cglb_ctx* c) { return {c->w_r, c->w_p, c->w_Ap, c->w_Kv, c->nloc, launch_kff_matvec, true, fused_direction, false}; }
+inline pcg_ops fused_ops(cglb_ctx* c) {
+    return {c->w_r, c->w_z, c->w_p, c->w_Ap, c->w_Kv, c->nloc, 1, c->scal + S_RZ, c->scal + S_NRZ, c->scal + S_PAP, c->host_scal,
+            [](cglb_ctx* cc, const pcg_ops&, const void* x, void* out, double* pdot) { return launch_kff_matvec(cc, x, out, pdot); }, true, fused_direction, false};
+}
 
-int pcg_solve(cglb_ctx* c, const pcg_ops& o, const void* b, void* v, double max_error, int max_iter, int restart_iter, int* steps, double* half_rz) {
+// One stop test before every iteration on 1/2 sum_b r_b^T P r_b (s > 1: the gap upper - lower of the summed bound); the restart rule
+// applies to all columns at once.  half_rz: that sum; half_rz_cols (optional, [s]): its terms.
+int pcg_solve(cglb_ctx* c, const pcg_ops& o, const void* b, void* v, double max_error, int max_iter, int restart_iter, int* steps, double* half_rz,
+              double* half_rz_cols = nullptr) {
     double* S = c->scal;
+    const int64_t sn = (int64_t)o.s * o.n;
     // A weighted copy p o w left behind by the LAST update of an earlier solve (loop left without a look-ahead mat-vec) must not be
     // taken for the operand of this solve's first mat-vec: the direction vector is rewritten below.
     c->pwh_src = nullptr;
@@ -392,18 +405,23 @@ int pcg_solve(cglb_ctx* c, const pcg_ops& o, const void* b, void* v, double max_
     // A cold start (v == 0, models.py:59-68) gives Av == 0 and r == b exactly, so the mat-vec is skipped in that case;
     // the result is bit-identical to computing it.  (On N ranks v is replicated: every rank takes the same branch.)
     double vnorm = 0.0;
-    CGLB_TRY(launch_dot(c, v, v, o.n, S + S_TMP));
+    CGLB_TRY(launch_dot(c, v, v, sn, S + S_TMP));
     CGLB_TRY(read_scalars(c, S + S_TMP, &vnorm, 1));
     if (vnorm == 0.0) {
-        HIP_CHECK(c, hipMemcpyAsync(o.r, b, (size_t)o.n * c->esz, hipMemcpyDeviceToDevice, c->stream));
+        HIP_CHECK(c, hipMemcpyAsync(o.r, b, (size_t)sn * c->esz, hipMemcpyDeviceToDevice, c->stream));
     } else {
-        CGLB_TRY(o.matvec(c, v, o.Kv, nullptr));
-        CGLB_TRY(launch_residual(c, o.r, b, o.Kv, o.n));
+        CGLB_TRY(o.matvec(c, o, v, o.Kv, nullptr));
+        CGLB_TRY(launch_residual(c, o.r, b, o.Kv, sn));
     }
-    double *s_rz = S + S_RZ, *s_nrz = S + S_NRZ;  // the two slots swap roles every iteration (:76) instead of being copied
+    double *s_rz = o.rz, *s_nrz = o.nrz;  // the two slots swap roles every iteration (:76) instead of being copied
     CGLB_TRY(o.direction(c, o, s_rz, s_rz, 1));
-    double rz = 0;
-    CGLB_TRY(read_scalars(c, s_rz, &rz, 1));
+    const auto host_sum = [&o]() {  // in column order
+        double t = o.host[0];
+        for (int k = 1; k < o.s; ++k) t += o.host[k];
+        return t;
+    };
+    CGLB_TRY(read_scalars(c, s_rz, o.host, o.s));
+    double rz = host_sum();
     if (o.rz_must_be_finite && !std::isfinite(rz)) return cglb_fail(c, CGLB_ERR_COMM, "r^T P r is not finite at the start of the solve");
     // The stop predicate (:65) is evaluated on the host, like the reference's (:80-81).  Look-ahead: while the residual is
     // still far above the tolerance (more than CGLB_LOOKAHEAD_FACTOR = 32x after the PREVIOUS iteration), the mat-vec of the next iteration is enqueued
@@ -412,27 +430,29 @@ int pcg_solve(cglb_ctx* c, const pcg_ops& o, const void* b, void* v, double max_
     int i = 0;
     bool ahead = false;
     while (0.5 * rz > max_error && i < max_iter) {  // :65
-        if (!ahead) CGLB_TRY(o.matvec(c, o.p, o.Ap, S + S_PAP));                                    // :66 and (p*Ap).sum() where fused
-        if (!o.dot_fused) CGLB_TRY(launch_dot(c, o.p, o.Ap, o.n, S + S_PAP));                       // :67
+        if (!ahead) CGLB_TRY(o.matvec(c, o, o.p, o.Ap, o.pap));                                     // :66 and (p*Ap).sum() where fused
+        if (!o.dot_fused) CGLB_TRY(launch_dot(c, o.p, o.Ap, o.n, o.pap, o.s));                      // :67
         const int restart = (restart_iter > 0) && (i % restart_iter == restart_iter - 1);          // :70
-        CGLB_TRY(launch_update_v_r(c, v, o.r, o.p, o.Ap, s_rz, S + S_PAP, !restart, o.n));          // :67-68, :72
+        CGLB_TRY(launch_update_v_r(c, v, o.r, o.p, o.Ap, s_rz, o.pap, !restart, o.n, o.s));         // :67-68, :72
         if (restart) {
-            CGLB_TRY(o.matvec(c, v, o.Kv, nullptr));
-            CGLB_TRY(launch_residual(c, o.r, b, o.Kv, o.n));
+            CGLB_TRY(o.matvec(c, o, v, o.Kv, nullptr));
+            CGLB_TRY(launch_residual(c, o.r, b, o.Kv, sn));
         }
         CGLB_TRY(o.direction(c, o, s_nrz, s_rz, restart));                                          // :73, :75
         std::swap(s_rz, s_nrz);                                                                     // :76
-        HIP_CHECK(c, hipMemcpyAsync(c->host_scal, s_rz, sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        HIP_CHECK(c, hipMemcpyAsync(o.host, s_rz, sizeof(double) * o.s, hipMemcpyDeviceToHost, c->stream));
         HIP_CHECK(c, hipEventRecord(c->scal_event, c->stream));
         ahead = c->pcg_lookahead && (i + 1 < max_iter) && (0.5 * rz > lookahead_factor(c) * max_error);  // rz: still the value of the previous iteration
-        if (ahead) CGLB_TRY(o.matvec(c, o.p, o.Ap, S + S_PAP));
+        if (ahead) CGLB_TRY(o.matvec(c, o, o.p, o.Ap, o.pap));
         HIP_CHECK(c, hipEventSynchronize(c->scal_event));                                            // host test of :65 (and the sync of :80-81)
-        rz = c->host_scal[0];  // N ranks: a function of all-gathered numbers only, so every rank reads the same value and leaves the loop together
+        rz = host_sum();  // N ranks: a function of all-gathered numbers only, so every rank reads the same value and leaves the loop together
         if (o.rz_must_be_finite && !std::isfinite(rz)) return cglb_fail(c, CGLB_ERR_COMM, "r^T P r is not finite after iteration " + std::to_string(i));
         ++i;
     }
     if (steps) *steps = i;
     if (half_rz) *half_rz = 0.5 * rz;  // :83
+    if (half_rz_cols)
+        for (int k = 0; k < o.s; ++k) half_rz_cols[k] = 0.5 * o.host[k];
     return CGLB_OK;
 }
 
@@ -705,29 +725,33 @@ struct eval_marks_guard {
     ~eval_marks_guard() { if (!done) c->eval_events_used = used; }
 };
 
-// The front half of an evaluation, the same on one GPU and on N ranks (o, b: where that path keeps the recurrence and its right-hand side):
-// the solve from e = y - mean (models.py:262-278), the third mark, K v, and phase 1 for that K v.
+// The solve of an evaluation and its K v, the same on one GPU, on N ranks and for s columns (o, b: where that path keeps the recurrence and its
+// right-hand side; y: the targets, [s][n]): the solve from e = y - mean (models.py:262-278), the third mark, then K v into o.Kv.
 // K v (option "final_matvec"): 1 recomputes it as the reference does (`cov @ v`, models.py:280).  0 (default), straight after a solve: o.r
 // still holds the residual the PCG recurrence carries, r = e - K v up to the rounding of its updates (exact at the start of the solve and after
 // every restart step, conjugate_gradient.py:58,72), so K v = e - r costs one vector kernel instead of N^2 pair evaluations.  The two differ
 // at the level of the mat-vec's own rounding (measured: DESIGN.md section 5).
-int eval_solve_phase1(cglb_ctx* c, const pcg_ops& o, void* b, void* v, int run_cg, double max_error, int max_iter, int restart_iter, int* steps,
-                      double* half_rz, void* u_partial) {
+int eval_solve_kv(cglb_ctx* c, const pcg_ops& o, void* b, const void* y, void* v, int run_cg, double max_error, int max_iter, int restart_iter, int* steps,
+                  double* half_rz) {
     if (steps) *steps = 0;
     if (half_rz) *half_rz = std::nan("");
     if (run_cg) {
-        CGLB_TRY(launch_sub_scalar(c, b, c->y, c->mean, o.n));
+        CGLB_TRY(launch_sub_scalar(c, b, y, c->mean, (int64_t)o.s * o.n));
         CGLB_TRY(pcg_solve(c, o, b, v, max_error, max_iter, restart_iter, steps, half_rz));
     }
     CGLB_TRY(eval_mark(c));
-    if (c->quad_term == 1) return obj_phase1_exact(c, u_partial);  // v = 0: no K v at all (one rank only: require_variant_ok, comm_alloc)
-    if (!run_cg || c->final_matvec) {
-        CGLB_TRY(o.matvec(c, v, o.Kv, nullptr));
-    } else {
-        CGLB_TRY(launch_residual(c, o.Kv, b, o.r, o.n));
-        // fused: the recurrence ran in the evaluation's own work vectors, so e and r are in place already (and r stays the recurrence's)
-        if (o.r == c->w_r) return precond_u_any(c, c->w_r, u_partial);
-    }
+    if (c->quad_term == 1) return CGLB_OK;  // v = 0: no K v at all (one rank, one column only: require_variant_ok, comm_alloc, require_multi_ok)
+    if (!run_cg || c->final_matvec) return o.matvec(c, o, v, o.Kv, nullptr);
+    return launch_residual(c, o.Kv, b, o.r, (int64_t)o.s * o.n);
+}
+
+// ... and phase 1 for that K v, one column
+int eval_solve_phase1(cglb_ctx* c, const pcg_ops& o, void* b, void* v, int run_cg, double max_error, int max_iter, int restart_iter, int* steps,
+                      double* half_rz, void* u_partial) {
+    CGLB_TRY(eval_solve_kv(c, o, b, c->y, v, run_cg, max_error, max_iter, restart_iter, steps, half_rz));
+    if (c->quad_term == 1) return obj_phase1_exact(c, u_partial);
+    // fused, K v = e - r: the recurrence ran in the evaluation's own work vectors, so e and r are in place already (and r stays the recurrence's)
+    if (run_cg && !c->final_matvec && o.r == c->w_r) return precond_u_any(c, c->w_r, u_partial);
     return obj_phase1_kv(c, (const char*)o.Kv + (size_t)c->r0 * c->esz, u_partial);
 }
 
@@ -854,7 +878,8 @@ int dist_direction(cglb_ctx* c, const pcg_ops& o, double* rz_new, const double* 
 // pcg_solve on replicated full vectors: three collectives per iteration (the mat-vec's all-reduce, u, the gather of z)
 inline pcg_ops dist_ops(cglb_ctx* c) {
     cglb_comm_state* m = c->comm;
-    return {m->r, m->p, m->Ap, m->Kv, c->N, [](cglb_ctx* cc, const void* x, void* out, double*) { return dist_matvec(cc, x, out); }, false, dist_direction, true};
+    return {m->r, nullptr, m->p, m->Ap, m->Kv, c->N, 1, c->scal + S_RZ, c->scal + S_NRZ, c->scal + S_PAP, c->host_scal,
+            [](cglb_ctx* cc, const pcg_ops&, const void* x, void* out, double*) { return dist_matvec(cc, x, out); }, false, dist_direction, true};
 }
 
 template <typename T>
@@ -867,17 +892,16 @@ __global__ __launch_bounds__(256) void unpack_pairs_kernel(const T* __restrict__
 }
 
 // ================================ multi-output targets: P columns, one shared K_ff product ================================
-// Column b of every [P][N] array is a contiguous vector; the batched PCG advances P independent recurrences (conjugate_gradient.py:41-86
-// per column, each with its own gamma_b and beta_b) in lockstep over one mat-mat product per iteration (kernels_kff_multi.hip).
+// Column b of every [P][N] array is a contiguous vector; pcg_solve advances the P recurrences through multi_ops.
 struct multi_work {
     char *r, *z, *p, *Ap, *Kv, *b;      // [s][N]
-    double *rz, *nrz, *pap, *tmp;       // [s] device scalars
+    double *rz, *nrz, *pap;             // [s] device scalars
 };
 
 int multi_reserve(cglb_ctx* c, int s, multi_work* w) {
     const size_t vec = (size_t)s * c->N * c->esz;
     CGLB_TRY(c->mem.reserve(c, &c->mw, &c->mw_cap, 6 * vec));
-    CGLB_TRY(c->mem.reserve(c, &c->mscal, &c->mscal_cap, (size_t)4 * s * sizeof(double)));
+    CGLB_TRY(c->mem.reserve(c, &c->mscal, &c->mscal_cap, (size_t)3 * s * sizeof(double)));
     if (c->mhost_cap < s) {
         if (c->mhost) (void)hipHostFree(c->mhost);
         c->mhost = nullptr; c->mhost_cap = 0;
@@ -886,7 +910,7 @@ int multi_reserve(cglb_ctx* c, int s, multi_work* w) {
     }
     char* base = (char*)c->mw;
     w->r = base; w->z = base + vec; w->p = base + 2 * vec; w->Ap = base + 3 * vec; w->Kv = base + 4 * vec; w->b = base + 5 * vec;
-    w->rz = c->mscal; w->nrz = c->mscal + s; w->pap = c->mscal + 2 * s; w->tmp = c->mscal + 3 * s;
+    w->rz = c->mscal; w->nrz = c->mscal + s; w->pap = c->mscal + 2 * s;
     return CGLB_OK;
 }
 
@@ -900,68 +924,15 @@ int require_multi_ok(cglb_ctx* c) {
 
 // z_b = P r_b column by column through the single launches (a batched panel pass is a follow-up), rz_new[b] = r_b . z_b, then the
 // direction update of all columns in one launch
-int multi_direction(cglb_ctx* c, const multi_work& w, int s, double* rz_new, const double* rz_old, int restart) {
-    const size_t stride = (size_t)c->N * c->esz;
-    for (int b = 0; b < s; ++b) CGLB_TRY(precond_single(c, w.r + b * stride, w.z + b * stride, rz_new + b));
-    return launch_update_p_multi(c, w.p, w.z, rz_new, rz_old, restart, c->N, s);
+int multi_direction(cglb_ctx* c, const pcg_ops& o, double* rz_new, const double* rz_old, int restart) {
+    const size_t stride = (size_t)o.n * c->esz;
+    for (int b = 0; b < o.s; ++b) CGLB_TRY(precond_single(c, (const char*)o.r + b * stride, (char*)o.z + b * stride, rz_new + b));
+    return launch_update_p(c, o.p, o.z, rz_new, rz_old, restart, o.n, false, o.s);
 }
-
-// sum of s device scalars read back in column order; the values stay in c->mhost
-int multi_read_sum(cglb_ctx* c, const double* dev, int s, double* sum) {
-    HIP_CHECK(c, hipMemcpyAsync(c->mhost, dev, sizeof(double) * s, hipMemcpyDeviceToHost, c->stream));
-    HIP_CHECK(c, hipStreamSynchronize(c->stream));
-    double t = 0.0;
-    for (int b = 0; b < s; ++b) t += c->mhost[b];
-    *sum = t;
-    return CGLB_OK;
-}
-
-// One stop test before every iteration on 1/2 sum_b r_b^T P r_b (the gap upper - lower of the summed bound); the restart rule applies to
-// all columns at once; look-ahead as in pcg_solve, on the summed statistic.
-int pcg_solve_multi(cglb_ctx* c, const multi_work& w, const void* B, void* V, int s, double max_error, int max_iter, int restart_iter, int* steps,
-                    double* half_rz_total, double* half_rz_cols) {
-    const int64_t n = c->N, sn = (int64_t)s * c->N;
-    c->pwh_src = nullptr;
-    double vnorm = 0.0;
-    CGLB_TRY(launch_dot(c, V, V, sn, c->scal + S_TMP));
-    CGLB_TRY(read_scalars(c, c->scal + S_TMP, &vnorm, 1));
-    if (vnorm == 0.0) {
-        HIP_CHECK(c, hipMemcpyAsync(w.r, B, (size_t)sn * c->esz, hipMemcpyDeviceToDevice, c->stream));
-    } else {
-        CGLB_TRY(launch_kff_matmat(c, V, s, w.Kv));
-        CGLB_TRY(launch_residual(c, w.r, B, w.Kv, sn));
-    }
-    double *s_rz = w.rz, *s_nrz = w.nrz;
-    CGLB_TRY(multi_direction(c, w, s, s_rz, s_rz, 1));
-    double rz = 0.0;
-    CGLB_TRY(multi_read_sum(c, s_rz, s, &rz));
-    int i = 0;
-    bool ahead = false;
-    while (0.5 * rz > max_error && i < max_iter) {
-        if (!ahead) CGLB_TRY(launch_kff_matmat(c, w.p, s, w.Ap));
-        CGLB_TRY(launch_dot_multi(c, w.p, w.Ap, n, s, w.pap));
-        const int restart = (restart_iter > 0) && (i % restart_iter == restart_iter - 1);
-        CGLB_TRY(launch_update_v_r_multi(c, V, w.r, w.p, w.Ap, s_rz, w.pap, !restart, n, s));
-        if (restart) {
-            CGLB_TRY(launch_kff_matmat(c, V, s, w.Kv));
-            CGLB_TRY(launch_residual(c, w.r, B, w.Kv, sn));
-        }
-        CGLB_TRY(multi_direction(c, w, s, s_nrz, s_rz, restart));
-        std::swap(s_rz, s_nrz);
-        HIP_CHECK(c, hipMemcpyAsync(c->mhost, s_rz, sizeof(double) * s, hipMemcpyDeviceToHost, c->stream));
-        HIP_CHECK(c, hipEventRecord(c->scal_event, c->stream));
-        ahead = c->pcg_lookahead && (i + 1 < max_iter) && (0.5 * rz > lookahead_factor(c) * max_error);
-        if (ahead) CGLB_TRY(launch_kff_matmat(c, w.p, s, w.Ap));
-        HIP_CHECK(c, hipEventSynchronize(c->scal_event));
-        rz = 0.0;
-        for (int b = 0; b < s; ++b) rz += c->mhost[b];
-        ++i;
-    }
-    if (steps) *steps = i;
-    if (half_rz_total) *half_rz_total = 0.5 * rz;
-    if (half_rz_cols)
-        for (int b = 0; b < s; ++b) half_rz_cols[b] = 0.5 * c->mhost[b];
-    return CGLB_OK;
+// pcg_solve on s columns in the buffers of multi_reserve(c, s, &w): one shared-kernel product per iteration, then a dot per column
+inline pcg_ops multi_ops(cglb_ctx* c, const multi_work& w, int s) {
+    return {w.r, w.z, w.p, w.Ap, w.Kv, c->N, s, w.rz, w.nrz, w.pap, c->mhost,
+            [](cglb_ctx* cc, const pcg_ops& o, const void* x, void* out, double*) { return launch_kff_matmat(cc, x, o.s, out); }, false, multi_direction, false};
 }
 
 // the single-column phases read the targets through c->y: point it at column b for the duration of a scope
@@ -976,6 +947,30 @@ struct target_column_guard {
 __global__ void grad_accumulate_kernel(double* __restrict__ sum, const double* __restrict__ g, int64_t n, int first) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) sum[i] = first ? g[i] : sum[i] + g[i];
+}
+
+// ms_avg = average time of `once` on the context stream over reps calls, after one warm-up call (which also sizes the work buffers)
+template <typename F>
+int time_repeated(cglb_ctx* c, int reps, F once, double* ms_avg) {
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    HIP_CHECK(c, hipEventCreate(&e0));
+    {
+        const hipError_t e = hipEventCreate(&e1);
+        if (e != hipSuccess) { (void)hipEventDestroy(e0); return cglb_fail(c, CGLB_ERR_HIP, std::string("hipEventCreate: ") + hipGetErrorString(e)); }
+    }
+    int rc = once();
+    if (rc == CGLB_OK) {
+        (void)hipEventRecord(e0, c->stream);
+        for (int i = 0; i < reps && rc == CGLB_OK; ++i) rc = once();
+        (void)hipEventRecord(e1, c->stream);
+        (void)hipEventSynchronize(e1);
+        float ms = 0;
+        (void)hipEventElapsedTime(&ms, e0, e1);
+        *ms_avg = (double)ms / reps;
+    }
+    (void)hipEventDestroy(e0);
+    (void)hipEventDestroy(e1);
+    return rc;
 }
 
 }  // namespace
@@ -1828,11 +1823,7 @@ int cglb_time_kernel(cglb_ctx* c, int which, int reps, double* ms_avg) {
     if (which != 0 && which != 3 && which != 4 && which != 5) CGLB_TRY(require_terms(c));
     HIP_CHECK(c, hipSetDevice(c->device));
     // operands: y as a generic vector (values do not change the instruction stream)
-    hipEvent_t e0, e1;
-    HIP_CHECK(c, hipEventCreate(&e0));
-    HIP_CHECK(c, hipEventCreate(&e1));
-    int rc = CGLB_OK;
-    auto once = [&]() -> int {
+    return time_repeated(c, reps, [&]() -> int {
         if (which == 0) return launch_kff_matvec(c, c->y, c->w_Ap, nullptr);
         if (which == 1) return precond_single(c, (const char*)c->y + (size_t)c->r0 * c->esz, c->w_z, c->scal + S_TMP);
         if (which == 2) return launch_grad_kff(c, c->y, (const char*)c->y + (size_t)c->r0 * c->esz, c->scal + S_TMP2);
@@ -1854,20 +1845,7 @@ int cglb_time_kernel(cglb_ctx* c, int which, int reps, double* ms_avg) {
             return r;
         }
         return cglb_fail(c, CGLB_ERR_BAD_ARG, "unknown kernel id");
-    };
-    rc = once();  // warm-up (also sizes the work buffers)
-    if (rc == CGLB_OK) {
-        (void)hipEventRecord(e0, c->stream);
-        for (int i = 0; i < reps && rc == CGLB_OK; ++i) rc = once();
-        (void)hipEventRecord(e1, c->stream);
-        (void)hipEventSynchronize(e1);
-        float ms = 0;
-        (void)hipEventElapsedTime(&ms, e0, e1);
-        *ms_avg = (double)ms / reps;
-    }
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-    return rc;
+    }, ms_avg);
 }
 
 // ---- multi-output targets (include/cglb_hip.h) ------------------------------------------------------------------------
@@ -1914,7 +1892,7 @@ int cglb_pcg_solve_multi(cglb_ctx* c, const void* B, void* V_inout, int s, doubl
     HIP_CHECK(c, hipSetDevice(c->device));
     multi_work w;
     CGLB_TRY(multi_reserve(c, s, &w));
-    return pcg_solve_multi(c, w, B, V_inout, s, max_error, max_cg_iter, restart_cg_iter, steps, half_rz_total, half_rz_cols);
+    return pcg_solve(c, multi_ops(c, w, s), B, V_inout, max_error, max_cg_iter, restart_cg_iter, steps, half_rz_total, half_rz_cols);
 }
 
 int cglb_objective_and_grad_multi(cglb_ctx* c, void* V_inout, int run_cg, double max_error, int max_cg_iter, int restart_cg_iter, double* out4,
@@ -1923,19 +1901,19 @@ int cglb_objective_and_grad_multi(cglb_ctx* c, void* V_inout, int run_cg, double
     if (c->p == 1) return cglb_objective_and_grad(c, V_inout, run_cg, max_error, max_cg_iter, restart_cg_iter, out4, grad, steps, half_rz);
     c->obj_valid = false;
     CGLB_TRY(require_multi_ok(c));
+    HIP_CHECK(c, hipSetDevice(c->device));
     const int P = c->p;
-    const int64_t pn = (int64_t)P * c->N;
     const size_t col = (size_t)c->N * c->esz, glen = (size_t)CGLB_GRAD_LEN(c->D, c->M);
+    if (c->eval_profile && c->eval_events_used + 5 > 5 * 512) CGLB_TRY(eval_collect(c));  // bounded pool
+    eval_marks_guard marks{c, c->eval_events_used};
+    CGLB_TRY(eval_mark(c));
     CGLB_TRY(cglb_setup(c));                                                        // models.py:155, shared by the columns
     multi_work w;
     CGLB_TRY(multi_reserve(c, P, &w));
-    if (steps) *steps = 0;
-    if (half_rz) *half_rz = std::nan("");
-    CGLB_TRY(launch_sub_scalar(c, w.b, c->Ym, c->mean, pn));                        // e_b = y_b - mean (one shared mean)
-    if (run_cg) CGLB_TRY(pcg_solve_multi(c, w, w.b, V_inout, P, max_error, max_cg_iter, restart_cg_iter, steps, half_rz, nullptr));
-    // K v for all columns: one shared-kernel product, or e - r from the residuals the recurrences carry (option "final_matvec", per column)
-    if (!run_cg || c->final_matvec) CGLB_TRY(launch_kff_matmat(c, V_inout, P, w.Kv));
-    else CGLB_TRY(launch_residual(c, w.Kv, w.b, w.r, pn));
+    CGLB_TRY(eval_mark(c));
+    // e_b = y_b - mean (one shared mean), the solve, K v for all columns (one shared-kernel product, or e - r per column)
+    CGLB_TRY(eval_solve_kv(c, multi_ops(c, w, P), w.b, c->Ym, V_inout, run_cg, max_error, max_cg_iter, restart_cg_iter, steps, half_rz));
+    CGLB_TRY(eval_mark(c));  // "eval_final_ms" is K v alone here: the columns below interleave their phase 1 / 2 with their gradients
     // the rest column by column through the single-output phases (a fused multi-column gradient pass is a follow-up); every column's
     // bound carries one log-det term and one constant, so the sums are the P-fold terms of the multi-output bound
     if (grad) CGLB_TRY(c->mem.alloc(c, &c->mgrad, glen * sizeof(double)));
@@ -1957,10 +1935,10 @@ int cglb_objective_and_grad_multi(cglb_ctx* c, void* V_inout, int run_cg, double
         CGLB_TRY(obj_finish(c, sc, o4));
         for (int k = 0; k < 4; ++k) out4[k] += o4[k];
     }
-    if (grad) {
-        HIP_CHECK(c, hipMemcpyAsync(grad, c->mgrad, glen * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-        HIP_CHECK(c, hipStreamSynchronize(c->stream));
-    }
+    if (grad) HIP_CHECK(c, hipMemcpyAsync(grad, c->mgrad, glen * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    CGLB_TRY(eval_mark(c));
+    if (grad) HIP_CHECK(c, hipStreamSynchronize(c->stream));
+    marks.done = true;
     return CGLB_OK;
 }
 
@@ -1996,26 +1974,7 @@ int cglb_time_matmat(cglb_ctx* c, int s, int reps, double* ms_avg) {
     CGLB_TRY(multi_reserve(c, s, &w));
     // operands: s copies of y (values do not change the instruction stream)
     for (int b = 0; b < s; ++b) HIP_CHECK(c, hipMemcpyAsync(w.p + (size_t)b * c->N * c->esz, c->y, (size_t)c->N * c->esz, hipMemcpyDeviceToDevice, c->stream));
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    HIP_CHECK(c, hipEventCreate(&e0));
-    {
-        const hipError_t e = hipEventCreate(&e1);
-        if (e != hipSuccess) { (void)hipEventDestroy(e0); return cglb_fail(c, CGLB_ERR_HIP, std::string("hipEventCreate: ") + hipGetErrorString(e)); }
-    }
-    auto once = [&]() -> int { return s == 1 ? launch_kff_matvec(c, w.p, w.Ap, nullptr) : launch_kff_matmat(c, w.p, s, w.Ap); };
-    int rc = once();  // warm-up (also sizes the slabs)
-    if (rc == CGLB_OK) {
-        (void)hipEventRecord(e0, c->stream);
-        for (int i = 0; i < reps && rc == CGLB_OK; ++i) rc = once();
-        (void)hipEventRecord(e1, c->stream);
-        (void)hipEventSynchronize(e1);
-        float ms = 0;
-        (void)hipEventElapsedTime(&ms, e0, e1);
-        *ms_avg = (double)ms / reps;
-    }
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-    return rc;
+    return time_repeated(c, reps, [&]() -> int { return s == 1 ? launch_kff_matvec(c, w.p, w.Ap, nullptr) : launch_kff_matmat(c, w.p, s, w.Ap); }, ms_avg);
 }
 
 }  // extern "C"

@@ -132,7 +132,7 @@ struct cglb_ctx {
     size_t k1_events_used = 0;
     double k1_ms_total = 0.0;
     long long k1_launches = 0;
-    // phase timing of cglb_objective_and_grad / cglb_dist_objective_and_grad ("eval_profile"): 5 events per completed evaluation (start | common terms | PCG | final mat-vec +
+    // phase timing of cglb_objective_and_grad / cglb_dist_objective_and_grad / cglb_objective_and_grad_multi ("eval_profile"): 5 events per completed evaluation (start | common terms | PCG | final mat-vec +
     // preconditioner + scalars | gradient), resolved lazily by cglb_get_stat "eval_*_ms"
     bool eval_profile = false;
     std::vector<hipEvent_t> eval_events;
@@ -180,9 +180,9 @@ struct cglb_ctx {
     size_t Ym_cap = 0;
     void* mw = nullptr;      // [6][s][N] work vectors of the batched PCG / evaluation: r, z, p, Ap, Kv, b
     size_t mw_cap = 0;
-    double* mscal = nullptr; // [4][s] device scalars per column: rz, new rz, p.Ap, scratch
+    double* mscal = nullptr; // [3][s] device scalars per column: rz, new rz, p.Ap (what scal + S_RZ / S_NRZ / S_PAP are to one column)
     size_t mscal_cap = 0;
-    double* mhost = nullptr; // pinned host mirror of one row of mscal (asynchronous read of the stop statistics)
+    double* mhost = nullptr; // [s] pinned host mirror of one row of mscal (what host_scal is to one column: pcg_ops::host)
     int mhost_cap = 0;
     double* mgrad = nullptr; // [GRAD_LEN] device sum of the per-column gradients
     void* mm_items = nullptr;   // work list (group of four row blocks, column span) of the multi-column pair kernel
@@ -319,15 +319,15 @@ int launch_scale(cglb_ctx* c, void* x, double a, int64_t n);
 int launch_precond_z_from(cglb_ctx* c, const void* r_local, const void* Ks_local, void* z_local, double* rz_slot);
 int launch_cross_matvec(cglb_ctx* c, const void* Xs_new, const void* xa_new, int64_t n_new, const void* v_full, void* out);
 // kernels_vec.hip
-int launch_dot(cglb_ctx* c, const void* a, const void* b, int64_t n, double* out_slot);
-int launch_update_v_r(cglb_ctx* c, void* v, void* r, const void* p, const void* Ap, const double* rz, const double* pAp, int update_r, int64_t n = -1);
+// dot, update_v_r, update_p: s columns of length n ([s][n], one launch each; per-column device scalars [s]); s = 1 is the one-column form.
+// A zero denominator gives a zero factor.
+int launch_dot(cglb_ctx* c, const void* a, const void* b, int64_t n, double* out_slots, int s = 1);
+int launch_update_v_r(cglb_ctx* c, void* v, void* r, const void* p, const void* Ap, const double* rz, const double* pAp, int update_r, int64_t n = -1,
+                      int s = 1);
 int launch_residual(cglb_ctx* c, void* r, const void* b, const void* Kv, int64_t n = -1);
 int launch_axpy(cglb_ctx* c, void* y, double alpha, const void* x, int64_t n);
-int launch_update_p(cglb_ctx* c, void* p, const void* z, const double* new_rz, const double* rz, int restart, int64_t n = -1, bool fuse = false);
-// batched forms over s columns of length n ([s][n], one launch each; per-column device scalars [s]); a zero denominator gives a zero factor
-int launch_dot_multi(cglb_ctx* c, const void* a, const void* b, int64_t n, int s, double* out_slots);
-int launch_update_v_r_multi(cglb_ctx* c, void* v, void* r, const void* p, const void* Ap, const double* rz, const double* pAp, int update_r, int64_t n, int s);
-int launch_update_p_multi(cglb_ctx* c, void* p, const void* z, const double* new_rz, const double* rz, int restart, int64_t n, int s);
+int launch_update_p(cglb_ctx* c, void* p, const void* z, const double* new_rz, const double* rz, int restart, int64_t n = -1, bool fuse = false,
+                    int s = 1);  // fuse: s == 1 only
 int launch_gemv_u(cglb_ctx* c, const void* r_local, void* u_out);               // u = A_loc r
 int launch_tri_apply(cglb_ctx* c, const void* u, void* t_out);                  // t = LB^-T LB^-1 u
 int launch_precond_z(cglb_ctx* c, const void* r_local, const void* t, void* z_local, double* rz_slot, void* rz_slot_T = nullptr);

@@ -4,13 +4,14 @@
 #include "devmath.h"
 #include "dispatch.h"
 
+// one block per sum: block k reduces partials[k * n .. k * n + n) in a fixed order into out[k]
 __global__ __launch_bounds__(256) void finalize_sum_kernel2(const double* __restrict__ partials, int n, double* __restrict__ out,
                                                             double scale) {
     __shared__ double smem[16];
     double s = 0.0;
-    for (int i = threadIdx.x; i < n; i += blockDim.x) s += partials[i];
+    for (int i = threadIdx.x; i < n; i += blockDim.x) s += partials[(int64_t)blockIdx.x * n + i];
     s = block_sum(s, smem);
-    if (threadIdx.x == 0) out[0] = s * scale;
+    if (threadIdx.x == 0) out[blockIdx.x] = s * scale;
 }
 
 static inline int vec_grid(int64_t n, int per_block = 1024) {
@@ -20,24 +21,32 @@ static inline int vec_grid(int64_t n, int per_block = 1024) {
     return (int)g;
 }
 
+// The three primitives of the PCG recurrence advance s independent recurrences in lockstep: blockIdx.y is the column, vectors are
+// [s][n] (column b contiguous), the device scalars rz[b], pAp[b], new_rz[b] belong to column b.  s = 1 is the one-column solve.
+// gamma_b = rz_b / pAp_b and beta_b = new_rz_b / rz_b; a zero denominator (a column that has converged exactly while its neighbours go
+// on, or an all-zero right-hand side) gives a zero factor, so that column stays where it is and stays finite.  NaN still propagates.
 // ---- dot ----------------------------------------------------------------------------------------------
 template <typename T>
 __global__ __launch_bounds__(256) void dot_kernel(const T* __restrict__ a, const T* __restrict__ b, int64_t n,
                                                   double* __restrict__ dotpart) {
     __shared__ double smem[16];
+    const T* __restrict__ ab = a + (int64_t)blockIdx.y * n;
+    const T* __restrict__ bb = b + (int64_t)blockIdx.y * n;
     double s = 0.0;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
-        s += (double)a[i] * (double)b[i];
+        s += (double)ab[i] * (double)bb[i];
     s = block_sum(s, smem);
-    if (threadIdx.x == 0) dotpart[blockIdx.x] = s;
+    if (threadIdx.x == 0) dotpart[(int64_t)blockIdx.y * gridDim.x + blockIdx.x] = s;
 }
 
-int launch_dot(cglb_ctx* c, const void* a, const void* b, int64_t n, double* out_slot) {
-    const int grid = vec_grid(n);
-    CGLB_DISPATCH_T(c->dtype, hipLaunchKernelGGL((dot_kernel<T>), dim3(grid), dim3(256), 0, c->stream, (const T*)a,
+int launch_dot(cglb_ctx* c, const void* a, const void* b, int64_t n, double* out_slots, int s) {
+    int grid = vec_grid(n);
+    if (grid > DOTPART_CAP / s) grid = DOTPART_CAP / s;  // column b's partials sit at dotpart[b * grid ..]
+    if (grid < 1) return cglb_fail(c, CGLB_ERR_BAD_ARG, "too many columns for the dot partials");
+    CGLB_DISPATCH_T(c->dtype, hipLaunchKernelGGL((dot_kernel<T>), dim3(grid, s), dim3(256), 0, c->stream, (const T*)a,
                                                  (const T*)b, n, c->dotpart));
     CGLB_LAUNCH_CHECK(c);
-    hipLaunchKernelGGL(finalize_sum_kernel2, dim3(1), dim3(256), 0, c->stream, (const double*)c->dotpart, grid, out_slot, 1.0);
+    hipLaunchKernelGGL(finalize_sum_kernel2, dim3(s), dim3(256), 0, c->stream, (const double*)c->dotpart, grid, out_slots, 1.0);
     CGLB_LAUNCH_CHECK(c);
     return CGLB_OK;
 }
@@ -47,19 +56,21 @@ template <typename T>
 __global__ __launch_bounds__(256) void update_v_r_kernel(T* __restrict__ v, T* __restrict__ r, const T* __restrict__ p,
                                                          const T* __restrict__ Ap, int64_t n, const double* __restrict__ rz,
                                                          const double* __restrict__ pAp, int update_r) {
-    const T gamma = (T)(rz[0] / pAp[0]);
+    const int64_t off = (int64_t)blockIdx.y * n;
+    const double den = pAp[blockIdx.y];
+    const T gamma = den == 0.0 ? T(0) : (T)(rz[blockIdx.y] / den);
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        v[i] = tfma<T>(gamma, p[i], v[i]);
-        if (update_r) r[i] = tfma<T>(-gamma, Ap[i], r[i]);
+        v[off + i] = tfma<T>(gamma, p[off + i], v[off + i]);
+        if (update_r) r[off + i] = tfma<T>(-gamma, Ap[off + i], r[off + i]);
     }
 }
 
 int launch_update_v_r(cglb_ctx* c, void* v, void* r, const void* p, const void* Ap, const double* rz, const double* pAp,
-                      int update_r, int64_t n) {
+                      int update_r, int64_t n, int s) {
     if (n < 0) n = c->nloc;
     if (n == 0) return CGLB_OK;
     const int grid = vec_grid(n, 256);
-    CGLB_DISPATCH_T(c->dtype, hipLaunchKernelGGL((update_v_r_kernel<T>), dim3(grid), dim3(256), 0, c->stream, (T*)v, (T*)r,
+    CGLB_DISPATCH_T(c->dtype, hipLaunchKernelGGL((update_v_r_kernel<T>), dim3(grid, s), dim3(256), 0, c->stream, (T*)v, (T*)r,
                                                  (const T*)p, (const T*)Ap, n, rz, pAp, update_r));
     CGLB_LAUNCH_CHECK(c);
     return CGLB_OK;
@@ -83,16 +94,18 @@ int launch_residual(cglb_ctx* c, void* r, const void* b, const void* Kv, int64_t
 }
 
 // ---- p = z + p * new_rz / rz  (or p = z on restart) --------------------------------------------------------
-// wh != null (RBF, unclamped range): the pre-weighted operand pw = p * wh of the symmetric pair kernel (folded column norm,
-// kernels_kff_sym.hip) is written in the same pass, so the next mat-vec needs no separate weighting launch.
+// wh != null (RBF, unclamped range; one column only): the pre-weighted operand pw = p * wh of the symmetric pair kernel (folded column
+// norm, kernels_kff_sym.hip) is written in the same pass, so the next mat-vec needs no separate weighting launch.
 template <typename T>
 __global__ __launch_bounds__(256) void update_p_kernel(T* __restrict__ p, const T* __restrict__ z, int64_t n,
                                                        const double* __restrict__ new_rz, const double* __restrict__ rz, int restart,
                                                        const T* __restrict__ wh, T* __restrict__ pw) {
-    const T beta = restart ? T(0) : (T)(new_rz[0] / rz[0]);
+    const int64_t off = (int64_t)blockIdx.y * n;
+    const double den = rz[blockIdx.y];
+    const T beta = (restart || den == 0.0) ? T(0) : (T)(new_rz[blockIdx.y] / den);
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        const T pi = restart ? z[i] : tfma<T>(beta, p[i], z[i]);
-        p[i] = pi;
+        const T pi = restart ? z[off + i] : tfma<T>(beta, p[off + i], z[off + i]);
+        p[off + i] = pi;
         if (wh) pw[i] = pi * wh[i];
     }
 }
@@ -104,13 +117,13 @@ static inline bool fuse_weights(const cglb_ctx* c, int64_t n) {
 
 // fuse: also write the weighted copy for the NEXT symmetric mat-vec of p.  Only for callers that own the loop (the fused PCG and the
 // segmented multi-GPU update): the copy is valid only while p is not modified before that mat-vec, which a caller of the generic
-// cglb_vec_update_p / cglb_shard_update_p entry points has not promised.
-int launch_update_p(cglb_ctx* c, void* p, const void* z, const double* new_rz, const double* rz, int restart, int64_t n, bool fuse) {
+// cglb_vec_update_p / cglb_shard_update_p entry points has not promised.  There is one weighted copy, so s > 1 never fuses.
+int launch_update_p(cglb_ctx* c, void* p, const void* z, const double* new_rz, const double* rz, int restart, int64_t n, bool fuse, int s) {
     if (n < 0) n = c->nloc;
     if (n == 0) return CGLB_OK;
     const int grid = vec_grid(n, 256);
-    const bool fw = fuse && fuse_weights(c, n);
-    CGLB_DISPATCH_T(c->dtype, hipLaunchKernelGGL((update_p_kernel<T>), dim3(grid), dim3(256), 0, c->stream, (T*)p, (const T*)z,
+    const bool fw = fuse && s == 1 && fuse_weights(c, n);
+    CGLB_DISPATCH_T(c->dtype, hipLaunchKernelGGL((update_p_kernel<T>), dim3(grid, s), dim3(256), 0, c->stream, (T*)p, (const T*)z,
                                                  n, new_rz, rz, restart, fw ? (const T*)c->wh : (const T*)nullptr, (T*)c->pwh));
     CGLB_LAUNCH_CHECK(c);
     c->pwh_src = fw ? p : nullptr;  // consumed (and cleared) by the next symmetric mat-vec of exactly this vector
@@ -147,71 +160,6 @@ int launch_update_p_seg(cglb_ctx* c, void* p, const void* zseg, int64_t n, int64
                                                  world, new_rz_out, rz, restart, fw ? (const T*)c->wh : (const T*)nullptr, (T*)c->pwh));
     CGLB_LAUNCH_CHECK(c);
     c->pwh_src = fw ? p : nullptr;
-    return CGLB_OK;
-}
-
-// ---- the same three primitives for s independent recurrences in lockstep (cglb_pcg_solve_multi): blockIdx.y = column ----------------
-// gamma_b = rz_b / pAp_b and beta_b = new_rz_b / rz_b; a zero denominator (a column that has converged exactly, or an all-zero
-// right-hand side) gives a zero factor, so that column stays where it is and stays finite.
-template <typename T>
-__global__ __launch_bounds__(256) void dot_multi_kernel(const T* __restrict__ a, const T* __restrict__ b, int64_t n, double* __restrict__ dotpart) {
-    __shared__ double smem[16];
-    const T* __restrict__ ab = a + (int64_t)blockIdx.y * n;
-    const T* __restrict__ bb = b + (int64_t)blockIdx.y * n;
-    double s = 0.0;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) s += (double)ab[i] * (double)bb[i];
-    s = block_sum(s, smem);
-    if (threadIdx.x == 0) dotpart[(int64_t)blockIdx.y * gridDim.x + blockIdx.x] = s;
-}
-__global__ __launch_bounds__(256) void finalize_sum_multi_kernel(const double* __restrict__ partials, int n, double* __restrict__ out) {
-    __shared__ double smem[16];
-    double s = 0.0;
-    for (int i = threadIdx.x; i < n; i += blockDim.x) s += partials[(int64_t)blockIdx.x * n + i];
-    s = block_sum(s, smem);
-    if (threadIdx.x == 0) out[blockIdx.x] = s;
-}
-int launch_dot_multi(cglb_ctx* c, const void* a, const void* b, int64_t n, int s, double* out_slots) {
-    int grid = vec_grid(n);
-    if (grid > DOTPART_CAP / s) grid = DOTPART_CAP / s;
-    if (grid < 1) return cglb_fail(c, CGLB_ERR_BAD_ARG, "too many columns for the dot partials");
-    CGLB_DISPATCH_T(c->dtype, hipLaunchKernelGGL((dot_multi_kernel<T>), dim3(grid, s), dim3(256), 0, c->stream, (const T*)a, (const T*)b, n, c->dotpart));
-    CGLB_LAUNCH_CHECK(c);
-    hipLaunchKernelGGL(finalize_sum_multi_kernel, dim3(s), dim3(256), 0, c->stream, (const double*)c->dotpart, grid, out_slots);
-    CGLB_LAUNCH_CHECK(c);
-    return CGLB_OK;
-}
-
-template <typename T>
-__global__ __launch_bounds__(256) void update_v_r_multi_kernel(T* __restrict__ v, T* __restrict__ r, const T* __restrict__ p, const T* __restrict__ Ap, int64_t n,
-                                                               const double* __restrict__ rz, const double* __restrict__ pAp, int update_r) {
-    const int64_t off = (int64_t)blockIdx.y * n;
-    const double den = pAp[blockIdx.y];
-    const T gamma = den == 0.0 ? T(0) : (T)(rz[blockIdx.y] / den);
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        v[off + i] = tfma<T>(gamma, p[off + i], v[off + i]);
-        if (update_r) r[off + i] = tfma<T>(-gamma, Ap[off + i], r[off + i]);
-    }
-}
-int launch_update_v_r_multi(cglb_ctx* c, void* v, void* r, const void* p, const void* Ap, const double* rz, const double* pAp, int update_r, int64_t n, int s) {
-    CGLB_DISPATCH_T(c->dtype, hipLaunchKernelGGL((update_v_r_multi_kernel<T>), dim3(vec_grid(n, 256), s), dim3(256), 0, c->stream, (T*)v, (T*)r, (const T*)p,
-                                                 (const T*)Ap, n, rz, pAp, update_r));
-    CGLB_LAUNCH_CHECK(c);
-    return CGLB_OK;
-}
-
-template <typename T>
-__global__ __launch_bounds__(256) void update_p_multi_kernel(T* __restrict__ p, const T* __restrict__ z, int64_t n, const double* __restrict__ new_rz,
-                                                             const double* __restrict__ rz, int restart) {
-    const int64_t off = (int64_t)blockIdx.y * n;
-    const double den = rz[blockIdx.y];
-    const T beta = (restart || den == 0.0) ? T(0) : (T)(new_rz[blockIdx.y] / den);
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
-        p[off + i] = restart ? z[off + i] : tfma<T>(beta, p[off + i], z[off + i]);
-}
-int launch_update_p_multi(cglb_ctx* c, void* p, const void* z, const double* new_rz, const double* rz, int restart, int64_t n, int s) {
-    CGLB_DISPATCH_T(c->dtype, hipLaunchKernelGGL((update_p_multi_kernel<T>), dim3(vec_grid(n, 256), s), dim3(256), 0, c->stream, (T*)p, (const T*)z, n, new_rz,
-                                                 rz, restart));
-    CGLB_LAUNCH_CHECK(c);
     return CGLB_OK;
 }
 

@@ -212,35 +212,27 @@ class HipContext:
         _lib.check(self.lib.cglb_time_matmat(self._ctx, int(s), int(reps), byref(ms)), self._ctx)
         return ms.value
 
-    def _objective_and_grad_multi(self, v_inout, run_cg, max_error, max_cg_iter, restart_cg_iter, with_grad) -> ObjectiveResult:
-        if v_inout.device != self.device or v_inout.dtype != self.dtype or tuple(v_inout.shape) != (self.N, self.P):
-            raise ValueError("v_inout must be a device tensor of shape [N, P] in the context dtype")
-        Vt = v_inout.t().contiguous()
-        out4 = (c_double * 4)()
-        g = np.empty(grad_len(self.D, self.M), dtype=np.float64) if with_grad else None
-        steps, half = c_int(), c_double()
-        rc = self.lib.cglb_objective_and_grad_multi(
-            self._ctx, _ptr(Vt), int(bool(run_cg)), float(max_error), int(max_cg_iter), int(restart_cg_iter), out4,
-            g.ctypes.data_as(ctypes.POINTER(c_double)) if with_grad else None, byref(steps), byref(half))
-        _lib.check(rc, self._ctx)
-        if run_cg:
-            v_inout.copy_(Vt.t())  # the persistent warm start, in the caller's layout
-        return ObjectiveResult(out4[0], out4[1], out4[2], out4[3], steps.value, half.value, self.unpack_grad(g) if with_grad else None)
-
     def objective_and_grad(self, v_inout: torch.Tensor, run_cg=True, max_error=1.0, max_cg_iter=100, restart_cg_iter=40,
                            with_grad=True) -> ObjectiveResult:
         """v_inout (device, length N; [N, P] for P > 1 target columns) is the persistent warm-start vector: updated in place when run_cg."""
+        if v_inout.device != self.device or v_inout.dtype != self.dtype:
+            raise ValueError("v_inout must be a device tensor in the context dtype")
         if self.P > 1:
-            return self._objective_and_grad_multi(v_inout, run_cg, max_error, max_cg_iter, restart_cg_iter, with_grad)
-        if v_inout.device != self.device or v_inout.dtype != self.dtype or v_inout.numel() != self.N or not v_inout.is_contiguous():
-            raise ValueError("v_inout must be a contiguous device vector of length N in the context dtype")
+            if tuple(v_inout.shape) != (self.N, self.P):
+                raise ValueError("v_inout must be a device tensor of shape [N, P] in the context dtype")
+            v, entry = v_inout.t().contiguous(), self.lib.cglb_objective_and_grad_multi  # the library's layout: column b contiguous
+        else:
+            if v_inout.numel() != self.N or not v_inout.is_contiguous():
+                raise ValueError("v_inout must be a contiguous device vector of length N in the context dtype")
+            v, entry = v_inout, self.lib.cglb_objective_and_grad
         out4 = (c_double * 4)()
         g = np.empty(grad_len(self.D, self.M), dtype=np.float64) if with_grad else None
         steps, half = c_int(), c_double()
-        rc = self.lib.cglb_objective_and_grad(
-            self._ctx, _ptr(v_inout), int(bool(run_cg)), float(max_error), int(max_cg_iter), int(restart_cg_iter), out4,
-            g.ctypes.data_as(ctypes.POINTER(c_double)) if with_grad else None, byref(steps), byref(half))
+        rc = entry(self._ctx, _ptr(v), int(bool(run_cg)), float(max_error), int(max_cg_iter), int(restart_cg_iter), out4,
+                   g.ctypes.data_as(ctypes.POINTER(c_double)) if with_grad else None, byref(steps), byref(half))
         _lib.check(rc, self._ctx)
+        if self.P > 1 and run_cg:
+            v_inout.copy_(v.t())  # the persistent warm start, in the caller's layout
         return ObjectiveResult(out4[0], out4[1], out4[2], out4[3], steps.value, half.value, self.unpack_grad(g) if with_grad else None)
 
     def objective_grad_v(self) -> torch.Tensor:

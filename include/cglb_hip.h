@@ -269,8 +269,10 @@ int cglb_time_kernel(cglb_ctx* ctx, int which, int reps, double* ms_avg);
  * "k1_pairs_per_launch": kernel pairs one launch of that kernel evaluates with the current geometry (~N(N+256)/2 on one GPU: the
  * symmetric form visits each unordered pair once) - the unit count of the roofline; "kpart_bytes": size of the partial-sum slabs;
  * after cglb_set_option(ctx, "eval_profile", 1): "eval_setup_ms" | "eval_pcg_ms" | "eval_final_ms" | "eval_grad_ms" = device time (HIP events on
- * the context stream) accumulated over the phases of every cglb_objective_and_grad since - common terms | PCG | final mat-vec, preconditioner
- * and bound scalars | gradient - and "eval_count" = the number of evaluations;
+ * the context stream) accumulated over the phases of every cglb_objective_and_grad / cglb_dist_objective_and_grad /
+ * cglb_objective_and_grad_multi since - common terms | PCG | final mat-vec, preconditioner and bound scalars | gradient - and "eval_count" =
+ * the number of evaluations.  With p > 1 columns the third phase is K v alone and the fourth holds the column-by-column rest (preconditioner,
+ * bound scalars and gradient of each column in turn);
  * "comm_allreduce_calls" | "comm_allgather_calls": collectives issued by the library since cglb_comm_init_*;
  * "L_diag_ratio": max/min of diag(chol(K_uu + jitter I)) of the last cglb_setup (a cheap proxy of cond(L)). */
 int cglb_get_stat(cglb_ctx* ctx, const char* name, double* value);

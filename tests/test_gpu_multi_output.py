@@ -198,6 +198,84 @@ def test_pcg_multi_column_equal_to_the_mean():
     ctx.close()
 
 
+def test_single_and_multi_solves_share_one_context():
+    """pcg, pcg_multi (P = 3), pcg again, then a one-column evaluation on ONE context: the one loop keeps the scalar slots, the host mirror
+    and the weighted-operand state of each column count apart, so the third call repeats the first and the evaluation that of a fresh context."""
+    X, Y, hyp, cov, Vref, steps, half = solve_case("rbf", 3)
+    y = np.ascontiguousarray(Y[:, 0])
+    b1, z1 = torch.from_numpy(y - hyp.mean), torch.zeros(len(y), dtype=torch.float64)
+
+    def evaluate(ctx):
+        v = torch.zeros(len(y), dtype=torch.float64, device=ctx.device)
+        res = ctx.objective_and_grad(v, True)
+        return (v.cpu().numpy().tobytes(), res.steps, res.residual_error, res.bound, res.lower, res.upper, res.logdet) + \
+            tuple(np.asarray(res.grad[k]).tobytes() for k in mref.GRAD_KEYS)
+
+    ctx = make_ctx("rbf", X, y, hyp, sym_chunk=16)
+    ctx.setup()
+    v1, s1, h1 = ctx.pcg(b1, z1, 1e-3)
+    assert s1 > 0
+    V, sm, total, cols = ctx.pcg_multi(torch.from_numpy(Y - hyp.mean), torch.zeros(Y.shape, dtype=torch.float64))
+    assert sm == steps
+    v3, s3, h3 = ctx.pcg(b1, z1, 1e-3)
+    assert (s3, h3) == (s1, h1) and v3.cpu().numpy().tobytes() == v1.cpu().numpy().tobytes()
+    shared = evaluate(ctx)
+    ctx.close()
+    fresh_ctx = make_ctx("rbf", X, y, hyp, sym_chunk=16)
+    fresh = evaluate(fresh_ctx)
+    fresh_ctx.close()
+    assert shared == fresh
+
+
+def test_pcg_multi_lookahead_is_bitwise_neutral():
+    """The multi-column twin of test_lookahead_stop_test_does_not_change_results (tests/test_gpu_edge_cases.py): a speculative mat-mat product
+    only writes Ap and the p.Ap slots, so V, the steps and the per-column statistics do not depend on the look-ahead rule."""
+    X, Y, hyp, cov, Vref, steps, half = solve_case("rbf", 2)
+    outs = []
+    for la in (0, 1, 2, 8):
+        ctx = make_ctx("rbf", X, Y, hyp, sym_chunk=16, pcg_lookahead=la)
+        ctx.setup()
+        V, st, total, cols = ctx.pcg_multi(torch.from_numpy(Y - hyp.mean), torch.zeros(Y.shape, dtype=torch.float64), max_error=1e-6)
+        outs.append((V.cpu().numpy().tobytes(), st, total, cols.tobytes()))
+        ctx.close()
+    print("steps", outs[0][1], "total", outs[0][2])
+    assert outs[0][1] > steps >= 1          # tighter than the default tolerance: several steps
+    for other in outs[1:]:
+        assert other == outs[0]
+
+
+def test_eval_profile_counts_multi_column_evaluations():
+    """eval_profile counts and times the evaluations of P > 1 columns like the one-column ones, and one that fails after its first mark
+    leaves no marks behind (tests/test_gpu_edge_cases.py has the one-column form).  The failing evaluation: a context that holds two
+    columns refuses set_option("logdet_bound", 1) itself (asserted below), so require_multi_ok's refusal cannot be reached through the
+    options; a singular K_uu without jitter makes cglb_setup fail inside the evaluation instead, after the first mark."""
+    X, Y, hyp, cov, Vref, steps, half = solve_case("rbf", 2)
+    ctx = make_ctx("rbf", X, Y, hyp, sym_chunk=16)
+    ctx.set_option("eval_profile", 1)
+    stats = ("eval_setup_ms", "eval_pcg_ms", "eval_final_ms", "eval_grad_ms")
+    for _ in range(2):
+        res = ctx.objective_and_grad(torch.zeros(Y.shape, dtype=torch.float64, device=ctx.device), True)
+        assert np.isfinite(res.bound)
+    ms = [ctx.get_stat(k) for k in stats]
+    print("eval_count", ctx.get_stat("eval_count"), "eval_*_ms", ms)
+    assert ctx.get_stat("eval_count") == 2
+    assert all(np.isfinite(t) and t >= 0.0 for t in ms)
+    with pytest.raises(ValueError, match="more than one target column"):
+        ctx.set_option("logdet_bound", 1)
+    Zdup = hyp.Z.copy()
+    Zdup[1] = Zdup[0]
+    ctx.set_hypers(np.ones(3), 1.0, 0.1, 0.0, Zdup, 0.0)     # k(z, z) = 1 exactly: the second pivot is an exact zero (as in test_error_mapping)
+    with pytest.raises(RuntimeError, match="[Cc]holesky"):
+        ctx.objective_and_grad(torch.zeros(Y.shape, dtype=torch.float64, device=ctx.device), True)
+    ctx.set_hypers(hyp.lengthscales, hyp.variance, hyp.noise, hyp.mean, hyp.Z, hyp.jitter)
+    res = ctx.objective_and_grad(torch.zeros(Y.shape, dtype=torch.float64, device=ctx.device), True)
+    assert np.isfinite(res.bound)
+    ms = [ctx.get_stat(k) for k in stats]
+    assert ctx.get_stat("eval_count") == 3
+    assert all(np.isfinite(t) and t >= 0.0 for t in ms)
+    ctx.close()
+
+
 @pytest.mark.parametrize("P", [2, 3])
 @pytest.mark.parametrize("kind", KINDS)
 def test_evaluation_at_given_v_and_after_solve(kind, P):

@@ -5,7 +5,8 @@ cglb_time_matmat for S in {2, 4, 8}, and a cold cglb_objective_and_grad_multi at
 the median of `--rounds` rounds of `--reps` back-to-back launches after a warm-up round (HIP events on the context stream); min and max
 of the rounds are kept as the spread.  The instruction model (18 + 3 S) / (21 S) is printed next to every measured ratio.
 
-    python tools/time_matmat.py [--n 100000] [--d 8] [--m 1024] [--reps 10] [--rounds 7] [--out profiles/multi_rhs_timing.json]"""
+    python tools/time_matmat.py [--n 100000] [--d 8] [--m 1024] [--reps 10] [--rounds 7] [--columns 2 4 8] [--no-eval]
+                                 [--out profiles/multi_rhs_timing.json]"""
 import argparse
 import json
 import os
@@ -47,6 +48,8 @@ def main():
     ap.add_argument("--m", type=int, default=1024)
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--rounds", type=int, default=7)
+    ap.add_argument("--columns", type=int, nargs="+", default=[2, 4, 8], help="column counts S of cglb_time_matmat")
+    ap.add_argument("--no-eval", action="store_true", help="products only: skip the evaluations at P = 4")
     ap.add_argument("--out", default=os.path.join("profiles", "multi_rhs_timing.json"))
     a = ap.parse_args()
     X, Y, Z = synthetic_problem(a.n, a.d, a.m, seed=0, P=4)
@@ -57,7 +60,7 @@ def main():
         ctx.set_hypers(hyp["lengthscales"], hyp["variance"], hyp["noise"], hyp["mean"], Z)
         rec = dict(matvec_ms=rounds_of(lambda: ctx.time_kernel(0, a.reps), a.rounds), matmat_ms={}, ratio_to_S_matvecs={}, model={})
         t1 = rec["matvec_ms"]["median"]
-        for S in (2, 4, 8):
+        for S in a.columns:
             r = rounds_of(lambda: ctx.time_matmat(S, a.reps), a.rounds)
             rec["matmat_ms"][str(S)] = r
             rec["ratio_to_S_matvecs"][str(S)] = r["median"] / (S * t1)
@@ -65,15 +68,16 @@ def main():
             print(f"{kind} S={S}: matmat {r['median']:.3f} ms ({r['min']:.3f}..{r['max']:.3f}), {S} x matvec {S * t1:.3f} ms, "
                   f"ratio {rec['ratio_to_S_matvecs'][str(S)]:.3f} (model {rec['model'][str(S)]:.3f})", flush=True)
         singles = []
-        for b in range(4):
+        for b in range(0 if a.no_eval else 4):
             ctx.set_targets(torch.from_numpy(Y[:, b].copy()))
             singles.append(evaluation_ms(ctx, (a.n,)))
-        ctx.set_targets(torch.from_numpy(Y))
-        rec["eval_single_ms"] = singles
-        rec["eval_multi_p4_ms"] = evaluation_ms(ctx, (a.n, 4))
-        rec["eval_ratio_to_4_singles"] = rec["eval_multi_p4_ms"]["median"] / sum(s["median"] for s in singles)
-        print(f"{kind} evaluation P=4: {rec['eval_multi_p4_ms']['median']:.1f} ms ({rec['eval_multi_p4_ms']['steps']} steps) against "
-              f"{sum(s['median'] for s in singles):.1f} ms for four single evaluations ({[s['steps'] for s in singles]} steps)", flush=True)
+        if not a.no_eval:
+            ctx.set_targets(torch.from_numpy(Y))
+            rec["eval_single_ms"] = singles
+            rec["eval_multi_p4_ms"] = evaluation_ms(ctx, (a.n, 4))
+            rec["eval_ratio_to_4_singles"] = rec["eval_multi_p4_ms"]["median"] / sum(s["median"] for s in singles)
+            print(f"{kind} evaluation P=4: {rec['eval_multi_p4_ms']['median']:.1f} ms ({rec['eval_multi_p4_ms']['steps']} steps) against "
+                  f"{sum(s['median'] for s in singles):.1f} ms for four single evaluations ({[s['steps'] for s in singles]} steps)", flush=True)
         out["kernels"][kind] = rec
         ctx.close()
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
