@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "../../include/cglb_hip.h"
+#include "pair_worklist.h"
 
 #define CGLB_MAX_D 1024        // widest input the context accepts (host-side arrays)
 #define CGLB_MAX_D_NARROW 32   // widest input of the register-resident pair kernels; beyond it the "wide" path runs (kernels_wide.hip)
@@ -122,8 +123,8 @@ struct cglb_ctx {
     void *fragA = nullptr, *fragB = nullptr;  // MFMA-ordered augmented operands (kernels_kff_mfma.hip)
     size_t fragA_cap = 0, fragB_cap = 0;
     bool frag_valid = false;  // fragA / fragB (operands of the experimental matrix-pipe variant) match the current hypers
-    void* sym_items = nullptr;       // work list (row block, column chunk) of the symmetric mat-vec
-    int64_t sym_n = -1, sym_chunk = 0, sym_chunk_opt = 0;
+    pair_list sym_list;              // work list (row block, column chunk) of the symmetric mat-vec (kernels_kff_sym.hip: ensure_sym_items)
+    int64_t sym_chunk_opt = 0;
     double sym_pairs = 0.0;          // kernel pairs one launch of the symmetric pair kernel evaluates (current item list)
     // in-situ timing of the dominant kernel (cglb_set_option "k1_profile", cglb_get_stat): HIP event pairs around every launch of the
     // symmetric pair kernel on the context stream, resolved lazily
@@ -141,8 +142,7 @@ struct cglb_ctx {
     long long eval_count = 0;
     int grad_gram = 1;    // 1: Gram-form symmetric gradient pass (moments), 0: direct differences
     int aat_block = 512;  // block width of the lower-triangle-only split-K A A^T (0 or not dividing M: the full square)
-    int sym_order = 1, sym_order_built = -1;  // item order of the symmetric kernel: 0 row-block major, 1 XCD-aware (kernels_kff_sym.hip)
-    int sym_rbrows = 0, sym_nitems = 0, sym_world = 1, sym_rank = 0;
+    int sym_order = 1;  // item order of the symmetric kernels: 0 row-block major, 1 XCD-aware (pair_worklist.h)
     int par_world = 1, par_rank = 0;  // cyclic distribution of the symmetric K_ff work over ranks (cglb_set_parallel)
     void* slabs = nullptr;   // split-K partial A A^T slabs [nslab][M][M]
     size_t slab_cap = 0;
@@ -185,9 +185,7 @@ struct cglb_ctx {
     double* mhost = nullptr; // [s] pinned host mirror of one row of mscal (what host_scal is to one column: pcg_ops::host)
     int mhost_cap = 0;
     double* mgrad = nullptr; // [GRAD_LEN] device sum of the per-column gradients
-    void* mm_items = nullptr;   // work list (group of four row blocks, column span) of the multi-column pair kernel
-    int64_t mm_n = -1, mm_span = 0;
-    int mm_rbrows = 0, mm_nwg = 0, mm_order_built = -1;
+    pair_list mm_list;          // work list (group of four row blocks, column span) of the multi-column pair kernel
     void* mm_part = nullptr;    // its partial-sum slabs
     size_t mm_part_cap = 0;
     void* mm_vi = nullptr;      // [N][8] interleaved (and pre-weighted) column-side operand

@@ -8,8 +8,7 @@
 //   delta_d = (x1_d - x2_d)/l_d,  h = kappa (RBF) | 3 exp(-sqrt3 r) (Matern-3/2).
 // Operands are the scaled ones of K1 (xs = (x-c)/l*kscale); the 1/(l_d kscale^2) factors are applied
 // in the finalize kernels.
-#include "devmath.h"
-#include "dispatch.h"
+#include "pair_common.h"
 
 // ---- N^2 pass ---------------------------------------------------------------------------------------
 // Thread owns R rows; the column operand (xs_j, v_j, u_j) is wave-uniform (scalar loads).
@@ -146,7 +145,6 @@ __global__ __launch_bounds__(256) void grad_kff_kernel(const T* __restrict__ XsR
 #ifndef CGLB_GRAM_W3_DP
 #define CGLB_GRAM_W3_DP 28  // padded width whose instance is pinned to 3 waves per SIMD (175 VGPRs unpinned: 2 waves; pinned 28 B of scratch: 7.26 -> 5.62 ms at N = 60k; the same at width 32 costs 130 B of scratch: 7.4 -> 8.5 ms)
 #endif
-#define GRAD_TR_LD 65  // leading dimension of a wave's 8 x 64 transposition scratch (odd: the column reads spread over the banks)
 template <typename T, int KIND, int DP, int R, int PREC, bool CLAMP>
 __global__ __launch_bounds__(256, (DP == CGLB_GRAM_W3_DP ? 3 : 1)) void grad_kff_gram_kernel(const T* __restrict__ Xh, const T* __restrict__ Xhsq, const T* __restrict__ ah,
                                                             const T* __restrict__ u, const T* __restrict__ v, const T* __restrict__ uc,
@@ -158,13 +156,13 @@ __global__ __launch_bounds__(256, (DP == CGLB_GRAM_W3_DP ? 3 : 1)) void grad_kff
     load_exp_table(tab, exp_tab);
     // RBF, unclamped range: folded column norm as in the symmetric mat-vec - h_ij = 2^(a_i + x_i.x_j) w_j with w_j = 2^(a_j) carried by the
     // column-side copies uc = u o w, vc = v o w of the two vectors (the row side uses u, v themselves), so the per-pair add of a_j is dropped
-    constexpr bool FOLD = (KIND == CGLB_RBF) && !CLAMP && sizeof(T) == 8;
+    constexpr bool FOLD = pair_fold<KIND, CLAMP>() && sizeof(T) == 8;  // the gradient pass folds for fp64 only
     // Matern-3/2, fast level, unclamped range: positivity bias in the row seeds instead of a clamp per pair (devmath.h CGLB_M32_BIAS_*)
-    constexpr bool BIASED = (KIND != CGLB_RBF) && !CLAMP && PREC != CGLB_PREC_EXACT && sizeof(T) == 8;
+    constexpr bool BIASED = pair_biased<T, KIND, CLAMP, PREC>();
     const int64_t rblock = ((int64_t)blockIdx.x * rb_stride + rb_offset) * (256 * R);  // cyclic over ranks when rb_stride > 1
     const int64_t rbase = rblock + threadIdx.x;
-    __shared__ T trbuf[4 * 8 * GRAD_TR_LD];
-    T* __restrict__ tr = trbuf + (threadIdx.x >> 6) * (8 * GRAD_TR_LD);
+    __shared__ T trbuf[4 * 8 * PAIR_TR_LD];
+    T* __restrict__ tr = trbuf + (threadIdx.x >> 6) * (8 * PAIR_TR_LD);
     const int lane = threadIdx.x & 63;
     // second moments: through column sums (COLSUM, below) or, for D <= 4 where that costs more than it saves, per lane with the R rows
     // sharing one accumulator set (S2 enters only through its sum over rows)
@@ -183,8 +181,7 @@ __global__ __launch_bounds__(256, (DP == CGLB_GRAM_W3_DP ? 3 : 1)) void grad_kff
             S1[k][d] = 0;
         }
         S0[k] = 0;
-        const T a = ah[row0 + rr];
-        aseed[k] = (KIND == CGLB_RBF) ? a : (BIASED ? T(-0.5) * (a + bias) : T(-0.5) * a);
+        aseed[k] = pair_row_seed<T, KIND, BIASED>(ah[row0 + rr], bias);
         // padded rows carry zero weight; Matern-3/2: h = 3 * 2^(-r), the factor 3 rides in the row weights
         const T hscale = (KIND == CGLB_RBF) ? T(1) : T(3);
         ui[k] = row < n ? hscale * u[row0 + rr] : T(0);
@@ -239,12 +236,12 @@ __global__ __launch_bounds__(256, (DP == CGLB_GRAM_W3_DP ? 3 : 1)) void grad_kff
         // Second moments.  sum_ij hv_ij x_jd^2 = sum_j x_jd^2 (sum_i hv_ij): only the COLUMN sums of the pair weights are needed,
         // so the per-pair accumulation S2_d += hv x_jd^2 (D fma per pair and D more scalar operands per column - at D = 24 / 32 they
         // no longer fit the SGPR file: 64 v_readlane/v_writelane per column, a 3.8x slower kernel) is replaced by one transposition
-        // of the 8 partials through LDS per batch (as in the symmetric mat-vec: lane (c, g) adds 8 lanes of column c, three
-        // xor-shuffles finish the wave's column sum) and NQ fma per lane: lane (c, g) weights x_{jb+c, d}^2 for d = g, g + 8, ...
+        // of the 8 partials through LDS per batch (wave_colsum8 of pair_common.h, written out: calling it moves the DP = 28 instances by up
+        // to 6 VGPRs; lane (c, g) holds the sum of column c) and NQ fma per lane: lane (c, g) weights x_{jb+c, d}^2 for d = g, g + 8, ...
 #pragma unroll
-        for (int jj = 0; jj < 8; ++jj) tr[jj * GRAD_TR_LD + lane] = t[jj];
+        for (int jj = 0; jj < 8; ++jj) tr[jj * PAIR_TR_LD + lane] = t[jj];
         __builtin_amdgcn_wave_barrier();
-        const T* __restrict__ src = tr + (lane & 7) * GRAD_TR_LD + (lane & ~7);
+        const T* __restrict__ src = tr + (lane & 7) * PAIR_TR_LD + (lane & ~7);
         T cs = src[0];
 #pragma unroll
         for (int i = 1; i < 8; ++i) cs += src[i];

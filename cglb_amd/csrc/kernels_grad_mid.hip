@@ -1,9 +1,6 @@
 // K5, mid widths (32 < D <= 96, fp64): the symmetric Gram-form N^2 pass of kernels_grad.hip with a matrix row shared by two (four) lanes
 // and the column operands broadcast across lanes.  A translation unit of its own: its instances build in parallel with the narrow ones.
-#include "devmath.h"
-#include "dispatch.h"
-
-#define GRAD_TR_LD 65  // leading dimension of a wave's 8 x 64 transposition scratch (as in kernels_grad.hip)
+#include "pair_common.h"
 
 // Mid-width form of the symmetric Gram-form pass (32 < D <= 96, fp64; cglb_internal.h: mid_dim).  A row's operand and its first moments
 // no longer fit one lane (4 DP registers), so a matrix row is shared by SPLIT lanes (lane l of each half of the wave, SPLIT = 2; of each
@@ -23,11 +20,10 @@ __global__ __launch_bounds__(256, 2) void grad_kff_mid_kernel(const double* __re
     using T = double;
     constexpr int HD = DP / SPLIT, CH = 8, NCH = HD / CH, NQ = (DP + 7) / 8, WROWS = 64 / SPLIT;
     static_assert((SPLIT == 2 || SPLIT == 4) && HD % CH == 0, "part width must be a multiple of 8");
-    constexpr bool FOLD = (KIND == CGLB_RBF) && !CLAMP;
-    constexpr bool BIASED = (KIND != CGLB_RBF) && !CLAMP && PREC != CGLB_PREC_EXACT;
+    constexpr bool FOLD = pair_fold<KIND, CLAMP>(), BIASED = pair_biased<T, KIND, CLAMP, PREC>();
     __shared__ double smem[16];
     __shared__ double tab[CGLB_TAB_SIZE];
-    __shared__ T trbuf[4 * 8 * GRAD_TR_LD];
+    __shared__ T trbuf[4 * 8 * PAIR_TR_LD];
     // DP = 96 with a row shared by two lanes needs 265 registers with the second-moment accumulators in VGPRs - one wave per SIMD; kept in
     // LDS instead (a private column of 12 slots per lane: no conflicts, no barrier; 36 LDS operations per batch of 8 columns) it fits 2 waves
     constexpr bool G2LDS = (DP > 80 && SPLIT == 2);
@@ -35,7 +31,7 @@ __global__ __launch_bounds__(256, 2) void grad_kff_mid_kernel(const double* __re
     load_exp_table(tab, exp_tab);
     const int lane = threadIdx.x & 63, prt = lane / WROWS, l8 = lane & 7;   // prt: which 1 / SPLIT of the dimensions this lane holds
     T* __restrict__ g2 = g2buf + (G2LDS ? (threadIdx.x >> 6) * (NQ * 64) + lane : 0);
-    T* __restrict__ tr = trbuf + (threadIdx.x >> 6) * (8 * GRAD_TR_LD);
+    T* __restrict__ tr = trbuf + (threadIdx.x >> 6) * (8 * PAIR_TR_LD);
     const int64_t rblock = ((int64_t)blockIdx.x * rb_stride + rb_offset) * (4 * WROWS);
     const int64_t row = rblock + (threadIdx.x >> 6) * WROWS + (lane & (WROWS - 1));
     const int64_t rr = row < n ? row : n - 1;
@@ -52,7 +48,8 @@ __global__ __launch_bounds__(256, 2) void grad_kff_mid_kernel(const double* __re
     }
     T S0 = 0;
     const T a = ah[rr];
-    const T aseed = prt ? T(0) : ((KIND == CGLB_RBF) ? a : (BIASED ? T(-0.5) * (a + bias) : T(-0.5) * a));  // the seed enters the sum of the parts once
+    // pair_row_seed of pair_common.h, written out (calling it here reschedules every instance); the seed enters the sum of the parts once
+    const T aseed = prt ? T(0) : ((KIND == CGLB_RBF) ? a : (BIASED ? T(-0.5) * (a + bias) : T(-0.5) * a));
     const T hscale = (KIND == CGLB_RBF) ? T(1) : T(3);
     const T ui = row < n ? hscale * u[rr] : T(0);
     const T vi = row < n ? hscale * v[rr] : T(0);
@@ -99,18 +96,8 @@ __global__ __launch_bounds__(256, 2) void grad_kff_mid_kernel(const double* __re
                 __builtin_amdgcn_sched_barrier(0);
             }
         }
-        // second moments through the column sums of the pair weights, as in grad_kff_gram_kernel; the squares are formed here
-#pragma unroll
-        for (int jj = 0; jj < 8; ++jj) tr[jj * GRAD_TR_LD + lane] = t[jj];
-        __builtin_amdgcn_wave_barrier();
-        const T* __restrict__ src = tr + (lane & 7) * GRAD_TR_LD + (lane & ~7);
-        T cs = src[0];
-#pragma unroll
-        for (int i = 1; i < 8; ++i) cs += src[i];
-        __builtin_amdgcn_wave_barrier();
-        cs += __shfl_xor(cs, 8, 64);
-        cs += __shfl_xor(cs, 16, 64);
-        cs += __shfl_xor(cs, 32, 64);
+        // second moments through the column sums of the pair weights (pair_common.h: wave_colsum8), as in grad_kff_gram_kernel; the squares are formed here
+        const T cs = wave_colsum8<T>(t, tr, lane);
         const int64_t jcol = jb + (lane & 7);
         const T* __restrict__ xq = Xh + (jcol < j1 ? jcol : j1 - 1) * DP;  // columns past the chunk carry cs == 0
 #pragma unroll

@@ -21,13 +21,10 @@
 //   Pcol[g][b][j], g < ceil(nrb / 4) : column sums produced by the group of row blocks 4g .. 4g+3 (valid where the group starts left of j)
 // Scope: fp64, Dp <= 32, unclamped exponent range, one rank, full square.  Everything else falls back to S single mat-vecs
 // (launch_kff_matmat below).
-#include "devmath.h"
-#include "dispatch.h"
-#include <algorithm>
+#include "pair_common.h"
 
 #define MULTI_PART 16        // partial sums per lane and batch: 16 / S_pad columns x S_pad right-hand sides
 #define MULTI_CS_MAX 1024    // column sums a wave stages in LDS (columns of a chunk x S_pad)
-#define MULTI_TR_LD 65       // leading dimension of the 8 x 64 transposition scratch of a wave (odd: conflict-free column reads)
 #define MULTI_LATE_DP 24     // padded width from which the next column's x operand is fetched after the Gram chain (SGPR budget)
 
 // rows per lane: at most 4 (the single kernel's 8 at Dp <= 4 left the Matern instances 10 VGPRs over the 256 of two waves per SIMD),
@@ -57,8 +54,7 @@ __device__ __forceinline__ void kff_multi_cols(const double* __restrict__ Xs, co
                                                const double (&xi)[R][DP], const double (&ai)[R], const double (&pr)[R][SP], double (&acc)[R][SP],
                                                int64_t j0, int64_t j1, int64_t c0, int64_t sym_from, double* __restrict__ cs,
                                                double* __restrict__ tr, const double* __restrict__ tab, int lane) {
-    constexpr bool FOLD = KIND == CGLB_RBF;
-    constexpr bool BIASED = KIND != CGLB_RBF && PREC != CGLB_PREC_EXACT;
+    constexpr bool FOLD = pair_fold<KIND, false>(), BIASED = pair_biased<double, KIND, false, PREC>();  // fp64, unclamped range
     constexpr int NB = MULTI_PART / SP;  // columns per batch
     constexpr bool LATE = DP >= MULTI_LATE_DP;
     const int64_t jfull = j0 + ((j1 - j0) / NB) * NB;  // j0 and the chunk are multiples of 16: only the last batch of the matrix is short
@@ -137,20 +133,10 @@ __device__ __forceinline__ void kff_multi_cols(const double* __restrict__ Xs, co
         }
         if (jb >= sym_from) {  // wave-uniform; sym_from is a multiple of 64, so a batch never straddles it
             // column sums of the batch = sums across the 64 lanes of the 16 partials; partial q = (column q / SP, right-hand side q % SP)
-            // lands at cs[(jb - c0) * SP + q]: the interleaved layout makes the single kernel's two 8-wide transpositions fit as they are
+            // lands at cs[(jb - c0) * SP + q]: with the interleaved layout the single kernel's two 8-wide transpositions (wave_colsum8) fit
 #pragma unroll
             for (int half = 0; half < 2; ++half) {
-#pragma unroll
-                for (int q = 0; q < 8; ++q) tr[q * MULTI_TR_LD + lane] = t[8 * half + q];
-                __builtin_amdgcn_wave_barrier();
-                const double* __restrict__ src = tr + (lane & 7) * MULTI_TR_LD + (lane & ~7);
-                double v = src[0];
-#pragma unroll
-                for (int i = 1; i < 8; ++i) v += src[i];
-                __builtin_amdgcn_wave_barrier();
-                v += __shfl_xor(v, 8, 64);
-                v += __shfl_xor(v, 16, 64);
-                v += __shfl_xor(v, 32, 64);
+                const double v = wave_colsum8<double>(t + 8 * half, tr, lane);
                 if (lane < 8) cs[(jb - c0) * SP + 8 * half + lane] = v;
             }
         }
@@ -195,10 +181,9 @@ __global__ __launch_bounds__(256, 2) void kff_multi_kernel(const double* __restr
                                                            double* __restrict__ Pcol, const double* __restrict__ exp_tab, double bias) {
     __shared__ double tab[CGLB_TAB_SIZE];
     __shared__ double csum[4 * MULTI_CS_MAX];
-    __shared__ double trbuf[4 * 8 * MULTI_TR_LD];
+    __shared__ double trbuf[4 * 8 * PAIR_TR_LD];
     load_exp_table(tab, exp_tab);  // before the early exit below: every thread reaches the barrier inside
-    constexpr bool FOLD = KIND == CGLB_RBF;
-    constexpr bool BIASED = KIND != CGLB_RBF && PREC != CGLB_PREC_EXACT;
+    constexpr bool FOLD = pair_fold<KIND, false>(), BIASED = pair_biased<double, KIND, false, PREC>();
     constexpr int RBROWS = 64 * R;
     const int lane = threadIdx.x & 63;
     const int2 grp = groups[blockIdx.x];
@@ -210,7 +195,7 @@ __global__ __launch_bounds__(256, 2) void kff_multi_kernel(const double* __restr
     const int64_t rbase = rb * RBROWS, gbase = 4 * g * RBROWS;
     const int64_t sym_from = rbase + RBROWS;   // columns at or beyond this get the transposed contribution
     double* __restrict__ cs = csum + wave * MULTI_CS_MAX;
-    double* __restrict__ tr = trbuf + wave * 8 * MULTI_TR_LD;
+    double* __restrict__ tr = trbuf + wave * 8 * PAIR_TR_LD;
     double xi[R][DP], ai[R], pr[R][SP], acc[R][SP];
 #pragma unroll
     for (int r = 0; r < R; ++r) {
@@ -219,8 +204,7 @@ __global__ __launch_bounds__(256, 2) void kff_multi_kernel(const double* __restr
         const int64_t rr = live ? row : n - 1;
 #pragma unroll
         for (int d = 0; d < DP; ++d) xi[r][d] = Xs[rr * DP + d];
-        const double a = xa[rr];
-        ai[r] = (KIND == CGLB_RBF) ? a : (BIASED ? -0.5 * (a + bias) : -0.5 * a);
+        ai[r] = pair_row_seed<double, KIND, BIASED>(xa[rr], bias);
 #pragma unroll
         for (int b = 0; b < SP; ++b) {
             pr[r][b] = (live && b < s) ? V[(int64_t)b * n + rr] : 0.0;
@@ -289,40 +273,16 @@ __global__ __launch_bounds__(256) void kff_multi_combine_kernel(const double* __
     }
 }
 
-// Work list: one entry (g, K) per workgroup, for every group g of four row blocks and every span K the group's first block reaches.
-// Order as in the single kernel (option "sym_order"): 0 group major; 1 XCD-aware - sorted by span, cut into 8 contiguous ranges, one per
-// XCD (workgroup b runs on XCD b % 8), group by group inside a range, padded with (-1, -1).
+// Work list: one entry (g, K) per workgroup, for every group g of four row blocks and every span K the group's first block reaches, in the
+// order of the single kernel (option "sym_order"; pair_worklist.h: pair_work_order).
 static int ensure_multi_items(cglb_ctx* c, int64_t n, int rbrows, int64_t span, int* nwg_out) {
-    if (c->mm_items && c->mm_n == n && c->mm_rbrows == rbrows && c->mm_span == span && c->mm_order_built == c->sym_order) {
-        *nwg_out = c->mm_nwg;
-        return CGLB_OK;
+    const int64_t key[6] = {n, span, rbrows, 1, 0, c->sym_order};
+    if (!c->mm_list.holds(key)) {
+        const int nrb = (int)((n + rbrows - 1) / rbrows), nspan = (int)((n + span - 1) / span);
+        auto first_span = [&](int g) { return (int)(((int64_t)4 * g * rbrows) / span); };
+        CGLB_TRY(pair_list_store(c, &c->mm_list, key, {}, pair_work_order((nrb + 3) / 4, nspan, first_span, c->sym_order)));
     }
-    const int nrb = (int)((n + rbrows - 1) / rbrows), ngroups = (nrb + 3) / 4, nspan = (int)((n + span - 1) / span);
-    auto first_span = [&](int g) { return (int)(((int64_t)4 * g * rbrows) / span); };
-    std::vector<int2> sorted, order;
-    if (c->sym_order == 0) {
-        for (int g = 0; g < ngroups; ++g)
-            for (int K = first_span(g); K < nspan; ++K) order.push_back(make_int2(g, K));
-    } else {
-        for (int K = 0; K < nspan; ++K)
-            for (int g = 0; g < ngroups; ++g)
-                if (first_span(g) <= K) sorted.push_back(make_int2(g, K));
-        const size_t T = sorted.size(), XCDS = 8, per_xcd = (T + XCDS - 1) / XCDS;
-        order.assign(per_xcd * XCDS, make_int2(-1, -1));
-        for (size_t x = 0; x < XCDS; ++x) {
-            const size_t lo = std::min(x * per_xcd, T), hi = std::min((x + 1) * per_xcd, T);
-            std::stable_sort(sorted.begin() + lo, sorted.begin() + hi, [](const int2& a, const int2& b) { return a.x < b.x; });
-            for (size_t q = lo; q < hi; ++q) order[(q - lo) * XCDS + x] = sorted[q];
-        }
-    }
-    if (order.empty()) order.push_back(make_int2(-1, -1));
-    HIP_CHECK(c, c->mem.drop(&c->mm_items));  // the list is replaced, at its new size
-    CGLB_TRY(c->mem.alloc(c, &c->mm_items, order.size() * sizeof(int2)));
-    HIP_CHECK(c, hipMemcpyAsync(c->mm_items, order.data(), order.size() * sizeof(int2), hipMemcpyHostToDevice, c->stream));
-    HIP_CHECK(c, hipStreamSynchronize(c->stream));
-    c->mm_n = n; c->mm_rbrows = rbrows; c->mm_span = span; c->mm_order_built = c->sym_order;
-    c->mm_nwg = (int)order.size();
-    *nwg_out = c->mm_nwg;
+    *nwg_out = c->mm_list.nwg;
     return CGLB_OK;
 }
 
@@ -330,19 +290,11 @@ template <int KIND, int DP, int SP>
 static int kff_multi_generic(cglb_ctx* c, const double* V, int s, double* Out, bool skip_combine) {
     constexpr int R = multi_rows_per_lane(DP, SP);
     constexpr int RBROWS = 64 * R;
-    constexpr bool FOLD = KIND == CGLB_RBF;
+    constexpr bool FOLD = pair_fold<KIND, false>();
     const int64_t n = c->N;
-    // span: the column chunk rule of the single kernel (1024, halved while a launch would have fewer than 16k work items; "sym_chunk");
-    // LDS chunk: at most MULTI_CS_MAX / SP columns of it; Q of them cover the span
-    int64_t span = 1024;
-    {
-        const double nrb_d = (double)((n + RBROWS - 1) / RBROWS);
-        while (span > 128 && nrb_d * ((double)n / (double)span) * 0.5 < 16384.0) span /= 2;
-    }
-    if (c->sym_chunk_opt > 0) span = c->sym_chunk_opt;
-    span = (span + 15) / 16 * 16;
-    if (span > 1024) span = 1024;
-    int64_t chunk = std::min<int64_t>(span, MULTI_CS_MAX / SP);  // 512 / 256 / 128: multiples of 16
+    // span: the column chunk rule of the single kernel (option "sym_chunk"); LDS chunk: at most MULTI_CS_MAX / SP columns of it, Q to the span
+    int64_t span = pair_column_chunk(n, RBROWS, 1, c->sym_chunk_opt);
+    const int64_t chunk = std::min<int64_t>(span, MULTI_CS_MAX / SP);  // 512 / 256 / 128: multiples of 16
     const int Q = (int)((span + chunk - 1) / chunk);
     span = (int64_t)Q * chunk;
     int nwg = 0;
@@ -350,15 +302,7 @@ static int kff_multi_generic(cglb_ctx* c, const double* V, int s, double* Out, b
     const int nrb = (int)((n + RBROWS - 1) / RBROWS), ngroups = (nrb + 3) / 4, nspan = (int)((n + span - 1) / span);
     const int64_t prow_ld = (int64_t)nrb * RBROWS;
     const size_t need = ((size_t)ngroups * n + (size_t)nspan * prow_ld) * SP * sizeof(double);
-    if (need > c->mm_part_cap) {
-        HIP_CHECK(c, c->mem.drop(&c->mm_part, &c->mm_part_cap));
-        size_t free_b = 0, total_b = 0;
-        HIP_CHECK(c, hipMemGetInfo(&free_b, &total_b));
-        if (need > free_b)
-            return cglb_fail(c, CGLB_ERR_HIP, "K_ff mat-mat needs " + std::to_string(need >> 20) + " MiB of partial-sum slabs but only " + std::to_string(free_b >> 20) +
-                                                  " MiB of device memory are free: multiply fewer columns at a time");
-    }
-    CGLB_TRY(c->mem.reserve(c, &c->mm_part, &c->mm_part_cap, need));
+    CGLB_TRY(pair_reserve_slabs(c, &c->mm_part, &c->mm_part_cap, need, "K_ff mat-mat", "", "multiply fewer columns at a time"));
     CGLB_TRY(c->mem.reserve(c, &c->mm_vi, &c->mm_vi_cap, (size_t)n * 8 * sizeof(double)));
     double* Prow = (double*)c->mm_part;
     double* Pcol = Prow + (size_t)nspan * prow_ld * SP;
@@ -368,7 +312,7 @@ static int kff_multi_generic(cglb_ctx* c, const double* V, int s, double* Out, b
     using T = double;
     CGLB_DISPATCH_PREC(c, hipLaunchKernelGGL((kff_multi_kernel<KIND, DP, R, SP, PREC>), dim3(nwg), dim3(256), 0, c->stream, (const double*)c->Xh,
                                              (const double*)c->xah, V, s, (const double*)c->mm_vi, (const double*)c->wh, n, chunk, Q, nrb,
-                                             (const int2*)c->mm_items, prow_ld, Prow, Pcol, (const double*)c->exp_tab, c->m32_bias));
+                                             (const int2*)c->mm_list.dev, prow_ld, Prow, Pcol, (const double*)c->exp_tab, c->m32_bias));
     CGLB_LAUNCH_CHECK(c);
     if (skip_combine) return CGLB_OK;
     hipLaunchKernelGGL(kff_multi_combine_kernel, dim3((unsigned)((n + 63) / 64), (unsigned)s), dim3(256), 0, c->stream, (const double*)Prow, nspan, prow_ld,

@@ -24,14 +24,12 @@
 // a_j is dropped: the row sums use the pre-weighted operand pw_j = p_j w_j (one N-element kernel per mat-vec) and the 16
 // column sums of a batch are multiplied by w_j after the cross-lane reduction.  The unweighted factor reaches
 // 2^(|x_j|^2/2); cglb_set_hypers keeps the whole exponent range inside +-1000 octaves (fp64) / +-100 (fp32) or selects CLAMP.
-#include "devmath.h"
-#include "dispatch.h"
-#include <algorithm>
+#include "pair_common.h"
 
 #define SYM_BATCH 16
 typedef float sym_f2 __attribute__((ext_vector_type(2)));  // two rows of a lane side by side: v_pk_fma_f32 (fp32 path)
 
-#define SYM_CHUNK_MAX 1024  // column chunk of a work item: at most this many columns (their sums are staged in LDS)
+#define SYM_CHUNK_MAX PAIR_CHUNK_MAX  // column chunk of a work item: at most this many columns (their sums are staged in LDS)
 #ifndef CGLB_SYM_TR_REG
 #define CGLB_SYM_TR_REG 0
 #endif
@@ -55,7 +53,6 @@ typedef float sym_f2 __attribute__((ext_vector_type(2)));  // two rows of a lane
 #define CGLB_SYM_MID_TR_REG 0
 #endif
 #define SYM_TR_IN_REG(T, DP, R) (CGLB_SYM_TR_REG || ((R) == 1 && !(sizeof(T) == 8 && (DP) >= CGLB_SYM_BCAST_DP && !CGLB_SYM_MID_TR_REG)))
-#define SYM_TR_LD 65         // leading dimension of the 8 x 64 transposition scratch of a wave (odd: the column reads spread over the banks)
 
 // One work item: rows of block `rb` against the columns of chunk `k` that lie at or right of the block's first row.  Row sums go to
 // Prow; the column sums (transposed use of the kernel values) go to `cs`, this wave's LDS array indexed by column - k * chunk.
@@ -63,9 +60,7 @@ template <typename T, int KIND, int DP, int R, bool CLAMP, int PREC>
 __device__ __forceinline__ void kff_sym_item(const T* __restrict__ Xs, const T* __restrict__ xa, const T* __restrict__ p, const T* __restrict__ pc,
                                              int64_t row0, int64_t n, int64_t chunk, int64_t rb, int64_t k, int64_t cslot, int64_t prow_ld,
                                              T* __restrict__ Prow, T* __restrict__ cs, T* __restrict__ tr, const double* __restrict__ tab, int lane, T bias) {
-    constexpr bool FOLD = (KIND == CGLB_RBF) && !CLAMP;
-    // Matern-3/2, fast level, unclamped range: squared distances kept positive by a bias in the row seeds instead of a clamp per pair
-    constexpr bool BIASED = (KIND != CGLB_RBF) && !CLAMP && PREC != CGLB_PREC_EXACT && sizeof(T) == 8;
+    constexpr bool FOLD = pair_fold<KIND, CLAMP>(), BIASED = pair_biased<T, KIND, CLAMP, PREC>();
     constexpr int RBROWS = 64 * R;
     const int64_t rbase = rb * RBROWS;
     // fp32: rows in pairs, so that the Gram chain and the two accumulations run as v_pk_fma_f32 (4.8 nominal cycles per pair of
@@ -100,8 +95,7 @@ __device__ __forceinline__ void kff_sym_item(const T* __restrict__ Xs, const T* 
             if (PACKED) xi2[r / 2][d][r % 2] = (float)v;
             else xi[r % RU][d] = v;
         }
-        const T a = xa[row0 + rr];
-        ai[r] = (KIND == CGLB_RBF) ? a : (BIASED ? T(-0.5) * (a + bias) : T(-0.5) * a);
+        ai[r] = pair_row_seed<T, KIND, BIASED>(xa[row0 + rr], bias);
         pr[r] = row < n ? p[row0 + rr] : T(0);
         acc[r] = 0;
     }
@@ -275,16 +269,14 @@ __device__ __forceinline__ void kff_sym_item(const T* __restrict__ Xs, const T* 
                 v += __shfl_xor(v, 32, 64);
                 if (lane < SYM_BATCH) cs[jb - k * chunk + lane] = v;
             } else {
-                // Transposed through LDS, 8 columns at a time: every lane writes its 8 partials (row jj of `tr`, stride SYM_TR_LD:
-                // conflict-free), then lane (c = lane & 7, g = lane >> 3) adds the 8 lanes 8g..8g+7 of column c in fixed order and three
-                // xor-shuffles add the 8 groups: 7 + 3 adds and no selects per 32 pairs, against 83 VALU instructions per 64 pairs for the
-                // in-register form.  One wave, in-order LDS: no barrier; the wave_barrier calls only pin the compiler's order.
+                // Transposed through LDS, 8 columns at a time: wave_colsum8 of pair_common.h (explained there), written out.  Calling it here
+                // reorders the address arithmetic hoisted out of the column loop and reschedules every instance (fp32, DP = 28: one more spill).
 #pragma unroll
                 for (int half = 0; half < 2; ++half) {
 #pragma unroll
-                    for (int jj = 0; jj < 8; ++jj) tr[jj * SYM_TR_LD + lane] = t[8 * half + jj];
+                    for (int jj = 0; jj < 8; ++jj) tr[jj * PAIR_TR_LD + lane] = t[8 * half + jj];
                     __builtin_amdgcn_wave_barrier();
-                    const T* __restrict__ src = tr + (lane & 7) * SYM_TR_LD + (lane & ~7);
+                    const T* __restrict__ src = tr + (lane & 7) * PAIR_TR_LD + (lane & ~7);
                     T v = src[0];
 #pragma unroll
                     for (int i = 1; i < 8; ++i) v += src[i];
@@ -359,9 +351,9 @@ __global__ __launch_bounds__(256, (sizeof(T) == 4 ? 4 : CGLB_SYM_WAVES(DP, R))) 
                                                       T* __restrict__ Pcol, const double* __restrict__ exp_tab, T bias) {
     __shared__ double tab[CGLB_TAB_SIZE];
     __shared__ T csum[4 * SYM_CHUNK_MAX];
-    __shared__ T trbuf[SYM_TR_IN_REG(T, DP, R) ? 1 : 4 * 8 * SYM_TR_LD];  // transposition scratch of the four waves (unused for R == 1)
+    __shared__ T trbuf[SYM_TR_IN_REG(T, DP, R) ? 1 : 4 * 8 * PAIR_TR_LD];  // transposition scratch of the four waves (unused for R == 1)
     load_exp_table(tab, exp_tab);  // before the early exit below: every thread reaches the barrier inside
-    constexpr bool FOLD = (KIND == CGLB_RBF) && !CLAMP;
+    constexpr bool FOLD = pair_fold<KIND, CLAMP>();
     const T* __restrict__ pc = FOLD ? pw : p;  // column-side operand
     const int lane = threadIdx.x & 63;
     const int2 grp = groups[blockIdx.x];
@@ -375,7 +367,7 @@ __global__ __launch_bounds__(256, (sizeof(T) == 4 ? 4 : CGLB_SYM_WAVES(DP, R))) 
     if (__builtin_amdgcn_readfirstlane(it.x) >= 0) {
         const int64_t rb = __builtin_amdgcn_readfirstlane(it.x), k = __builtin_amdgcn_readfirstlane(it.y);
         const int64_t cslot = rb / rb_stride;  // compact slot: with a cyclic rank distribution only every rb_stride-th block is here
-        kff_sym_item<T, KIND, DP, R, CLAMP, PREC>(Xs, xa, p, pc, row0, n, chunk, rb, k, cslot, prow_ld, Prow, cs, trbuf + (SYM_TR_IN_REG(T, DP, R) ? 0 : wave * 8 * SYM_TR_LD), tab, lane, bias);
+        kff_sym_item<T, KIND, DP, R, CLAMP, PREC>(Xs, xa, p, pc, row0, n, chunk, rb, k, cslot, prow_ld, Prow, cs, trbuf + (SYM_TR_IN_REG(T, DP, R) ? 0 : wave * 8 * PAIR_TR_LD), tab, lane, bias);
     }
     __syncthreads();
     const int64_t gslot = __builtin_amdgcn_readfirstlane(grp.x), k = __builtin_amdgcn_readfirstlane(grp.y);
@@ -487,74 +479,36 @@ static int ensure_sym_items(cglb_ctx* c, int64_t n, int rbrows, int64_t chunk, i
                             int* nchunk_out) {
     const int nrb = (int)((n + rbrows - 1) / rbrows);
     const int nchunk = (int)((n + chunk - 1) / chunk);
-    if (c->sym_items && c->sym_n == n && c->sym_rbrows == rbrows && c->sym_chunk == chunk && c->sym_world == world && c->sym_rank == rank &&
-        c->sym_order_built == c->sym_order) {
-        *nblocks_out = c->sym_nitems; *nrb_out = nrb; *nchunk_out = nchunk;
-        return CGLB_OK;
-    }
-    const int nlb = rank < nrb ? (nrb - rank + world - 1) / world : 0;  // row blocks of this rank
-    const int ngroups = (nlb + 3) / 4;
-    auto first_chunk = [&](int lb) { return (int)((((int64_t)rank + (int64_t)lb * world) * rbrows) / chunk); };  // chunk holding the block's first row
-    std::vector<int2> sorted;  // (g, k)
-    if (c->sym_order == 0) {
-        // group major, longest rows first (group 0 sweeps the most columns)
-        for (int g = 0; g < ngroups; ++g)
-            for (int k = first_chunk(4 * g); k < nchunk; ++k) sorted.push_back(make_int2(g, k));
-    } else {
-        // XCD-aware order.  Workgroups go round-robin to the 8 XCDs (workgroup b -> XCD b % 8), each with its own 4-MB L2, and the
-        // streamed side of a workgroup is its column chunk (chunk * (DP + 2) operands, 80 KB at 1024 columns).  Groups are sorted by
-        // column chunk and the sorted list is cut into 8 contiguous ranges of equal length, one per XCD: an XCD then only ever
-        // streams its own ~1/8 of the columns (L2-resident), instead of every XCD sweeping all of X through the Infinity Cache.
-        for (int k = 0; k < nchunk; ++k)
-            for (int g = 0; g < ngroups; ++g)
-                if (first_chunk(4 * g) <= k) sorted.push_back(make_int2(g, k));
-    }
-    const size_t T = sorted.size();
-    std::vector<int2> order;  // workgroup b -> (g, k) or (-1, -1)
-    if (c->sym_order == 0) {
-        order = sorted;
-    } else {
-        const int XCDS = 8;
-        const size_t per_xcd = (T + XCDS - 1) / XCDS;  // workgroups per XCD
-        order.assign(per_xcd * XCDS, make_int2(-1, -1));
-        // inside an XCD's range (a dozen column chunks, ~1 MB of streamed operands that stay in its L2) go group by group,
-        // so that the row operands of a group are fetched once per XCD rather than once per workgroup
-        for (size_t x = 0; x < (size_t)XCDS; ++x) {
-            const size_t lo = x * per_xcd < T ? x * per_xcd : T, hi = (x + 1) * per_xcd < T ? (x + 1) * per_xcd : T;
-            std::stable_sort(sorted.begin() + lo, sorted.begin() + hi, [](const int2& a, const int2& b) { return a.x < b.x; });
-            for (size_t q = lo; q < hi; ++q) order[(q - lo) * XCDS + x] = sorted[q];  // workgroup index that lands on XCD x
+    *nrb_out = nrb; *nchunk_out = nchunk;
+    const int64_t key[6] = {n, chunk, rbrows, world, rank, c->sym_order};
+    if (!c->sym_list.holds(key)) {
+        const int nlb = rank < nrb ? (nrb - rank + world - 1) / world : 0;  // row blocks of this rank
+        auto first_chunk = [&](int lb) { return (int)((((int64_t)rank + (int64_t)lb * world) * rbrows) / chunk); };  // chunk holding the block's first row
+        // workgroup b -> (g, k) or (-1, -1)
+        const std::vector<pair_unit> order = pair_work_order((nlb + 3) / 4, nchunk, [&](int g) { return first_chunk(4 * g); }, c->sym_order);
+        std::vector<pair_unit> items(order.size() * 4, pair_unit{-1, -1});
+        double pairs = 0.0;  // evaluated kernel pairs of one launch (cglb_get_stat "k1_pairs_per_launch")
+        for (size_t b = 0; b < order.size(); ++b) {
+            const int g = order[b].x, k = order[b].y;
+            if (g < 0) continue;
+            for (int w = 0; w < 4; ++w) {
+                const int lb = 4 * g + w;
+                items[4 * b + w] = pair_unit{-1, k};
+                if (lb >= nlb || first_chunk(lb) > k) continue;
+                const int rb = rank + lb * world;
+                items[4 * b + w] = pair_unit{rb, k};
+                const int64_t rbase = (int64_t)rb * rbrows;
+                const int64_t rows = (n - rbase < rbrows) ? n - rbase : rbrows;
+                int64_t j0 = (int64_t)k * chunk, j1 = ((int64_t)k + 1) * chunk;
+                if (j0 < rbase) j0 = rbase;
+                if (j1 > n) j1 = n;
+                if (j1 > j0) pairs += (double)rows * (double)(j1 - j0);
+            }
         }
+        c->sym_pairs = pairs;
+        CGLB_TRY(pair_list_store(c, &c->sym_list, key, items, order));  // the items first, the groups behind them
     }
-    std::vector<int2> items(order.size() * 4, make_int2(-1, -1));
-    double pairs = 0.0;  // evaluated kernel pairs of one launch (cglb_get_stat "k1_pairs_per_launch")
-    for (size_t b = 0; b < order.size(); ++b) {
-        const int g = order[b].x, k = order[b].y;
-        if (g < 0) continue;
-        for (int w = 0; w < 4; ++w) {
-            const int lb = 4 * g + w;
-            items[4 * b + w] = make_int2(-1, k);
-            if (lb >= nlb || first_chunk(lb) > k) continue;
-            const int rb = rank + lb * world;
-            items[4 * b + w] = make_int2(rb, k);
-            const int64_t rbase = (int64_t)rb * rbrows;
-            const int64_t rows = (n - rbase < rbrows) ? n - rbase : rbrows;
-            int64_t j0 = (int64_t)k * chunk, j1 = ((int64_t)k + 1) * chunk;
-            if (j0 < rbase) j0 = rbase;
-            if (j1 > n) j1 = n;
-            if (j1 > j0) pairs += (double)rows * (double)(j1 - j0);
-        }
-    }
-    c->sym_pairs = pairs;
-    HIP_CHECK(c, c->mem.drop(&c->sym_items));  // the list is replaced, at its new size
-    if (order.empty()) { order.push_back(make_int2(-1, -1)); items.assign(4, make_int2(-1, -1)); }  // keep the allocation non-empty
-    // one allocation: the items first, the groups behind them
-    CGLB_TRY(c->mem.alloc(c, &c->sym_items, (items.size() + order.size()) * sizeof(int2)));
-    HIP_CHECK(c, hipMemcpyAsync(c->sym_items, items.data(), items.size() * sizeof(int2), hipMemcpyHostToDevice, c->stream));
-    HIP_CHECK(c, hipMemcpyAsync((int2*)c->sym_items + items.size(), order.data(), order.size() * sizeof(int2), hipMemcpyHostToDevice, c->stream));
-    HIP_CHECK(c, hipStreamSynchronize(c->stream));
-    c->sym_n = n; c->sym_rbrows = rbrows; c->sym_chunk = chunk; c->sym_world = world; c->sym_rank = rank; c->sym_order_built = c->sym_order;
-    c->sym_nitems = T > 0 ? (int)order.size() : 0;  // number of workgroups
-    *nblocks_out = c->sym_nitems; *nrb_out = nrb; *nchunk_out = nchunk;
+    *nblocks_out = c->sym_list.nwg;
     return CGLB_OK;
 }
 
@@ -569,16 +523,7 @@ static int kff_sym_generic(cglb_ctx* c, const T* p_full, T* out_local, double* p
     const int64_t n = cyclic ? c->N : c->nloc;
     const int64_t row0 = cyclic ? 0 : c->r0;
     const int world = cyclic ? c->par_world : 1, rank = cyclic ? c->par_rank : 0;
-    // (measured per-rank kernel at N=100k: world 8: 0.48 ms at 128, 0.63 ms at 1024; world 4: 0.82 at 256, 0.86 at 512) -> halve the
-    // 1024-column chunk until a rank has >= 16k items; large N keeps 1024 at any world size (fewer, larger slabs)
-    int64_t chunk = 1024;
-    {
-        const double nrb_rank = (double)((n + RBROWS - 1) / RBROWS) / world;
-        while (chunk > 128 && nrb_rank * ((double)n / (double)chunk) * 0.5 < 16384.0) chunk /= 2;
-    }
-    if (c->sym_chunk_opt > 0) chunk = c->sym_chunk_opt;
-    chunk = (chunk + SYM_BATCH - 1) / SYM_BATCH * SYM_BATCH;
-    if (chunk > SYM_CHUNK_MAX) chunk = SYM_CHUNK_MAX;  // the column sums of a chunk are staged in LDS
+    const int64_t chunk = pair_column_chunk(n, RBROWS, world, c->sym_chunk_opt);  // a multiple of SYM_BATCH, at most SYM_CHUNK_MAX
     int nblocks = 0, nrb = 0, nchunk = 0;
     CGLB_TRY(ensure_sym_items(c, n, RBROWS, chunk, world, rank, &nblocks, &nrb, &nchunk));
     const int ncslot = (nrb + world - 1) / world;      // row blocks of a rank (upper bound): row-sum slab rows
@@ -589,15 +534,7 @@ static int kff_sym_generic(cglb_ctx* c, const T* p_full, T* out_local, double* p
     if (nleft > 0 || nright > 0) plain_slots_max = 2 * 512;
     const int64_t prow_ld = (int64_t)ncslot * RBROWS;  // compact rows of this rank's row blocks
     const size_t need = (((size_t)plain_slots_max + ngslot) * n + (size_t)nchunk * prow_ld) * sizeof(T);
-    if (need > c->kpart_cap) {
-        HIP_CHECK(c, c->mem.drop(&c->kpart, &c->kpart_cap));  // the old slabs count as free below
-        size_t free_b = 0, total_b = 0;
-        HIP_CHECK(c, hipMemGetInfo(&free_b, &total_b));
-        if (need > free_b)  // the partial-sum slabs grow as N^2 / 256 elements per rank: say so instead of failing inside hipMalloc
-            return cglb_fail(c, CGLB_ERR_HIP, "K_ff mat-vec needs " + std::to_string(need >> 20) + " MiB of partial-sum slabs (N^2/256 + N^2/chunk elements per rank) but only " +
-                                                  std::to_string(free_b >> 20) + " MiB of device memory are free: shard the rows over more GPUs");
-    }
-    CGLB_TRY(c->mem.reserve(c, &c->kpart, &c->kpart_cap, need));
+    CGLB_TRY(pair_reserve_slabs(c, &c->kpart, &c->kpart_cap, need, "K_ff mat-vec", " (N^2/256 + N^2/chunk elements per rank)", "shard the rows over more GPUs"));
     T* plain = (T*)c->kpart;
     int64_t nplain = 0;
     if (nleft > 0) {
@@ -613,7 +550,7 @@ static int kff_sym_generic(cglb_ctx* c, const T* p_full, T* out_local, double* p
     T* Prow = plain + nplain * n;
     T* Pcol = Prow + (int64_t)nchunk * prow_ld;
     const int grid = nblocks;
-    const int2* items_dev = (const int2*)c->sym_items;
+    const int2* items_dev = (const int2*)c->sym_list.dev;
     const int2* groups_dev = items_dev + (size_t)4 * (nblocks > 0 ? nblocks : 1);
     if (grid > 0) {
         if (!c->exp_clamp && KIND == CGLB_RBF) {  // folded column norm: pre-weight the operand over the columns of this block

@@ -1,0 +1,62 @@
+// Launch geometry of the symmetric pair kernels (kernels_kff_sym.hip, kernels_kff_multi.hip): the column-chunk rule and the order of the
+// work list.  Pure integer host code without HIP types, so that a plain C++ program can include and test it (tests/host).
+#pragma once
+#include <algorithm>
+#include <cstdint>
+#include <vector>
+
+#define PAIR_CHUNK_MAX 1024  // a workgroup stages the column sums of one chunk in LDS: at most this many per wave
+
+struct pair_unit { int x, y; };  // (group of four row blocks, column unit), (-1, -1) = padding; the layout of int2 (pair_common.h checks)
+
+// A work list on the device with what it was built for; one per kernel, so that alternating launches of the two rebuild nothing.
+struct pair_list {
+    void* dev = nullptr;
+    int64_t key[6] = {-1, 0, 0, 0, 0, 0};  // n, column unit, rows per block, world, rank, order
+    int nwg = 0;                           // workgroups of a launch (padding included)
+    bool holds(const int64_t (&k)[6]) const { return dev && std::equal(k, k + 6, key); }
+};
+
+// Columns per work item: 1024, halved down to 128 while a rank has fewer than 16k items (measured per-rank kernel at N = 100k: world 8:
+// 0.48 ms at 128, 0.63 ms at 1024; world 4: 0.82 at 256, 0.86 at 512; large N keeps 1024 at any world size: fewer, larger slabs); the
+// option "sym_chunk" (> 0, at most 2^20: cglb_set_option) overrides; rounded up to the batch of 16 columns and clamped to the LDS staging.
+static inline int64_t pair_column_chunk(int64_t n, int rbrows, int world, int64_t sym_chunk_opt) {
+    int64_t chunk = PAIR_CHUNK_MAX;
+    const double nrb_rank = (double)((n + rbrows - 1) / rbrows) / world;
+    while (chunk > 128 && nrb_rank * ((double)n / (double)chunk) * 0.5 < 16384.0) chunk /= 2;
+    if (sym_chunk_opt > 0) chunk = sym_chunk_opt;
+    chunk = (chunk + 15) / 16 * 16;
+    return chunk > PAIR_CHUNK_MAX ? PAIR_CHUNK_MAX : chunk;
+}
+
+// Workgroup b -> (group g, unit k) for every g < ngroups and first_unit(g) <= k < nunits; first_unit(g) is the unit that holds the first
+// row of the group's first block.  Never empty: an empty problem gives one padding entry.
+//   order 0: group major, longest rows first (group 0 sweeps the most columns).
+//   order 1: XCD-aware.  Workgroups go round-robin to the 8 XCDs (workgroup b -> XCD b % 8), each with its own 4-MB L2, and the streamed
+//            side of a workgroup is its column unit (chunk * (DP + 2) operands, 80 KB at 1024 columns).  The list sorted by unit is cut into
+//            8 contiguous ranges of equal length, one per XCD: an XCD then only ever streams its own ~1/8 of the columns (L2-resident)
+//            instead of every XCD sweeping all of X through the Infinity Cache.  Inside a range (a dozen units, ~1 MB of operands) the
+//            entries go group by group, so that the row operands of a group are fetched once per XCD rather than once per workgroup.
+//            Entry q of range x is workgroup 8 q + x; the ranges are padded to equal length.
+template <typename F>
+static std::vector<pair_unit> pair_work_order(int ngroups, int nunits, F first_unit, int order) {
+    std::vector<pair_unit> list;
+    if (order == 0) {
+        for (int g = 0; g < ngroups; ++g)
+            for (int k = first_unit(g); k < nunits; ++k) list.push_back({g, k});
+    } else {
+        std::vector<pair_unit> sorted;
+        for (int k = 0; k < nunits; ++k)
+            for (int g = 0; g < ngroups; ++g)
+                if (first_unit(g) <= k) sorted.push_back({g, k});
+        const size_t T = sorted.size(), XCDS = 8, per_xcd = (T + XCDS - 1) / XCDS;
+        list.assign(per_xcd * XCDS, {-1, -1});
+        for (size_t x = 0; x < XCDS; ++x) {
+            const size_t lo = std::min(x * per_xcd, T), hi = std::min((x + 1) * per_xcd, T);
+            std::stable_sort(sorted.begin() + lo, sorted.begin() + hi, [](const pair_unit& a, const pair_unit& b) { return a.x < b.x; });
+            for (size_t q = lo; q < hi; ++q) list[(q - lo) * XCDS + x] = sorted[q];
+        }
+    }
+    if (list.empty()) list.push_back({-1, -1});  // keeps the device allocation non-empty
+    return list;
+}

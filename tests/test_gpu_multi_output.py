@@ -112,6 +112,36 @@ def test_matmat_zero_equal_and_permuted_columns(kind):
     ctx.close()
 
 
+@pytest.mark.parametrize("kind", KINDS)
+def test_alternating_matvec_and_matmat_keep_their_work_lists_apart(kind):
+    """One context, N = 2500, D = 3 (five 512-row blocks in two groups for the single kernel, 256- and 128-row blocks for the multi
+    kernel), mat-vec and mat-mat calls in turn under a shuffled sequence of sym_chunk and sym_order: each kernel caches its own work
+    list, keyed by what it was built for.  A wrong or shared key would serve a stale list: every result is held to the dense oracle and
+    every repeat of a configuration to the bits of its first occurrence."""
+    N = 2500
+    X, hyp, V, ref = matmat_case(kind, N, 3)
+    ctx = make_ctx(kind, X, np.zeros(N), hyp)
+    settings = [(chunk, order) for chunk in (128, 256, 1024) for order in (0, 1)]
+    rng = np.random.default_rng(17)
+    vec = [(c, o, 1) for c, o in settings] * 6            # 36 mat-vecs and 36 mat-mats: every configuration returns
+    mat = [(c, o, S) for c, o in settings for S in (2, 3, 8)] * 2
+    rng.shuffle(vec)
+    rng.shuffle(mat)
+    first = {}
+    for step, (chunk, order, S) in enumerate(x for pair in zip(vec, mat) for x in pair):
+        ctx.set_option("sym_chunk", chunk)
+        ctx.set_option("sym_order", order)
+        if S == 1:
+            out = ctx.matvec(torch.from_numpy(V[:, 0].copy())).cpu().numpy()[:, None]
+        else:
+            out = ctx.matmat(torch.from_numpy(V[:, :S].copy())).cpu().numpy()
+        what = f"{kind} step {step}: chunk {chunk} order {order} S {S}"
+        check_columns(out, ref[:, :S], what)
+        assert first.setdefault((chunk, order, S), out.tobytes()) == out.tobytes(), what + " differs from its first occurrence"
+    assert len(first) == 24
+    ctx.close()
+
+
 @functools.lru_cache(maxsize=None)
 def solve_case(kind, P, noise=None, max_error=1.0):
     N, D, M = 400, 3, 24
