@@ -96,6 +96,9 @@ SIGNATURES = {
                                               POINTER(c_int), POINTER(c_double)]),
     "cglb_predict_multi": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
     "cglb_time_matmat": (c_int, [c_void_p, c_int, c_int, POINTER(c_double)]),
+    "cglb_gpr_set_hypers": (c_int, [c_void_p, POINTER(c_double), c_double, c_double, c_double]),
+    "cglb_gpr_objective_and_grad": (c_int, [c_void_p, POINTER(c_double), POINTER(c_double)]),
+    "cglb_gpr_predict": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
 }
 
 _lib = None

@@ -19,7 +19,7 @@ import numpy as np
 
 __all__ = [
     "Config", "ModelConfig", "KernelConfig", "SquaredExponentialConfig", "Matern32Config", "CGLBConfig", "CGLBN2MConfig",
-    "CGLBNM2Config", "SGPRN2MConfig", "GPRConfig", "SGPRConfig", "InducingVariableConfig", "GPR_CONFIGS", "SGPR_CONFIGS",
+    "CGLBNM2Config", "SGPRN2MConfig", "GPRConfig", "ExactGPConfig", "SGPRConfig", "InducingVariableConfig", "GPR_CONFIGS", "SGPR_CONFIGS",
     "KERNEL_CONFIGS", "INDUCING_VARIABLE_CONFIGS",
 ]
 

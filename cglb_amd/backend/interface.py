@@ -1,7 +1,7 @@
 """Backend interface for the HIP path — mirror of cglb/backend/pytorch/interface.py restricted to what the CGLB
 path needs: configure_backend, set_default_float/jitter, get_default_float(_str), create_kernel,
-create_model (all five classes of SGPR_CONFIGS: cglb, cglbn2m, cglbnm2, sgpr, sgprn2m), model_parameters, optimize (SciPy L-BFGS-B, four-round schedule :445-543), save, load,
-metrics_fn (:607-658).  Exact-GP / Adam / MultiDeviceKernel branches are out of scope and raise NotImplementedError,
+create_model (all five classes of SGPR_CONFIGS: cglb, cglbn2m, cglbnm2, sgpr, sgprn2m, and the exact `gpr` class of GPR_CONFIGS), model_parameters, optimize (SciPy L-BFGS-B, four-round schedule :445-543), save, load,
+metrics_fn (:607-658).  gpytorch's iterative `exactgp` baseline / Adam / MultiDeviceKernel branches are out of scope and raise NotImplementedError,
 like the reference's unregistered singledispatch defaults (:120-147).
 """
 from __future__ import annotations
@@ -19,10 +19,11 @@ import torch
 
 from . import jsonio, metric
 from .callbacks import Logger
-from .config import (CGLBConfig, CGLBN2MConfig, CGLBNM2Config, KernelConfig, Matern32Config, ModelConfig, SGPRConfig, SGPRN2MConfig,
-                     SquaredExponentialConfig)
-from .models import (CGLB, CGLBN2M, CGLBNM2, GPR, SGPR, SGPRN2M, BaseKernel, GaussianLikelihood, InducingPointKernel, LowerBoundCG,
-                     LowerBoundSGPR, PredictCG, PredictSGPR, ScaleKernel, get_cholesky_jitter, log_density, set_cholesky_jitter)
+from .config import (CGLBConfig, CGLBN2MConfig, CGLBNM2Config, ExactGPConfig, GPRConfig, KernelConfig, Matern32Config, ModelConfig, SGPRConfig,
+                     SGPRN2MConfig, SquaredExponentialConfig)
+from .models import (CGLB, CGLBN2M, CGLBNM2, GPR, SGPR, SGPRN2M, BaseKernel, ExactGPR, GaussianLikelihood, InducingPointKernel,
+                     LogMarginalLikelihood, LowerBoundCG, LowerBoundSGPR, PredictCG, PredictGPR, PredictSGPR, ScaleKernel, get_cholesky_jitter,
+                     log_density, set_cholesky_jitter)
 from .optimizer import Scipy
 
 __all__ = ["create_kernel", "create_model", "optimize", "save", "load", "metrics_fn"]
@@ -235,6 +236,23 @@ def _create_model_sgprn2m(model_cfg: SGPRN2MConfig, data: Data):
     return SGPRN2M((np.asarray(data[0]), _targets(data[1])), likelihood, kernel, dtype=_STATE["dtype"])
 
 
+@create_model.register
+def _create_model_gpr(model_cfg: GPRConfig, data: Data):
+    """tensorflow/interface.py:200-206: noise 1.0, constant mean, the kernel of the kernel config; no inducing points.  One rank, fp64 (an fp32
+    default float is refused with the library's message, which names `-t fp64`)."""
+    _require_one_rank("gpr")
+    likelihood = GaussianLikelihood(lower_bound=1e-6)
+    likelihood.noise = model_cfg.params(data)["noise_variance"]
+    kernel = create_kernel(model_cfg.kernel, data)
+    return ExactGPR((np.asarray(data[0]), _targets(data[1])), likelihood, kernel, dtype=_STATE["dtype"])
+
+
+@create_model.register
+def _create_model_exactgp(model_cfg: ExactGPConfig, data: Data):
+    raise NotImplementedError("model class 'exactgp' (gpytorch's iterative exact-GP baseline, pytorch/interface.py:233-260) is out of scope here: "
+                              "use 'gpr', the dense Cholesky exact GP")
+
+
 def _targets(y) -> np.ndarray:
     """Targets as the models take them: [N, P] stays 2-D for P > 1, a single column (either shape) is the flat vector it always was."""
     y = np.asarray(y)
@@ -413,6 +431,33 @@ def _optimize_sgpr(model: SGPR, dataset, num_steps: int, logger: Logger, optimiz
         return results
 
 
+@optimize.register
+def _optimize_gpr(model: ExactGPR, dataset, num_steps: int, logger: Logger, optimize: str = "scipy"):
+    """The L-BFGS-B rounds of `_optimize_sgpr` on loss = -lml; there are no inducing points to leave out of the later rounds."""
+    assert optimize == "scipy"
+    with _narrow_host_pools():
+        lbfgs = Scipy()
+        lml = LogMarginalLikelihood(model)
+
+        def closure() -> Tensor:
+            return -lml(None)
+
+        params = list(model.parameters())
+        with logger.no_recording():
+            torch.autograd.grad(closure(), params)
+            torch.cuda.synchronize()
+        logger.timer.reset()
+        logger.timer.start()
+        results, remaining = [], num_steps
+        for _round in range(4):
+            if remaining <= 0:
+                break
+            result = lbfgs.minimize(closure, params, options=dict(maxiter=remaining, ftol=0.0, gtol=0.0, disp=False), step_callback=logger)
+            remaining -= result.nit
+            results.append(result)
+        return results
+
+
 @save.register
 def _save(model: GPR, logdir: str):  # interface.py:546-551: json_tricks.dump(model_parameters(model)) -> same encoding (jsonio.py)
     os.makedirs(logdir, exist_ok=True)
@@ -433,6 +478,44 @@ def _load(model: GPR, filepath: str):
     model.covar_module.base_kernel.base_kernel.lengthscale = params[".kernel.lengthscales"]
     model.covar_module.base_kernel.outputscale = params[".kernel.variance"]
     return model
+
+
+@load.register
+def _load_gpr(model: ExactGPR, filepath: str):
+    """Parameters saved by ANY model class (cli.py:166-181 evaluates the exact metrics at hyper-parameters a sparse model was trained to): an
+    inducing-point entry is ignored."""
+    params = jsonio.load(filepath)
+    model.likelihood.noise = params[".likelihood.variance"]
+    with torch.no_grad():
+        model.mean_module.constant.copy_(torch.as_tensor(np.asarray(params[".mean_function.c"]), dtype=torch.float64).reshape(()))
+    model.covar_module.base_kernel.lengthscale = params[".kernel.lengthscales"]
+    model.covar_module.outputscale = params[".kernel.variance"]
+    return model
+
+
+@metrics_fn.register
+def _compute_metrics_gpr(model: ExactGPR, dataset_bundle):
+    """tensorflow/interface.py:386-395: lml, loss = -lml, and rmse / nlpd of the exact predictive on the train and test sets."""
+    train, test = dataset_bundle
+
+    def gpr_metrics():
+        with torch.no_grad():
+            lml = _numpy(LogMarginalLikelihood(model)(None))
+        return dict(lml=lml, loss=-lml)
+
+    x_full = np.concatenate([np.asarray(train[0]), np.asarray(test[0])], axis=0)
+    y_full = np.concatenate([np.asarray(train[1]).reshape(-1), np.asarray(test[1]).reshape(-1)], axis=0).reshape(-1, 1)
+
+    def error_and_logdensity():
+        predict_f = PredictGPR(model)
+        with torch.no_grad():
+            f_mean, f_var = predict_f(torch.as_tensor(x_full))   # the library works through the new points in batches of 4096
+            y = torch.as_tensor(y_full, dtype=f_mean.dtype, device=f_mean.device)
+            lpd, err = _numpy(log_density(model, y, f_mean, f_var)), _numpy(y - f_mean)
+        n = np.asarray(train[0]).shape[0]
+        return (err[:n], err[n:]), (lpd[:n], lpd[n:])
+
+    return lambda: metric.call_metric_fns(gpr_metrics, metric.rmse_and_lpd_fn(error_and_logdensity))
 
 
 @metrics_fn.register

@@ -544,3 +544,103 @@ class PredictSGPR(nn.Module):
                 self.cached = True
             f_mean, f_var = hip.predict(model._zero_v, xnew)
         return f_mean.reshape(-1, 1), f_var.reshape(-1, 1)
+
+
+class ExactGPR(GPR):
+    """Exact GP regression (GPRConfig: tensorflow/interface.py:200-206 builds gpflow's GPR with a constant mean; pytorch/interface.py:561-604
+    trains it on ExactMarginalLogLikelihood times n).  The module tree and parameter keys of the SGPR family without the inducing points:
+    `covar_module` is the ScaleKernel itself.  The N x N kernel matrix is factored on the GPU (cglb_gpr_*: fp64, one rank, one target column)."""
+
+    def __init__(self, data: Data, likelihood: GaussianLikelihood, kernel: ScaleKernel, dtype: torch.dtype = torch.float64,
+                 device: Optional[torch.device] = None, context=None):
+        super().__init__(data, likelihood, kernel)
+        self.dtype = dtype
+        if self.num_outputs > 1:
+            raise NotImplementedError("ExactGPR is not available for more than one target column (only CGLB takes [N, P] targets)")
+        if context is None:
+            import torch.distributed as dist
+            if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+                raise NotImplementedError("ExactGPR is not available on more than one rank (only CGLB runs row-sharded); run it as a single process")
+            context = HipContext(self.train_inputs[0], self.train_targets, 1, kernel.base_kernel.kind, dtype=dtype, device=device)  # M = 1: placeholder
+        elif getattr(context, "world", 1) > 1:
+            raise NotImplementedError("ExactGPR is not available on more than one rank (only CGLB runs row-sharded)")
+        self.hip = context
+        self.push_hypers()   # an fp32 context is refused here, with the library's message, not at the first evaluation
+
+    check_same_data = SGPR.check_same_data
+
+    def hyper_tensors(self):
+        k = self.covar_module
+        return (k.base_kernel.lengthscale.reshape(-1), k.outputscale.reshape(()), self.likelihood.noise.reshape(()),
+                self.mean_module.constant.reshape(()))
+
+    def push_hypers(self):
+        ls, var, noise, mean = [t.detach() for t in self.hyper_tensors()]
+        self.hip.gpr_set_hypers(ls.cpu().numpy(), float(var), float(noise), float(mean))
+
+
+class _GPRFunction(torch.autograd.Function):
+    """lml(lengthscales, variance, noise, mean) of the exact model with the analytic gradient from the GPU."""
+
+    @staticmethod
+    def forward(ctx, model, ls, var, noise, mean):
+        hip = model.hip
+        hip.gpr_set_hypers(ls.detach().cpu().numpy(), float(var), float(noise), float(mean))
+        res = hip.gpr_objective_and_grad(with_grad=any(ctx.needs_input_grad[1:]))
+        model.last_bound = float(res.lml)
+        ctx.grads = res.grad
+        return torch.tensor(res.lml, dtype=torch.float64)
+
+    @staticmethod
+    def backward(ctx, gout):
+        g = ctx.grads
+        if g is None:
+            raise RuntimeError("gradient was not requested in forward")
+        gout = gout.to(torch.float64)
+        return (None, gout * torch.from_numpy(g["lengthscales"]), gout * g["variance"], gout * g["noise"], gout * g["mean"])
+
+
+class LogMarginalLikelihood(nn.Module):
+    """`LogMarginalLikelihood(model)(data)`: the exact log marginal likelihood of an ExactGPR model (gpflow GPR.log_marginal_likelihood).
+    `data` must be None or the model's own training set, as for LowerBoundCG."""
+
+    def __init__(self, model: ExactGPR):
+        if not isinstance(model, ExactGPR):
+            raise ValueError(f"ExactGPR model expected in the constructor of the {self.__class__}")
+        super().__init__()
+        object.__setattr__(self, "model", model)
+
+    def forward(self, data: Optional[Tuple[Tensor, Tensor]] = None) -> Tensor:
+        if data is not None:
+            self.model.check_same_data(data)
+        ls, var, noise, mean = self.model.hyper_tensors()
+        return _GPRFunction.apply(self.model, ls, var, noise, mean)
+
+
+class PredictGPR(nn.Module):
+    """predict_f of the exact model: mean c + K_*f K^-1 e, variance f - |L^-1 K_f*|^2.  The library keeps the factor of the last evaluation at
+    the current hyper-parameters and factors first if there is none."""
+
+    def __init__(self, model: ExactGPR):
+        if not isinstance(model, ExactGPR):
+            raise ValueError(f"ExactGPR model expected in the constructor of the {self.__class__}")
+        super().__init__()
+        object.__setattr__(self, "model", model)
+
+    def forward(self, xnew: Tensor, full_cov: bool = False, full_output_cov: bool = False) -> Tuple[Tensor, Tensor]:
+        if full_cov:
+            raise NotImplementedError("The predict_f method currently  supports only `full_cov=False` option")
+        with torch.no_grad():
+            self.model.push_hypers()
+            f_mean, f_var = self.model.hip.gpr_predict(xnew)
+        return f_mean.reshape(-1, 1), f_var.reshape(-1, 1)
+
+
+class PredictLogdensityGPR(PredictGPR):
+    def forward(self, data: Tuple[Tensor, Tensor], full_cov: bool = False, full_output_cov: bool = False):
+        if full_cov or full_output_cov:
+            raise NotImplementedError(
+                "The predict_log_density method currently supports only the argument values full_cov=False and full_output_cov=False")
+        x, y = data
+        f_mean, f_var = super().forward(x, full_cov=full_cov, full_output_cov=full_output_cov)
+        return log_density(self.model, y, f_mean, f_var)

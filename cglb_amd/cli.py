@@ -4,8 +4,12 @@ that exercise the hot path:
     python -m cglb_amd.cli -b hip -t fp64 -l LOGDIR -s SEED train -d DATASET -n STEPS cglb -k Matern32 -m cglb -i cv -M 1024
     python -m cglb_amd.cli -b hip -t fp64 -l LOGDIR metric -d DATASET cglb -k Matern32 -m cglb -i cv -M 1024 -p LOGDIR/model.json
     python -m cglb_amd.cli -b hip -t fp64 -l LOGDIR train -d DATASET -n STEPS sgpr -k Matern32 -m sgpr -i cv -M 1024
+    python -m cglb_amd.cli -b hip -t fp64 -l LOGDIR train -d DATASET -n STEPS gpr -k Matern32 -m gpr
+    python -m cglb_amd.cli -b hip -t fp64 -l LOGDIR gpr_metric -d DATASET -k Matern32 -p RUN/model.json
 
 `cglb -m` takes cglb | cglbn2m | cglbnm2, `sgpr -m` takes sgpr | sgprn2m (cli.py:203-209, :304-310; these four run on one rank).
+`gpr -m gpr` is the exact GP (cli.py:196-200, :293-311: dense Cholesky on the GPU, fp64, one rank); `gpr_metric` (cli.py:166-181) evaluates
+the exact lml, rmse and nlpd at parameters saved by ANY model class and writes gpr_metric.npy next to the parameter file.
 
 Same option letters as cli.py:60-65, :141-152, :207-216; writes model.json / results.json / logs.json with the reference's keys
 (cli.py:100-109, pytorch/interface.py:546-551).  Datasets: the reference downloads UCI sets through robustgp_experiments
@@ -32,7 +36,7 @@ from typing import Callable, Tuple
 import click
 import numpy as np
 
-from .backend import BACKENDS, INDUCING_VARIABLE_CONFIGS, KERNEL_CONFIGS, SGPR_CONFIGS, jsonio
+from .backend import BACKENDS, GPR_CONFIGS, INDUCING_VARIABLE_CONFIGS, KERNEL_CONFIGS, SGPR_CONFIGS, jsonio
 from .backend.callbacks import Logger
 from .data import synthetic_problem
 
@@ -243,10 +247,39 @@ def _sgpr_command(group):
     return sgpr
 
 
+def _gpr_command(group):
+    @group.command("gpr")
+    @click.option("-m", "--model-class", type=click.Choice(sorted(GPR_CONFIGS)), required=True)
+    @click.option("-k", "--kernel", type=click.Choice(sorted(KERNEL_CONFIGS)), required=True)
+    @click.option("-p", "--param_file", type=click.Path(readable=True))
+    @click.pass_context
+    def gpr(ctx, model_class, kernel, param_file):
+        """cli.py:196-200, :293-301 (_execute_cb_gpr): the exact GP; `exactgp` is listed like in the reference and raises NotImplementedError"""
+        _run_model(ctx, GPR_CONFIGS[model_class](KERNEL_CONFIGS[kernel]()), param_file)
+
+    return gpr
+
+
+@main.command("gpr_metric")
+@click.option("-d", "--dataset", type=str, required=True)
+@click.option("-k", "--kernel", type=click.Choice(sorted(KERNEL_CONFIGS)), required=True)
+@click.option("-p", "--param_file", type=click.Path(readable=True), required=True)
+@click.pass_context
+def gpr_metric(ctx, dataset, kernel, param_file):
+    """cli.py:166-181: the exact metrics (lml, rmse, nlpd) at the parameters of `param_file`, whichever model class saved them (an
+    inducing-point entry is ignored); the result goes to gpr_metric.npy next to that file."""
+    o = ctx.obj
+    bundle = get_dataset(dataset, o["seed"])
+    o.update(dataset=bundle, callback=create_metric_fn(o["backend"], bundle, Path(Path(param_file).parent, "gpr_metric.npy")))
+    _run_model(ctx, GPR_CONFIGS["gpr"](KERNEL_CONFIGS[kernel]()), param_file)
+
+
 _cglb_command(train)
 _cglb_command(metric)
 _sgpr_command(train)
 _sgpr_command(metric)
+_gpr_command(train)
+_gpr_command(metric)
 
 if __name__ == "__main__":
     main()

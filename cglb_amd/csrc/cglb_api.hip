@@ -1058,7 +1058,9 @@ int cglb_ctx_destroy(cglb_ctx* c) {
     if (c->stream) (void)hipStreamSynchronize(c->stream); else (void)hipDeviceSynchronize();
     comm_free(c);
     n2m_free(c);
+    gpr_free(c);
     c->mem.release();
+    for (hipEvent_t ev : c->gpr_ev) if (ev) (void)hipEventDestroy(ev);
     for (hipEvent_t ev : c->k1_events) (void)hipEventDestroy(ev);
     for (hipEvent_t ev : c->eval_events) (void)hipEventDestroy(ev);
     if (c->host_scal) (void)hipHostFree(c->host_scal);
@@ -1115,6 +1117,11 @@ int cglb_set_option(cglb_ctx* c, const char* name, int64_t value) {
         c->n2m_tile = value;
         c->have_terms = false;
     }
+    else if (!strcmp(name, "gpr_block")) {  // outer block edge of the exact GPR pipeline (kernels_gpr.hip); its buffers are sized by it
+        if (value < 64 || value > 4096 || value % 64 != 0) return cglb_fail(c, CGLB_ERR_BAD_ARG, "gpr_block must be a multiple of 64 in [64, 4096]");
+        if (value != c->gpr_block) gpr_free(c);
+        c->gpr_block = value;
+    }
     else if (!strcmp(name, "logdet_bound") || !strcmp(name, "quad_term")) {
         const bool ld = name[0] == 'l';
         if (value < 0 || value > (ld ? 2 : 1))
@@ -1164,6 +1171,7 @@ int cglb_set_data(cglb_ctx* c, const void* X, const void* y) {
         c->xradius2 = std::fmax(c->xradius2, r2);
     }
     c->have_data = true;
+    c->gpr_factored = false;
     c->p = 1;  // one target column again (cglb_set_targets)
     c->have_local = c->have_terms = false;
     return CGLB_OK;
@@ -1807,6 +1815,10 @@ int cglb_get_stat(cglb_ctx* c, const char* name, double* value) {
             if (!strcmp(name, names[k])) { CGLB_TRY(eval_collect(c)); *value = c->eval_ms[k]; return CGLB_OK; }
         if (!strcmp(name, "eval_count")) { CGLB_TRY(eval_collect(c)); *value = (double)c->eval_count; return CGLB_OK; }
     }
+    {
+        const int rc = gpr_stat(c, name, value);  // "gpr_bytes", "gpr_fill_ms" | "gpr_factor_ms" | "gpr_solve_ms" | "gpr_inverse_ms" | "gpr_grad_ms"
+        if (rc != -1) return rc;
+    }
     if (!strcmp(name, "k1_pairs_per_launch")) { *value = c->sym_pairs; return CGLB_OK; }  // of the most recent symmetric launch geometry
     if (!strcmp(name, "kpart_bytes")) { *value = (double)c->kpart_cap; return CGLB_OK; }     // partial-sum slabs of the mat-vec
     if (!strcmp(name, "comm_allreduce_calls")) { *value = c->comm ? (double)c->comm->n_allreduce : 0.0; return CGLB_OK; }
@@ -1865,6 +1877,7 @@ int cglb_set_targets(cglb_ctx* c, const void* Y, int p) {
     HIP_CHECK(c, hipMemcpyAsync(c->y, Y, col, hipMemcpyDefault, c->stream));  // column 0: what the single-column entry points see
     HIP_CHECK(c, hipStreamSynchronize(c->stream));                             // the caller owns Y again
     c->p = p;
+    c->gpr_factored = false;  // alpha = K^-1 (y - c) of the exact GPR class belongs to the old targets
     return CGLB_OK;
 }
 

@@ -59,6 +59,7 @@ struct cglb_ctx {
     cglb_comm_state* comm = nullptr;
     cglb_devpool mem;      // owns every device buffer below but the n2m_* ones; released by cglb_ctx_destroy
     cglb_devpool n2m_mem;  // owns the n2m_* buffers; released by n2m_free (a changed "n2m_tile" drops the tiles) and cglb_ctx_destroy
+    cglb_devpool gpr_mem;  // owns the gpr_* buffers (Xn, the N x N factor and inverse); released by gpr_free (a changed "gpr_block") and cglb_ctx_destroy
     // geometry
     int64_t N = 0, r0 = 0, r1 = 0, nloc = 0, lda = 0;  // lda: leading dimension of At/Guf (nloc rounded up to 8)
     int D = 0, Dp = 0, M = 0, dtype = CGLB_F64, kind = CGLB_RBF, device = 0;
@@ -197,6 +198,22 @@ struct cglb_ctx {
     int64_t n2m_bt = 0;    // tile edge of the K / G panels
     int64_t n2m_tile = 0;  // option "n2m_tile": requested tile edge (0: min(4096, N rounded up to 64))
     double n2m_tau = 0, n2m_BH = 0, n2m_trBinv = 0;  // tau = tr K~ - tr(C K~ C^T), <B^-1, H>, tr B^-1 (of the last setup)
+    // exact GPR (kernels_gpr.hip; cglb_gpr_*), fp64, one shard, one target column; everything allocated on first use
+    std::vector<double> gpr_ls;                         // lengthscales of cglb_gpr_set_hypers (host); its variance, noise and mean follow
+    double gpr_var = 1, gpr_noise = 1, gpr_mean = 0;
+    bool gpr_have_hypers = false, gpr_factored = false; // gpr_L / gpr_alpha hold chol(K) and K^-1 e at the current data and hypers
+    int64_t gpr_block = 2048;                           // option "gpr_block": outer block edge of the fill, the factorisation and the gradient pass
+    double *gpr_Xn = nullptr, *gpr_lsd = nullptr;       // X / l [N][D]; device lengthscales
+    double *gpr_L = nullptr, *gpr_Kinv = nullptr;       // N x N column-major, lower triangle: chol(K); K^-1 (gradient evaluations only)
+    double *gpr_blk = nullptr;                          // dense copy of the current diagonal block (edge gpr_block)
+    double *gpr_e = nullptr, *gpr_alpha = nullptr, *gpr_ones = nullptr;  // [N]: y - c, K^-1 e, ones
+    double *gpr_part = nullptr, *gpr_acc = nullptr, *gpr_scal = nullptr; // block partials [(block / 64)^2][D + 2], their sums [D + 2], scalars [8]
+    int* gpr_info = nullptr;                            // pivot status of the current diagonal block; potri status
+    double *gpr_Ks = nullptr, *gpr_xnew = nullptr;      // prediction: K_f* (N x batch, column-major) and the scaled new points
+    size_t gpr_Ks_cap = 0, gpr_xnew_cap = 0;
+    size_t gpr_bytes = 0;                               // device bytes the pool holds (cglb_get_stat "gpr_bytes")
+    hipEvent_t gpr_ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};  // start | fill | factor | solves | inverse | gradient of the last evaluation
+    int gpr_ev_last = 0;                                // index of the last event that evaluation recorded (2: no solve reached, 3: value only, 5: with gradient)
     std::string err;
 };
 
@@ -283,6 +300,9 @@ int wide_grad_panel(cglb_ctx* c, const void* G, int64_t ldg, const void* cvec, c
 int n2m_setup(cglb_ctx* c);  // W = K_ff A^T, H = A W, tau, <B^-1, H>, tr B^-1
 int n2m_grad_terms(cglb_ctx* c, const double* Binv);  // E (n2m_E, trace in n2m_scal[2]) and n2m_gacc[d] = sum_ij G_ij dK_ij/dl_d, G = C^T C
 void n2m_free(cglb_ctx* c);
+// exact GPR (kernels_gpr.hip): releases gpr_mem (the next evaluation allocates and factors again); the phase times of the last evaluation
+void gpr_free(cglb_ctx* c);
+int gpr_stat(cglb_ctx* c, const char* name, double* value);  // CGLB_OK if `name` is one of the gpr_* statistics, -1 if it is not
 
 // ---- launchers implemented in the kernel translation units (all enqueue on ctx->stream) ----------
 // kernels_prep.hip
@@ -294,6 +314,7 @@ int launch_kuu(cglb_ctx* c);  // Lc <- Kuu + jitter I (full symmetric)
 // kernels_kff.hip
 int launch_kff_matvec(cglb_ctx* c, const void* p_full, void* out_local, double* pdot_slot);
 int launch_cholesky_lower(cglb_ctx* c, void* A, int* info_slot);
+int launch_cholesky_lower_n(cglb_ctx* c, void* A, int n, int* info_slot);  // dense n x n, leading dimension n
 int launch_frag_prep(cglb_ctx* c);
 int launch_kff_sym(cglb_ctx* c, const void* p_full, void* out_local, double* pdot_slot);
 int launch_hot_weights(cglb_ctx* c);  // wh = 2^(xah/T) after set_hypers (RBF)

@@ -212,8 +212,7 @@ __global__ __launch_bounds__(256) void chol_update_kernel(T* __restrict__ A, int
 }
 
 template <typename T>
-static int cholesky_impl(cglb_ctx* c, T* A, int* info_slot) {
-    const int n = c->M;
+static int cholesky_impl(cglb_ctx* c, T* A, int n, int* info_slot) {
     CGLB_TRY(c->mem.alloc(c, &c->chol_blk, (CHOL_NB * CHOL_NB + CHOL_NB) * sizeof(double)));
     T* Dblk = (T*)c->chol_blk;
     HIP_CHECK(c, hipMemsetAsync(info_slot, 0, sizeof(int), c->stream));
@@ -236,5 +235,9 @@ static int cholesky_impl(cglb_ctx* c, T* A, int* info_slot) {
 // In-place lower Cholesky of the column-major M x M matrix `A`; *info_slot (device int) = 0 or 1 + index of the first
 // non-positive pivot.  A failed factorisation leaves garbage below the failing block (callers check info before use).
 int launch_cholesky_lower(cglb_ctx* c, void* A, int* info_slot) {
-    CGLB_DISPATCH_T(c->dtype, return cholesky_impl<T>(c, (T*)A, info_slot));
+    CGLB_DISPATCH_T(c->dtype, return cholesky_impl<T>(c, (T*)A, c->M, info_slot));
+}
+// the same for a dense n x n matrix with leading dimension n (the diagonal blocks of the exact GPR factorisation, kernels_gpr.hip)
+int launch_cholesky_lower_n(cglb_ctx* c, void* A, int n, int* info_slot) {
+    CGLB_DISPATCH_T(c->dtype, return cholesky_impl<T>(c, (T*)A, n, info_slot));
 }

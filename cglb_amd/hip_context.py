@@ -33,6 +33,14 @@ class ObjectiveResult:
     grad: Optional[dict]  # constrained-space gradient of `bound`
 
 
+@dataclass
+class GPRResult:
+    lml: float      # log marginal likelihood = quad + logdet - N/2 log 2 pi
+    quad: float     # -1/2 e^T K^-1 e
+    logdet: float   # -sum log diag chol(K) = -1/2 log|K|
+    grad: Optional[dict]  # d lml / d {lengthscales, variance, noise, mean}
+
+
 def _ptr(t: Optional[torch.Tensor]):
     return None if t is None else c_void_p(t.data_ptr())
 
@@ -265,6 +273,28 @@ class HipContext:
         v = self._dev(v_full, self.N)
         mean, var = self.empty(xn.shape[0]), self.empty(xn.shape[0])
         _lib.check(self.lib.cglb_predict(self._ctx, _ptr(v), _ptr(xn), xn.shape[0], _ptr(mean), _ptr(var)), self._ctx)
+        return mean, var
+
+    # -- exact GPR (cglb_gpr_*): dense Cholesky marginal likelihood, fp64, one rank, one target column; num_inducing is a placeholder ----
+    def gpr_set_hypers(self, lengthscales, variance, noise, mean):
+        ls = np.ascontiguousarray(np.broadcast_to(np.asarray(lengthscales, dtype=np.float64).reshape(-1), (self.D,)))
+        rc = self.lib.cglb_gpr_set_hypers(self._ctx, ls.ctypes.data_as(ctypes.POINTER(c_double)), float(variance), float(noise), float(mean))
+        _lib.check(rc, self._ctx)
+
+    def gpr_objective_and_grad(self, with_grad=True) -> GPRResult:
+        out3 = (c_double * 3)()
+        g = np.empty(self.D + 3, dtype=np.float64) if with_grad else None
+        rc = self.lib.cglb_gpr_objective_and_grad(self._ctx, out3, g.ctypes.data_as(ctypes.POINTER(c_double)) if with_grad else None)
+        _lib.check(rc, self._ctx)
+        D = self.D
+        grad = None if g is None else {"lengthscales": g[:D].copy(), "variance": float(g[D]), "noise": float(g[D + 1]), "mean": float(g[D + 2])}
+        return GPRResult(out3[0], out3[1], out3[2], grad)
+
+    def gpr_predict(self, xnew) -> Tuple[torch.Tensor, torch.Tensor]:
+        """predict_f mean and variance at xnew [n_new, D] from the factor of the last evaluation (factored first if there is none)."""
+        xn = torch.as_tensor(xnew, dtype=self.dtype).reshape(-1, self.D).contiguous().to(self.device)
+        mean, var = self.empty(xn.shape[0]), self.empty(xn.shape[0])
+        _lib.check(self.lib.cglb_gpr_predict(self._ctx, _ptr(xn), xn.shape[0], _ptr(mean), _ptr(var)), self._ctx)
         return mean, var
 
     def get_stat(self, name: str) -> float:

@@ -245,6 +245,26 @@ int cglb_predict_multi(cglb_ctx* ctx, const void* V, const void* xnew, int64_t n
 /* average duration (ms) of `reps` back-to-back products with s columns (pair kernel + slab combine), in the style of cglb_time_kernel(which = 0) */
 int cglb_time_matmat(cglb_ctx* ctx, int s, int reps, double* ms_avg);
 
+/* ---- exact GP regression: model class "gpr" (GPRConfig: cglb_experiments/cli.py:166-181, :196-200, :293-311; tensorflow/interface.py:200-206,
+ *      :386-395 - gpflow's GPR.log_marginal_likelihood; pytorch/interface.py:561-604 - ExactMarginalLogLikelihood times n) ---------------------
+ * K = variance kappa(X, X) + noise I = L L^T (dense, N x N, factored on the GPU), e = y - mean, alpha = K^-1 e,
+ * lml = -1/2 e^T alpha - sum log L_ii - N/2 log 2 pi.  fp64 contexts with one shard covering all rows, one rank and one target column;
+ * anything else returns CGLB_ERR_BAD_ARG.  The context is created like any other: this class has no inducing points, so the caller passes
+ * m = 1 as a placeholder, and none of these entry points calls cglb_setup or reads Z or the Nystrom panel.  Device memory: 8 N^2 bytes for
+ * the factor, 8 N^2 more once a gradient is asked for, checked against the free device memory before they are allocated; released by
+ * cglb_ctx_destroy and by a changed "gpr_block". */
+/* lengthscales: host double[d].  No inducing points, no jitter.  The noise need not be positive: a matrix that is not positive definite is
+ * reported by the evaluation (CGLB_ERR_NOT_PD with the row of the first non-positive pivot). */
+int cglb_gpr_set_hypers(cglb_ctx* ctx, const double* lengthscales, double variance, double noise, double mean);
+/* out3 = {lml, -1/2 e^T alpha, -sum log L_ii} (host).  grad: host double[d + 3] = d lml / d {lengthscales, variance, noise, mean}, or NULL
+ * (value only: no inverse is formed).  With W = alpha alpha^T - K^-1: 1/2 sum_ij W_ij dK_ij/dl_d, 1/2 sum_ij W_ij kappa_ij, 1/2 tr W,
+ * sum alpha.  Two evaluations of the same inputs return bitwise equal numbers. */
+int cglb_gpr_objective_and_grad(cglb_ctx* ctx, double* out3, double* grad);
+/* predict_f at new points (gpflow GPR.predict_f, full_cov = False): f_mean = mean + K_*f alpha, f_var = variance - |L^-1 K_f*|^2 column-wise.
+ * xnew: any [n_new, d]; f_mean, f_var: dev [n_new].  Uses the factor of the last evaluation at the current data and hyper-parameters and
+ * factors first if there is none. */
+int cglb_gpr_predict(cglb_ctx* ctx, const void* xnew, int64_t n_new, void* f_mean, void* f_var);
+
 /* ---- inducing-point initialisation: InducingVariableConfig.init, config.py:55-65 ------------------------
  * The reference calls robustgp.ConditionalVariance(sample=False) (third-party): greedy maximisation of the conditional
  * variance under the INITIAL kernel (pivoted Cholesky of K_ff, lowest index on ties).  Needs set_data only; works on all n rows
@@ -274,7 +294,10 @@ int cglb_time_kernel(cglb_ctx* ctx, int which, int reps, double* ms_avg);
  * the number of evaluations.  With p > 1 columns the third phase is K v alone and the fourth holds the column-by-column rest (preconditioner,
  * bound scalars and gradient of each column in turn);
  * "comm_allreduce_calls" | "comm_allgather_calls": collectives issued by the library since cglb_comm_init_*;
- * "L_diag_ratio": max/min of diag(chol(K_uu + jitter I)) of the last cglb_setup (a cheap proxy of cond(L)). */
+ * "L_diag_ratio": max/min of diag(chol(K_uu + jitter I)) of the last cglb_setup (a cheap proxy of cond(L));
+ * "gpr_bytes": device bytes the exact GPR class holds; "gpr_fill_ms" | "gpr_factor_ms" | "gpr_solve_ms" | "gpr_inverse_ms" | "gpr_grad_ms": device
+ * time (HIP events on the context stream) of the phases of the last cglb_gpr_objective_and_grad - tiles of K | factorisation | alpha and the
+ * scalars | K^-1 | gradient pass; 0 for a phase that evaluation did not run. */
 int cglb_get_stat(cglb_ctx* ctx, const char* name, double* value);
 /* Tunables: name = "kff_variant" | "kff_jsplit" | "kff_rows" | "sym_chunk" | "precond_mode" | "chol_mode" | "pcg_lookahead" | "sym_order" | "aat_block" | "grad_gram" | "k1_profile" |
  * "grad_trsm" (gradient algebra against L = chol(K_uu): 0 products with the explicit inverse, 1 backward-stable triangular solves, 2 = default:
@@ -303,6 +326,8 @@ int cglb_get_stat(cglb_ctx* ctx, const char* name, double* value);
  *  solve runs whatever run_cg says) and issue no N^2 work).  Both options at 0: every entry point behaves exactly as without them.  A
  *  non-zero value is refused on a context with more than one rank (cglb_set_parallel / cglb_comm_init_*), and both of those refuse a context
  *  that carries one;
+ * "gpr_block" (outer block edge of the exact GPR class: its tiles of K, the block columns of its factorisation and the tiles of its gradient
+ *  pass; a multiple of 64 in [64, 4096], default 2048; a changed value releases the buffers of that class);
  * returns CGLB_ERR_BAD_ARG if unknown. */
 int cglb_set_option(cglb_ctx* ctx, const char* name, int64_t value);
 
