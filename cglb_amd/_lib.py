@@ -99,6 +99,12 @@ SIGNATURES = {
     "cglb_gpr_set_hypers": (c_int, [c_void_p, POINTER(c_double), c_double, c_double, c_double]),
     "cglb_gpr_objective_and_grad": (c_int, [c_void_p, POINTER(c_double), POINTER(c_double)]),
     "cglb_gpr_predict": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
+    "cglb_itergp_objective_and_grad": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_double, c_int, c_int, POINTER(c_double), POINTER(c_double),
+                                               POINTER(c_int), POINTER(c_double)]),
+    "cglb_itergp_get_coefficients": (c_int, [c_void_p, POINTER(c_double), POINTER(c_double)]),
+    "cglb_itergp_predict": (c_int, [c_void_p, c_void_p, c_int64, c_double, c_int, c_void_p, c_void_p]),
+    "cglb_grad_kff_multi": (c_int, [c_void_p, c_void_p, c_void_p, c_int, POINTER(c_double)]),
+    "cglb_time_grad_kff_multi": (c_int, [c_void_p, c_int, c_int, POINTER(c_double)]),
 }
 
 _lib = None

@@ -19,7 +19,7 @@ import numpy as np
 
 __all__ = [
     "Config", "ModelConfig", "KernelConfig", "SquaredExponentialConfig", "Matern32Config", "CGLBConfig", "CGLBN2MConfig",
-    "CGLBNM2Config", "SGPRN2MConfig", "GPRConfig", "ExactGPConfig", "SGPRConfig", "InducingVariableConfig", "GPR_CONFIGS", "SGPR_CONFIGS",
+    "CGLBNM2Config", "SGPRN2MConfig", "GPRConfig", "ExactGPConfig", "IterGPRConfig", "SGPRConfig", "InducingVariableConfig", "GPR_CONFIGS", "SGPR_CONFIGS",
     "KERNEL_CONFIGS", "INDUCING_VARIABLE_CONFIGS",
 ]
 
@@ -78,7 +78,13 @@ def _gpr_params(self, data: Data):
 
 
 GPRConfig = _record("GPRConfig", (ModelConfig,), [("kernel", KernelConfig)], namespace={"params": _gpr_params}, doc="Exact GP regression.")
-ExactGPConfig = _record("ExactGPConfig", (GPRConfig,), doc="Exact GP (iterative baseline; out of scope here).")
+ExactGPConfig = _record("ExactGPConfig", (GPRConfig,), doc="Exact GP (gpytorch's iterative baseline; out of scope here: see IterGPRConfig).")
+IterGPRConfig = _record("IterGPRConfig", (GPRConfig,),
+                        [("num_probes", int, dataclasses.field(default=10)), ("prec_size", int, dataclasses.field(default=100)),
+                         ("max_error", float, dataclasses.field(default=1.0)), ("max_cg_iter", int, dataclasses.field(default=1000)),
+                         ("lanczos_iter", int, dataclasses.field(default=20)), ("seed", int, dataclasses.field(default=0))],
+                        doc="Iterative exact GP: batched CG with a pivoted-Cholesky preconditioner of rank prec_size (the reference's _prec_size() = 100) "
+                            "and stochastic Lanczos quadrature on num_probes probe vectors.")
 
 
 def _sgpr_params(self, data: Data):
@@ -104,7 +110,7 @@ CGLBNM2Config = _record("CGLBNM2Config", (CGLBConfig,), doc="Log-det ablation (o
 SGPRN2MConfig = _record("SGPRN2MConfig", (SGPRConfig,), doc="Log-det ablation (out of scope).")
 
 # registries: the keys are the reference's CLI choices (config.py:139-166)
-GPR_CONFIGS = dict(gpr=GPRConfig, exactgp=ExactGPConfig)
+GPR_CONFIGS = dict(gpr=GPRConfig, exactgp=ExactGPConfig, itergp=IterGPRConfig)
 SGPR_CONFIGS = dict(sgpr=SGPRConfig, cglb=CGLBConfig, sgprn2m=SGPRN2MConfig, cglbn2m=CGLBN2MConfig, cglbnm2=CGLBNM2Config)
 KERNEL_CONFIGS = {"SquaredExponential": SquaredExponentialConfig, "Matern32": Matern32Config, "mat32": Matern32Config,
                   "rbf": SquaredExponentialConfig}

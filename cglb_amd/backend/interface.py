@@ -1,7 +1,7 @@
 """Backend interface for the HIP path — mirror of cglb/backend/pytorch/interface.py restricted to what the CGLB
 path needs: configure_backend, set_default_float/jitter, get_default_float(_str), create_kernel,
-create_model (all five classes of SGPR_CONFIGS: cglb, cglbn2m, cglbnm2, sgpr, sgprn2m, and the exact `gpr` class of GPR_CONFIGS), model_parameters, optimize (SciPy L-BFGS-B, four-round schedule :445-543), save, load,
-metrics_fn (:607-658).  gpytorch's iterative `exactgp` baseline / Adam / MultiDeviceKernel branches are out of scope and raise NotImplementedError,
+create_model (all five classes of SGPR_CONFIGS: cglb, cglbn2m, cglbnm2, sgpr, sgprn2m, and the exact `gpr` and iterative `itergp` classes of GPR_CONFIGS), model_parameters, optimize (SciPy L-BFGS-B, four-round schedule :445-543; `adam_<lr>` for itergp), save, load,
+metrics_fn (:607-658).  gpytorch's own `exactgp` baseline / MultiDeviceKernel branches are out of scope and raise NotImplementedError,
 like the reference's unregistered singledispatch defaults (:120-147).
 """
 from __future__ import annotations
@@ -19,11 +19,11 @@ import torch
 
 from . import jsonio, metric
 from .callbacks import Logger
-from .config import (CGLBConfig, CGLBN2MConfig, CGLBNM2Config, ExactGPConfig, GPRConfig, KernelConfig, Matern32Config, ModelConfig, SGPRConfig,
+from .config import (CGLBConfig, CGLBN2MConfig, CGLBNM2Config, ExactGPConfig, GPRConfig, IterGPRConfig, KernelConfig, Matern32Config, ModelConfig, SGPRConfig,
                      SGPRN2MConfig, SquaredExponentialConfig)
-from .models import (CGLB, CGLBN2M, CGLBNM2, GPR, SGPR, SGPRN2M, BaseKernel, ExactGPR, GaussianLikelihood, InducingPointKernel,
-                     LogMarginalLikelihood, LowerBoundCG, LowerBoundSGPR, PredictCG, PredictGPR, PredictSGPR, ScaleKernel, get_cholesky_jitter,
-                     log_density, set_cholesky_jitter)
+from .models import (CGLB, CGLBN2M, CGLBNM2, GPR, SGPR, SGPRN2M, BaseKernel, ExactGPR, GaussianLikelihood, InducingPointKernel, IterGPR,
+                     LogMarginalLikelihood, LowerBoundCG, LowerBoundSGPR, PredictCG, PredictGPR, PredictIterGPR, PredictSGPR, ScaleKernel,
+                     StochasticLogMarginalLikelihood, get_cholesky_jitter, log_density, set_cholesky_jitter)
 from .optimizer import Scipy
 
 __all__ = ["create_kernel", "create_model", "optimize", "save", "load", "metrics_fn"]
@@ -253,6 +253,21 @@ def _create_model_exactgp(model_cfg: ExactGPConfig, data: Data):
                               "use 'gpr', the dense Cholesky exact GP")
 
 
+@create_model.register
+def _create_model_itergp(model_cfg: IterGPRConfig, data: Data):
+    """The iterative exact GP in the library's own estimator (pytorch/interface.py:233-260 builds the reference's on gpytorch): the noise bound
+    1e-4 of the reference's exactgp, constant mean, no inducing points.  One rank, fp64."""
+    _require_one_rank("itergp")
+    if _STATE["dtype"] != torch.float64:
+        raise ValueError("model class 'itergp' needs fp64: run with -t fp64")
+    likelihood = GaussianLikelihood(lower_bound=1e-4)
+    likelihood.noise = model_cfg.params(data)["noise_variance"]
+    kernel = create_kernel(model_cfg.kernel, data)
+    return IterGPR((np.asarray(data[0]), _targets(data[1])), likelihood, kernel, dtype=_STATE["dtype"], num_probes=model_cfg.num_probes,
+                   prec_size=model_cfg.prec_size, max_error=model_cfg.max_error, max_cg_iter=model_cfg.max_cg_iter,
+                   lanczos_iter=model_cfg.lanczos_iter, seed=model_cfg.seed)
+
+
 def _targets(y) -> np.ndarray:
     """Targets as the models take them: [N, P] stays 2-D for P > 1, a single column (either shape) is the flat vector it always was."""
     y = np.asarray(y)
@@ -357,7 +372,7 @@ def _assert_ranks_agree(model: CGLB, what: str):
 def _optimize_cglb_impl(model: CGLB, dataset, num_steps: int, logger: Logger, optimize: str = "scipy"):
     """interface.py:445-543: warm-up evaluation outside the clock, then up to four L-BFGS-B rounds, the last two
     without the inducing points."""
-    assert optimize == "scipy"
+    _require_scipy(model, optimize)
     lbfgs = Scipy()
     lower_bound = LowerBoundCG(model)
     results = []
@@ -404,7 +419,7 @@ def _optimize_cglb_impl(model: CGLB, dataset, num_steps: int, logger: Logger, op
 def _optimize_sgpr(model: SGPR, dataset, num_steps: int, logger: Logger, optimize: str = "scipy"):
     """The same L-BFGS-B rounds as CGLB without the v bookkeeping (the TF backend trains every class this way,
     tensorflow/interface.py:296-337)."""
-    assert optimize == "scipy"
+    _require_scipy(model, optimize)
     with _narrow_host_pools():
         lbfgs = Scipy()
         bound = LowerBoundSGPR(model)
@@ -434,7 +449,7 @@ def _optimize_sgpr(model: SGPR, dataset, num_steps: int, logger: Logger, optimiz
 @optimize.register
 def _optimize_gpr(model: ExactGPR, dataset, num_steps: int, logger: Logger, optimize: str = "scipy"):
     """The L-BFGS-B rounds of `_optimize_sgpr` on loss = -lml; there are no inducing points to leave out of the later rounds."""
-    assert optimize == "scipy"
+    _require_scipy(model, optimize)
     with _narrow_host_pools():
         lbfgs = Scipy()
         lml = LogMarginalLikelihood(model)
@@ -456,6 +471,56 @@ def _optimize_gpr(model: ExactGPR, dataset, num_steps: int, logger: Logger, opti
             remaining -= result.nit
             results.append(result)
         return results
+
+
+def _require_scipy(model, optimizer: str):
+    """The classes with an exact gradient train with L-BFGS-B only; `adam_<lr>` belongs to the iterative class."""
+    if optimizer != "scipy":
+        raise ValueError(f"optimizer {optimizer!r} is not available for {type(model).__name__}: this class trains with 'scipy' (L-BFGS-B); "
+                         f"'adam_<lr>' is the optimizer of model class 'itergp' (gpr -m itergp)")
+
+
+def adam_learning_rate(optimizer: str) -> float:
+    """The learning rate of an `adam_<lr>` optimizer name (pytorch/interface.py:561-604 parses the same form); ValueError otherwise."""
+    name, _, lr = str(optimizer).partition("_")
+    try:
+        value = float(lr)
+    except ValueError:
+        value = -1.0
+    if name != "adam" or not value > 0.0:
+        raise ValueError(f"optimizer {optimizer!r}: expected adam_<learning rate>, e.g. adam_0.1")
+    return value
+
+
+@optimize.register
+def _optimize_itergp(model: IterGPR, dataset, num_steps: int, logger: Logger, optimize: str = "adam_0.1"):
+    """`num_steps` Adam steps on the full training set with fresh probes at every step - the last phase of the reference's exactgp training
+    (pytorch/interface.py:561-604); its L-BFGS and subset phases are out of scope.  L-BFGS-B is refused: it needs gradients that are the
+    derivative of the value it is given, and this class returns an unbiased gradient estimate next to a separately estimated value."""
+    if optimize == "scipy":
+        raise ValueError("model class 'itergp' cannot be trained with -o scipy: its gradient is a stochastic estimate and not the derivative of "
+                         "the returned value, which the L-BFGS-B line search assumes; use -o adam_<lr>, e.g. adam_0.1")
+    lr = adam_learning_rate(optimize)
+    with _narrow_host_pools():
+        lml = StochasticLogMarginalLikelihood(model)
+        params = list(model.parameters())
+        adam = torch.optim.Adam(params, lr=lr)
+        with logger.no_recording():
+            torch.autograd.grad(-lml(None), params)
+            torch.cuda.synchronize()
+        logger.timer.reset()
+        logger.timer.start()
+        losses = []
+        for step in range(num_steps):
+            adam.zero_grad()
+            loss = -lml(None)
+            loss.backward()
+            stats = model.cg_stats
+            logger.log_for_feval(steps=stats.steps, residual_error=stats.residual_error)
+            adam.step()
+            losses.append(float(loss.detach()))
+            logger(step)
+        return losses
 
 
 @save.register
@@ -493,6 +558,9 @@ def _load_gpr(model: ExactGPR, filepath: str):
     return model
 
 
+load.register(IterGPR, _load_gpr)   # the same module tree and parameter keys
+
+
 @metrics_fn.register
 def _compute_metrics_gpr(model: ExactGPR, dataset_bundle):
     """tensorflow/interface.py:386-395: lml, loss = -lml, and rmse / nlpd of the exact predictive on the train and test sets."""
@@ -516,6 +584,33 @@ def _compute_metrics_gpr(model: ExactGPR, dataset_bundle):
         return (err[:n], err[n:]), (lpd[:n], lpd[n:])
 
     return lambda: metric.call_metric_fns(gpr_metrics, metric.rmse_and_lpd_fn(error_and_logdensity))
+
+
+@metrics_fn.register
+def _compute_metrics_itergp(model: IterGPR, dataset_bundle):
+    """The metrics of the exact class from the iterative estimator: lml (one draw of the probes), loss = -lml, and rmse / nlpd of the predictive
+    on the train and test sets; the variances cost (n_train + n_test) / 8 batched solves."""
+    train, test = dataset_bundle
+
+    def itergp_metrics():
+        with torch.no_grad():
+            lml = _numpy(StochasticLogMarginalLikelihood(model)(None))
+        stats = model.cg_stats
+        return {"lml": lml, "loss": -lml, "cg/steps": stats.steps, "cg/error": stats.residual_error}
+
+    x_full = np.concatenate([np.asarray(train[0]), np.asarray(test[0])], axis=0)
+    y_full = np.concatenate([np.asarray(train[1]).reshape(-1), np.asarray(test[1]).reshape(-1)], axis=0).reshape(-1, 1)
+
+    def error_and_logdensity():
+        predict_f = PredictIterGPR(model)
+        with torch.no_grad():
+            f_mean, f_var = predict_f(torch.as_tensor(x_full))
+            y = torch.as_tensor(y_full, dtype=f_mean.dtype, device=f_mean.device)
+            lpd, err = _numpy(log_density(model, y, f_mean, f_var)), _numpy(y - f_mean)
+        n = np.asarray(train[0]).shape[0]
+        return (err[:n], err[n:]), (lpd[:n], lpd[n:])
+
+    return lambda: metric.call_metric_fns(itergp_metrics, metric.rmse_and_lpd_fn(error_and_logdensity))
 
 
 @metrics_fn.register

@@ -644,3 +644,123 @@ class PredictLogdensityGPR(PredictGPR):
         x, y = data
         f_mean, f_var = super().forward(x, full_cov=full_cov, full_output_cov=full_output_cov)
         return log_density(self.model, y, f_mean, f_var)
+
+
+class IterGPR(GPR):
+    """Iterative exact GP regression: the "Iterative GP" baseline (pytorch/interface.py:233-260 builds it on gpytorch's ExactGP with a
+    pivoted-Cholesky preconditioner of rank `_prec_size()` = 100, batched CG and stochastic Lanczos quadrature).  The module tree and parameter
+    keys of ExactGPR; O(N) memory.  The estimator is the library's (cglb_itergp_*: fp64, one rank, one target column): `num_probes` probe
+    vectors drawn on the host from this model's generator, one batched solve warm-started at the persistent `v_vec`, the log-determinant from
+    the Lanczos coefficients of the solve.  gpytorch's random numbers and stop rule are not reproduced."""
+
+    def __init__(self, data: Data, likelihood: GaussianLikelihood, kernel: ScaleKernel, dtype: torch.dtype = torch.float64,
+                 device: Optional[torch.device] = None, context=None, num_probes: int = 10, prec_size: int = 100, max_error: float = 1.0,
+                 max_cg_iter: int = 1000, lanczos_iter: int = 20, seed: int = 0, deterministic_probes: bool = False):
+        super().__init__(data, likelihood, kernel)
+        self.dtype = dtype
+        if self.num_outputs > 1:
+            raise NotImplementedError("IterGPR is not available for more than one target column (only CGLB takes [N, P] targets)")
+        if dtype != torch.float64:
+            raise ValueError("the iterative exact GP class needs fp64 (-t fp64)")
+        n = int(self.train_inputs[0].shape[0])
+        self.num_probes, self.prec_size = int(num_probes), min(int(prec_size), n)
+        self.max_error, self.max_cg_iter, self.lanczos_iter = float(max_error), int(max_cg_iter), int(lanczos_iter)
+        if context is None:
+            import torch.distributed as dist
+            if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+                raise NotImplementedError("IterGPR is not available on more than one rank (only CGLB runs row-sharded); run it as a single process")
+            context = HipContext(self.train_inputs[0], self.train_targets, self.prec_size, kernel.base_kernel.kind, dtype=dtype, device=device)
+        elif getattr(context, "world", 1) > 1:
+            raise NotImplementedError("IterGPR is not available on more than one rank (only CGLB runs row-sharded)")
+        self.hip = context
+        self.register_buffer("v_vec", torch.zeros(n, dtype=dtype, device=context.device), persistent=False)   # the warm start of the data column
+        self.generator = torch.Generator(device="cpu")
+        self.generator.manual_seed(int(seed))
+        self.deterministic_probes = bool(deterministic_probes)
+        self._eps = None
+        self.cg_stats: Optional[ConjugateGradientStats] = None
+        self._placeholder_Z = self.train_inputs[0][:self.prec_size].detach().cpu().to(torch.float64)   # replaced by the pivots at every evaluation
+        self._pushed = None
+
+    check_same_data = SGPR.check_same_data
+    hyper_tensors = ExactGPR.hyper_tensors
+
+    def probes(self) -> Tensor:
+        """[num_probes, prec_size + N] standard-normal draws: fresh at every call, or one draw kept when `deterministic_probes`."""
+        if self._eps is None or not self.deterministic_probes:
+            self._eps = torch.randn(self.num_probes, self.prec_size + self.hip.N, dtype=torch.float64, generator=self.generator)
+        return self._eps
+
+    def push_hypers(self, jitter: float):
+        """Hands the hyper-parameters to the library unless these very values are already there: a new set_hypers would make the library
+        forget the preconditioner and the alpha of its last evaluation, which the predictive solve starts from."""
+        ls, var, noise, mean = [t.detach() for t in self.hyper_tensors()]
+        key = (ls.cpu().numpy().tobytes(), float(var), float(noise), float(mean), float(jitter))
+        if key != self._pushed:
+            self.hip.set_hypers(ls.cpu().numpy(), float(var), float(noise), float(mean), self._placeholder_Z, jitter)
+            self._pushed = key
+
+
+class _IterGPRFunction(torch.autograd.Function):
+    """The stochastic estimate of lml(lengthscales, variance, noise, mean) with the library's unbiased gradient estimate: the backward is NOT
+    the derivative of the forward value (the log-determinant estimate and its gradient use the same probes in different estimators)."""
+
+    @staticmethod
+    def forward(ctx, model, ls, var, noise, mean):
+        hip = model.hip
+        model.push_hypers(get_cholesky_jitter())
+        res = hip.itergp_objective_and_grad(model.probes(), model.v_vec, model.max_error, model.max_cg_iter, model.lanczos_iter,
+                                            with_grad=any(ctx.needs_input_grad[1:]))
+        model.last_bound = float(res.lml)
+        model.cg_stats = ConjugateGradientStats(steps=res.steps, residual_error=res.residual_error)
+        ctx.grads = res.grad
+        return torch.tensor(res.lml, dtype=torch.float64)
+
+    backward = _GPRFunction.backward
+
+
+class StochasticLogMarginalLikelihood(nn.Module):
+    """`StochasticLogMarginalLikelihood(model)(data)`: the iterative estimate of the log marginal likelihood of an IterGPR model.  `data` must
+    be None or the model's own training set, as for LowerBoundCG."""
+
+    def __init__(self, model: IterGPR):
+        if not isinstance(model, IterGPR):
+            raise ValueError(f"IterGPR model expected in the constructor of the {self.__class__}")
+        super().__init__()
+        object.__setattr__(self, "model", model)
+
+    def forward(self, data: Optional[Tuple[Tensor, Tensor]] = None) -> Tensor:
+        if data is not None:
+            self.model.check_same_data(data)
+        ls, var, noise, mean = self.model.hyper_tensors()
+        return _IterGPRFunction.apply(self.model, ls, var, noise, mean)
+
+
+class PredictIterGPR(nn.Module):
+    """predict_f of the iterative model: mean c + K_*f alpha from one solve at `max_error` (1e-3 like PredictCG), warm-started at the alpha of
+    the last evaluation, and the variances f - k_*^T K^-1 k_* by batched solves, 8 new points at a time: n_new / 8 solves per call."""
+
+    def __init__(self, model: IterGPR, max_error: float = 1e-3):
+        if not isinstance(model, IterGPR):
+            raise ValueError(f"IterGPR model expected in the constructor of the {self.__class__}")
+        super().__init__()
+        object.__setattr__(self, "model", model)
+        self.max_error = float(max_error)
+
+    def forward(self, xnew: Tensor, full_cov: bool = False, full_output_cov: bool = False) -> Tuple[Tensor, Tensor]:
+        if full_cov:
+            raise NotImplementedError("The predict_f method currently  supports only `full_cov=False` option")
+        with torch.no_grad():
+            self.model.push_hypers(get_cholesky_jitter())
+            f_mean, f_var = self.model.hip.itergp_predict(xnew, self.max_error, self.model.max_cg_iter)
+        return f_mean.reshape(-1, 1), f_var.reshape(-1, 1)
+
+
+class PredictLogdensityIterGPR(PredictIterGPR):
+    def forward(self, data: Tuple[Tensor, Tensor], full_cov: bool = False, full_output_cov: bool = False):
+        if full_cov or full_output_cov:
+            raise NotImplementedError(
+                "The predict_log_density method currently supports only the argument values full_cov=False and full_output_cov=False")
+        x, y = data
+        f_mean, f_var = super().forward(x, full_cov=full_cov, full_output_cov=full_output_cov)
+        return log_density(self.model, y, f_mean, f_var)

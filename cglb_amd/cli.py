@@ -6,6 +6,7 @@ that exercise the hot path:
     python -m cglb_amd.cli -b hip -t fp64 -l LOGDIR train -d DATASET -n STEPS sgpr -k Matern32 -m sgpr -i cv -M 1024
     python -m cglb_amd.cli -b hip -t fp64 -l LOGDIR train -d DATASET -n STEPS gpr -k Matern32 -m gpr
     python -m cglb_amd.cli -b hip -t fp64 -l LOGDIR gpr_metric -d DATASET -k Matern32 -p RUN/model.json
+    python -m cglb_amd.cli -b hip -t fp64 -l LOGDIR train -d DATASET -n STEPS -o adam_0.1 gpr -k Matern32 -m itergp
 
 `cglb -m` takes cglb | cglbn2m | cglbnm2, `sgpr -m` takes sgpr | sgprn2m (cli.py:203-209, :304-310; these four run on one rank).
 `gpr -m gpr` is the exact GP (cli.py:196-200, :293-311: dense Cholesky on the GPU, fp64, one rank); `gpr_metric` (cli.py:166-181) evaluates
@@ -177,9 +178,14 @@ def main(ctx, backend, float_type, logdir, seed, keops):
 @main.group()
 @click.option("-n", "--num-steps", default=100, type=int)
 @click.option("-d", "--dataset", type=str, required=True)
-@click.option("-o", "--optimizer", type=click.Choice(["scipy"]), default="scipy")
+@click.option("-o", "--optimizer", type=str, default="scipy", help="scipy (L-BFGS-B) or adam_<lr>, e.g. adam_0.1 (model class itergp)")
 @click.pass_context
 def train(ctx, dataset, num_steps, optimizer):
+    if optimizer != "scipy":
+        try:
+            ctx.obj["backend"].interface().adam_learning_rate(optimizer)
+        except ValueError as exc:
+            raise click.BadParameter(str(exc), param_hint="-o")
     o = ctx.obj
     bundle = get_dataset(dataset, o["seed"])
     o.update(dataset=bundle, callback=create_optimize_fn(o["backend"], bundle, o["logdir"], num_steps, optimizer))
@@ -254,7 +260,8 @@ def _gpr_command(group):
     @click.option("-p", "--param_file", type=click.Path(readable=True))
     @click.pass_context
     def gpr(ctx, model_class, kernel, param_file):
-        """cli.py:196-200, :293-301 (_execute_cb_gpr): the exact GP; `exactgp` is listed like in the reference and raises NotImplementedError"""
+        """cli.py:196-200, :293-301 (_execute_cb_gpr): the exact GP; `exactgp` is listed like in the reference and raises NotImplementedError;
+        `itergp` is the iterative exact GP in the library's own estimator (train with -o adam_<lr>)"""
         _run_model(ctx, GPR_CONFIGS[model_class](KERNEL_CONFIGS[kernel]()), param_file)
 
     return gpr

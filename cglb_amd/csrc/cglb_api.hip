@@ -9,6 +9,7 @@
 
 #include "devmath.h"
 #include "dispatch.h"
+#include "slq_host.h"
 
 namespace {
 
@@ -381,6 +382,7 @@ struct pcg_ops {
     bool dot_fused;         // false: pdot_slot is ignored and a launch_dot follows the mat-vec
     int (*direction)(cglb_ctx* c, const pcg_ops& o, double* rz_new, const double* rz_old, int restart);  // z = P r, rz_new = r.z, p = z (+ p rz_new / rz_old)
     bool rz_must_be_finite; // N ranks leave the loop together or not at all: a non-finite r^T P r is CGLB_ERR_COMM, not a quiet end
+    pcg_log* log = nullptr; // optional: receives rz_b before every iteration and after the last, and p_b.Ap_b of every iteration (host_pap: [s] pinned)
 };
 
 int fused_direction(cglb_ctx* c, const pcg_ops& o, double* rz_new, const double* rz_old, int restart) {
@@ -421,6 +423,10 @@ int pcg_solve(cglb_ctx* c, const pcg_ops& o, const void* b, void* v, double max_
         return t;
     };
     CGLB_TRY(read_scalars(c, s_rz, o.host, o.s));
+    if (o.log) {
+        o.log->rz.assign(o.host, o.host + o.s);
+        o.log->pap.clear();
+    }
     double rz = host_sum();
     if (o.rz_must_be_finite && !std::isfinite(rz)) return cglb_fail(c, CGLB_ERR_COMM, "r^T P r is not finite at the start of the solve");
     // The stop predicate (:65) is evaluated on the host, like the reference's (:80-81).  Look-ahead: while the residual is
@@ -432,6 +438,7 @@ int pcg_solve(cglb_ctx* c, const pcg_ops& o, const void* b, void* v, double max_
     while (0.5 * rz > max_error && i < max_iter) {  // :65
         if (!ahead) CGLB_TRY(o.matvec(c, o, o.p, o.Ap, o.pap));                                     // :66 and (p*Ap).sum() where fused
         if (!o.dot_fused) CGLB_TRY(launch_dot(c, o.p, o.Ap, o.n, o.pap, o.s));                      // :67
+        if (o.log) HIP_CHECK(c, hipMemcpyAsync(o.log->host_pap, o.pap, sizeof(double) * o.s, hipMemcpyDeviceToHost, c->stream));  // before a look-ahead product rewrites the slot
         const int restart = (restart_iter > 0) && (i % restart_iter == restart_iter - 1);          // :70
         CGLB_TRY(launch_update_v_r(c, v, o.r, o.p, o.Ap, s_rz, o.pap, !restart, o.n, o.s));         // :67-68, :72
         if (restart) {
@@ -446,6 +453,10 @@ int pcg_solve(cglb_ctx* c, const pcg_ops& o, const void* b, void* v, double max_
         if (ahead) CGLB_TRY(o.matvec(c, o, o.p, o.Ap, o.pap));
         HIP_CHECK(c, hipEventSynchronize(c->scal_event));                                            // host test of :65 (and the sync of :80-81)
         rz = host_sum();  // N ranks: a function of all-gathered numbers only, so every rank reads the same value and leaves the loop together
+        if (o.log) {
+            o.log->pap.insert(o.log->pap.end(), o.log->host_pap, o.log->host_pap + o.s);
+            o.log->rz.insert(o.log->rz.end(), o.host, o.host + o.s);
+        }
         if (o.rz_must_be_finite && !std::isfinite(rz)) return cglb_fail(c, CGLB_ERR_COMM, "r^T P r is not finite after iteration " + std::to_string(i));
         ++i;
     }
@@ -973,6 +984,105 @@ int time_repeated(cglb_ctx* c, int reps, F once, double* ms_avg) {
     return rc;
 }
 
+// ================================ iterative exact GP: batched CG with Lanczos log-det (include/cglb_hip.h) ================================
+__global__ __launch_bounds__(256) void negate_kernel(const double* __restrict__ x, int n, double* __restrict__ out) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) out[i] = -x[i];
+}
+// U[b] = a_b V[b] with a_0 = a0 and a_b = a for the probe columns: the left vectors (alpha / 2, -a_i / (2 t)) of the gradient's bilinear forms
+__global__ __launch_bounds__(256) void itergp_left_kernel(const double* __restrict__ V, int64_t n, int s, double a0, double a, double* __restrict__ U) {
+    const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx < n * s) U[idx] = (idx < n ? a0 : a) * V[idx];
+}
+// out[0] = sum_i x_i (one block, fixed order)
+__global__ __launch_bounds__(256) void vec_sum_kernel(const double* __restrict__ x, int64_t n, double* __restrict__ out) {
+    __shared__ double smem[16];
+    double s = 0.0;
+    for (int64_t i = threadIdx.x; i < n; i += blockDim.x) s += x[i];
+    s = block_sum(s, smem);
+    if (threadIdx.x == 0) out[0] = s;
+}
+// x += a (prediction mean);  out[b] = f - q[b] (prediction variance of one group of new points)
+__global__ __launch_bounds__(256) void add_scalar_kernel(double* __restrict__ x, int64_t n, double a) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) x[i] += a;
+}
+__global__ void itergp_var_kernel(const double* __restrict__ q, int n, double f, double* __restrict__ out) {
+    if ((int)threadIdx.x < n) out[threadIdx.x] = f - q[threadIdx.x];
+}
+
+// the scope of the class: what more than one column needs (one shard, one rank, the default bound), fp64, one target column, the stored panel
+int require_itergp_ok(cglb_ctx* c) {
+    CGLB_TRY(require_multi_ok(c));
+    if (c->dtype != CGLB_F64)
+        return cglb_fail(c, CGLB_ERR_BAD_ARG, "the iterative exact GP class needs an fp64 context (-t fp64): its Lanczos coefficients are differences of fp64 recurrences");
+    if (c->p != 1) return cglb_fail(c, CGLB_ERR_BAD_ARG, "the iterative exact GP class takes one target column");
+    if (c->precond_mode != 0) return cglb_fail(c, CGLB_ERR_BAD_ARG, "the iterative exact GP class needs the stored panel A (precond_mode 0): its probes are formed from it");
+    if (c->M > c->N) return cglb_fail(c, CGLB_ERR_BAD_ARG, "the preconditioner rank (the context's m) must not exceed the number of training points");
+    if (!c->have_data || !c->have_hypers) return cglb_fail(c, CGLB_ERR_STATE, "set_data and set_hypers must precede the iterative exact GP class");
+    return CGLB_OK;
+}
+
+int itergp_mark(cglb_ctx* c, int k) {
+    if (!c->it_ev[k]) HIP_CHECK(c, hipEventCreate(&c->it_ev[k]));
+    HIP_CHECK(c, hipEventRecord(c->it_ev[k], c->stream));
+    c->it_ev_last = k;
+    return CGLB_OK;
+}
+
+// "itergp_select_ms" | "itergp_solve_ms" | "itergp_grad_ms" of the last evaluation (0 for a phase it did not run); -1: not one of these names
+int itergp_stat(cglb_ctx* c, const char* name, double* value) {
+    static const char* names[] = {"itergp_select_ms", "itergp_solve_ms", "itergp_grad_ms"};
+    for (int k = 0; k < 3; ++k) {
+        if (strcmp(name, names[k])) continue;
+        *value = 0.0;
+        if (c->it_ev_last > k) {
+            float ms = 0.f;
+            HIP_CHECK(c, hipEventSynchronize(c->it_ev[c->it_ev_last]));
+            HIP_CHECK(c, hipEventElapsedTime(&ms, c->it_ev[k], c->it_ev[k + 1]));
+            *value = ms;
+        }
+        return CGLB_OK;
+    }
+    return -1;
+}
+
+// P = Q_ff + noise I under the current hyper-parameters: Z = the M greedily selected training points (the pivoted Cholesky of K_ff of rank M,
+// kernels_select.hip, reading the scaled inputs set_hypers left), then the common terms of the Nystrom preconditioner
+int itergp_common_terms(cglb_ctx* c) {
+    {
+        long long* chosen_dev = nullptr;
+        double* trace_dev = nullptr;
+        DevTemps tmp;
+        CGLB_TRY(tmp.alloc(c, (void**)&chosen_dev, (size_t)c->M * sizeof(long long)));
+        CGLB_TRY(tmp.alloc(c, (void**)&trace_dev, sizeof(double)));
+        CGLB_TRY(launch_select_inducing(c, c->var, c->jitter, chosen_dev, c->Z, trace_dev));  // blocking
+    }
+    if (is_wide(c)) {
+        CGLB_TRY(wide_after_hypers(c));
+    } else {
+        CGLB_TRY(launch_prep_scaled(c, c->Z, c->M, c->Zs, c->za));
+        CGLB_TRY(launch_prep_scaled(c, c->Z, c->M, c->Zh, c->zah, true));
+    }
+    c->have_local = c->have_terms = false;
+    return cglb_setup(c);
+}
+
+int itergp_reserve(cglb_ctx* c, int s, size_t eps_doubles) {
+    const size_t col = (size_t)c->N * sizeof(double);
+    CGLB_TRY(c->mem.reserve(c, &c->it_V, &c->it_V_cap, (size_t)s * col));
+    CGLB_TRY(c->mem.reserve(c, &c->it_eps, &c->it_eps_cap, eps_doubles * sizeof(double)));
+    CGLB_TRY(c->mem.reserve(c, &c->it_scal, &c->it_scal_cap, (size_t)(c->D + 3 + s + 8) * sizeof(double)));
+    CGLB_TRY(c->mem.alloc(c, &c->it_alpha, col));
+    if (c->it_log.host_cap < s) {
+        if (c->it_log.host_pap) (void)hipHostFree(c->it_log.host_pap);
+        c->it_log.host_pap = nullptr; c->it_log.host_cap = 0;
+        HIP_CHECK(c, hipHostMalloc((void**)&c->it_log.host_pap, (size_t)s * sizeof(double), hipHostMallocDefault));
+        c->it_log.host_cap = s;
+    }
+    return CGLB_OK;
+}
+
 }  // namespace
 
 // =================================================== C ABI ====================================================
@@ -1061,6 +1171,8 @@ int cglb_ctx_destroy(cglb_ctx* c) {
     gpr_free(c);
     c->mem.release();
     for (hipEvent_t ev : c->gpr_ev) if (ev) (void)hipEventDestroy(ev);
+    for (hipEvent_t ev : c->it_ev) if (ev) (void)hipEventDestroy(ev);
+    if (c->it_log.host_pap) (void)hipHostFree(c->it_log.host_pap);
     for (hipEvent_t ev : c->k1_events) (void)hipEventDestroy(ev);
     for (hipEvent_t ev : c->eval_events) (void)hipEventDestroy(ev);
     if (c->host_scal) (void)hipHostFree(c->host_scal);
@@ -1172,6 +1284,7 @@ int cglb_set_data(cglb_ctx* c, const void* X, const void* y) {
     }
     c->have_data = true;
     c->gpr_factored = false;
+    c->it_valid = false;
     c->p = 1;  // one target column again (cglb_set_targets)
     c->have_local = c->have_terms = false;
     return CGLB_OK;
@@ -1189,6 +1302,7 @@ int cglb_set_hypers(cglb_ctx* c, const double* lengthscales, double variance, do
     c->var = variance; c->noise = noise; c->mean = mean; c->jitter = jitter;
     HIP_CHECK(c, hipMemcpyAsync(c->Z, Z, (size_t)c->M * c->D * c->esz, hipMemcpyDefault, c->stream));
     c->have_hypers = true;
+    c->it_valid = false;
     c->pwh_src = nullptr;  // the column weights change with the hypers
     {   // |a_i + a_j + xs_i.xs_j| <= 2 max|xs|^2 (scaled units: octaves for RBF, octaves^2 for Matern).  The unclamped 2^x of
         // the hot loops needs the exponent inside [-1000, 0] octaves (exp2_tab_scale) and its hot-unit integer below 2^30.
@@ -1819,6 +1933,10 @@ int cglb_get_stat(cglb_ctx* c, const char* name, double* value) {
         const int rc = gpr_stat(c, name, value);  // "gpr_bytes", "gpr_fill_ms" | "gpr_factor_ms" | "gpr_solve_ms" | "gpr_inverse_ms" | "gpr_grad_ms"
         if (rc != -1) return rc;
     }
+    {
+        const int rc = itergp_stat(c, name, value);  // "itergp_select_ms" | "itergp_solve_ms" | "itergp_grad_ms"
+        if (rc != -1) return rc;
+    }
     if (!strcmp(name, "k1_pairs_per_launch")) { *value = c->sym_pairs; return CGLB_OK; }  // of the most recent symmetric launch geometry
     if (!strcmp(name, "kpart_bytes")) { *value = (double)c->kpart_cap; return CGLB_OK; }     // partial-sum slabs of the mat-vec
     if (!strcmp(name, "comm_allreduce_calls")) { *value = c->comm ? (double)c->comm->n_allreduce : 0.0; return CGLB_OK; }
@@ -1878,6 +1996,7 @@ int cglb_set_targets(cglb_ctx* c, const void* Y, int p) {
     HIP_CHECK(c, hipStreamSynchronize(c->stream));                             // the caller owns Y again
     c->p = p;
     c->gpr_factored = false;  // alpha = K^-1 (y - c) of the exact GPR class belongs to the old targets
+    c->it_valid = false;      // ... and so does the one of the iterative class
     return CGLB_OK;
 }
 
@@ -1988,6 +2107,183 @@ int cglb_time_matmat(cglb_ctx* c, int s, int reps, double* ms_avg) {
     // operands: s copies of y (values do not change the instruction stream)
     for (int b = 0; b < s; ++b) HIP_CHECK(c, hipMemcpyAsync(w.p + (size_t)b * c->N * c->esz, c->y, (size_t)c->N * c->esz, hipMemcpyDeviceToDevice, c->stream));
     return time_repeated(c, reps, [&]() -> int { return s == 1 ? launch_kff_matvec(c, w.p, w.Ap, nullptr) : launch_kff_matmat(c, w.p, s, w.Ap); }, ms_avg);
+}
+
+// ---- iterative exact GP (include/cglb_hip.h) -----------------------------------------------------------------------------
+int cglb_itergp_objective_and_grad(cglb_ctx* c, const void* eps, int t, void* v_inout, double max_error, int max_cg_iter, int lanczos_iter, double* out4,
+                                   double* grad, int* steps, double* half_rz) {
+    if (c) c->obj_valid = false;
+    if (!c || !eps || !v_inout || !out4 || t < 1 || max_cg_iter < 0 || lanczos_iter < 0) return c ? cglb_fail(c, CGLB_ERR_BAD_ARG, "bad argument") : CGLB_ERR_BAD_ARG;
+    CGLB_TRY(require_itergp_ok(c));
+    HIP_CHECK(c, hipSetDevice(c->device));
+    c->it_valid = false;
+    c->it_ev_last = 0;
+    const int64_t N = c->N;
+    const int k = c->M, s = 1 + t, D = c->D;
+    const size_t col = (size_t)N * sizeof(double);
+    CGLB_TRY(itergp_mark(c, 0));
+    CGLB_TRY(itergp_common_terms(c));
+    CGLB_TRY(itergp_mark(c, 1));
+    multi_work w;
+    CGLB_TRY(multi_reserve(c, s, &w));
+    CGLB_TRY(itergp_reserve(c, s, (size_t)t * (k + N)));
+    HIP_CHECK(c, hipMemcpyAsync(c->it_eps, eps, (size_t)t * (k + N) * sizeof(double), hipMemcpyDefault, c->stream));
+    // right-hand sides: e = y - mean, then the probes z_i = sqrt(s) (A^T eps_i[:k] + eps_i[k:]) through the A^T product of the preconditioner,
+    // (r - A^T t) / s at r = eps_i[k:], t = -eps_i[:k], times s sqrt(s)
+    CGLB_TRY(launch_sub_scalar(c, w.b, c->y, c->mean, N));
+    for (int i = 0; i < t; ++i) {
+        const double* ei = c->it_eps + (size_t)i * (k + N);
+        hipLaunchKernelGGL(negate_kernel, dim3((k + 255) / 256), dim3(256), 0, c->stream, ei, k, (double*)c->w_t);
+        CGLB_LAUNCH_CHECK(c);
+        CGLB_TRY(launch_precond_z(c, ei + k, c->w_t, w.b + (size_t)(i + 1) * col, nullptr));
+    }
+    CGLB_TRY(launch_scale(c, w.b + col, c->noise * std::sqrt(c->noise), (int64_t)t * N));
+    // one batched solve: column 0 warm-started, the probe columns from zero, no restart steps (a restart breaks the three-term recurrence)
+    HIP_CHECK(c, hipMemcpyAsync(c->it_V, v_inout, col, hipMemcpyDeviceToDevice, c->stream));
+    HIP_CHECK(c, hipMemsetAsync(c->it_V + N, 0, (size_t)t * col, c->stream));
+    pcg_ops o = multi_ops(c, w, s);
+    o.log = &c->it_log;
+    int st = 0;
+    double half = 0.0;
+    CGLB_TRY(pcg_solve(c, o, w.b, c->it_V, max_error, max_cg_iter, 0, &st, &half));
+    HIP_CHECK(c, hipMemcpyAsync(v_inout, c->it_V, col, hipMemcpyDeviceToDevice, c->stream));
+    HIP_CHECK(c, hipMemcpyAsync(c->it_alpha, c->it_V, col, hipMemcpyDeviceToDevice, c->stream));
+    CGLB_TRY(itergp_mark(c, 2));
+    // device scalars: [0, D] the kernel part of the gradient | [D + 1, D + 1 + s) u_b . v_b | e . alpha | sum alpha
+    double* sc = c->it_scal;
+    const int nsc = D + 3 + s;
+    HIP_CHECK(c, hipMemsetAsync(sc, 0, (size_t)nsc * sizeof(double), c->stream));
+    CGLB_TRY(launch_dot(c, w.b, c->it_V, N, sc + D + 1 + s));
+    if (grad) {
+        // right vectors in w.z: alpha and b_i = P^-1 z_i; left vectors in w.p: alpha / 2 and -a_i / (2 t)
+        HIP_CHECK(c, hipMemcpyAsync(w.z, c->it_V, col, hipMemcpyDeviceToDevice, c->stream));
+        for (int i = 1; i < s; ++i) CGLB_TRY(precond_single(c, w.b + (size_t)i * col, w.z + (size_t)i * col, c->scal + S_TMP));
+        hipLaunchKernelGGL(itergp_left_kernel, dim3(grid1d_full((int64_t)s * N)), dim3(256), 0, c->stream, (const double*)c->it_V, N, s, 0.5, -0.5 / t,
+                           (double*)w.p);
+        CGLB_LAUNCH_CHECK(c);
+        CGLB_TRY(launch_grad_kff_multi(c, w.p, w.z, s, sc));
+        CGLB_TRY(launch_dot(c, w.p, w.z, N, sc + D + 1, s));
+        hipLaunchKernelGGL(vec_sum_kernel, dim3(1), dim3(256), 0, c->stream, (const double*)c->it_V, N, sc + D + 2 + s);
+        CGLB_LAUNCH_CHECK(c);
+        CGLB_TRY(itergp_mark(c, 3));
+    }
+    std::vector<double> host((size_t)nsc);
+    CGLB_TRY(read_scalars(c, sc, host.data(), nsc));
+    // stochastic Lanczos quadrature on the host (csrc/slq_host.h)
+    int status = 0;
+    const double corr = slq_logdet_correction(c->it_log.rz.data(), c->it_log.pap.data(), st, t, lanczos_iter, &status);
+    if (status != 0)
+        return cglb_fail(c, CGLB_ERR_NOT_PD, status == 1 ? "Lanczos quadrature: the eigenvalue iteration did not converge"
+                                                         : "Lanczos quadrature: a tridiagonal of the CG coefficients is not positive definite");
+    const double logP = (double)N * std::log(c->noise) + 2.0 * c->sum_log_diag_LB;
+    out4[1] = -0.5 * host[D + 1 + s];
+    out4[2] = -0.5 * (logP + corr);
+    out4[3] = logP;
+    out4[0] = out4[1] + out4[2] - 0.5 * (double)N * std::log(2.0 * 3.14159265358979323846);
+    if (grad) {
+        for (int d = 0; d <= D; ++d) grad[d] = host[d];
+        double gs = 0.0;
+        for (int b = 0; b < s; ++b) gs += host[D + 1 + b];  // in column order
+        grad[D + 1] = gs;
+        grad[D + 2] = host[D + 2 + s];
+    }
+    if (steps) *steps = st;
+    if (half_rz) *half_rz = half;
+    c->it_steps = st;
+    c->it_t = t;
+    c->it_valid = true;
+    return CGLB_OK;
+}
+
+int cglb_itergp_get_coefficients(cglb_ctx* c, double* rz_log, double* pap_log) {
+    if (!c || !rz_log || !pap_log) return c ? cglb_fail(c, CGLB_ERR_BAD_ARG, "NULL argument") : CGLB_ERR_BAD_ARG;
+    const size_t s = (size_t)1 + c->it_t;
+    if (c->it_t < 1 || c->it_log.rz.size() != ((size_t)c->it_steps + 1) * s || c->it_log.pap.size() != (size_t)c->it_steps * s)
+        return cglb_fail(c, CGLB_ERR_STATE, "cglb_itergp_get_coefficients must follow cglb_itergp_objective_and_grad");
+    std::copy(c->it_log.rz.begin(), c->it_log.rz.end(), rz_log);
+    std::copy(c->it_log.pap.begin(), c->it_log.pap.end(), pap_log);
+    return CGLB_OK;
+}
+
+int cglb_itergp_predict(cglb_ctx* c, const void* xnew, int64_t n_new, double max_error, int max_cg_iter, void* f_mean, void* f_var) {
+    if (c) c->obj_valid = false;
+    if (!c || !xnew || !f_mean || !f_var || n_new < 0 || max_cg_iter < 0) return c ? cglb_fail(c, CGLB_ERR_BAD_ARG, "bad argument") : CGLB_ERR_BAD_ARG;
+    CGLB_TRY(require_itergp_ok(c));
+    if (is_wide(c)) return cglb_fail(c, CGLB_ERR_BAD_ARG, "the predictive of the iterative exact GP class is available up to 32 input dimensions");
+    if (n_new == 0) return CGLB_OK;
+    HIP_CHECK(c, hipSetDevice(c->device));
+    const int64_t N = c->N;
+    const size_t col = (size_t)N * sizeof(double);
+    multi_work w;
+    CGLB_TRY(multi_reserve(c, 8, &w));
+    CGLB_TRY(itergp_reserve(c, 8, 0));
+    if (!(c->it_valid && c->have_terms)) {  // no evaluation at the current data and hyper-parameters: the preconditioner first, alpha from zero
+        CGLB_TRY(itergp_common_terms(c));
+        HIP_CHECK(c, hipMemsetAsync(c->it_alpha, 0, col, c->stream));
+    }
+    // alpha = K^-1 e at the tolerance of this call, warm-started at the alpha of the last evaluation
+    CGLB_TRY(launch_sub_scalar(c, c->w_e, c->y, c->mean, N));
+    CGLB_TRY(pcg_solve(c, fused_ops(c), c->w_e, c->it_alpha, max_error, max_cg_iter, 40, nullptr, nullptr));
+    c->it_valid = true;
+    void *xr = nullptr, *xs = nullptr, *xa = nullptr;
+    DevTemps tmp;  // freed on every path below
+    CGLB_TRY(tmp.alloc(c, &xr, (size_t)n_new * c->D * sizeof(double)));
+    CGLB_TRY(tmp.alloc(c, &xs, (size_t)n_new * c->Dp * sizeof(double)));
+    CGLB_TRY(tmp.alloc(c, &xa, (size_t)n_new * sizeof(double)));
+    auto body = [&]() -> int {
+        HIP_CHECK(c, hipMemcpyAsync(xr, xnew, (size_t)n_new * c->D * sizeof(double), hipMemcpyDefault, c->stream));
+        CGLB_TRY(launch_prep_scaled(c, xr, n_new, xs, xa, true));                  // hot units for the pair kernel
+        CGLB_TRY(launch_cross_matvec(c, xs, xa, n_new, c->it_alpha, f_mean));      // K_*f alpha
+        hipLaunchKernelGGL(add_scalar_kernel, dim3(grid1d_full(n_new)), dim3(256), 0, c->stream, (double*)f_mean, n_new, c->mean);
+        CGLB_LAUNCH_CHECK(c);
+        CGLB_TRY(launch_prep_scaled(c, xr, n_new, xs, xa, false));                 // plain scaled units for the panel fill
+        // f_var = f - k_*^T K^-1 k_*: batched solves on the columns of K_f*, 8 new points at a time (n_new / 8 solves)
+        for (int64_t g0 = 0; g0 < n_new; g0 += 8) {
+            const int sg = (int)std::min<int64_t>(8, n_new - g0);
+            using T = double;
+            dim3 grid((unsigned)((N + 255) / 256), 1);
+            CGLB_DISPATCH_KIND(c->kind, CGLB_DISPATCH_DP(c->Dp, hipLaunchKernelGGL((kus_kernel<T, KIND, DP>), grid, dim3(256), 0, c->stream,
+                                                                                    (const T*)xs + g0 * DP, (const T*)c->Xs, N, N, sg, (T)c->var, (T*)w.b)));
+            CGLB_LAUNCH_CHECK(c);
+            HIP_CHECK(c, hipMemsetAsync(c->it_V, 0, (size_t)sg * col, c->stream));
+            if (sg == 1) CGLB_TRY(pcg_solve(c, fused_ops(c), w.b, c->it_V, max_error, max_cg_iter, 40, nullptr, nullptr));
+            else CGLB_TRY(pcg_solve(c, multi_ops(c, w, sg), w.b, c->it_V, max_error, max_cg_iter, 40, nullptr, nullptr));
+            CGLB_TRY(launch_dot(c, w.b, c->it_V, N, c->it_scal, sg));
+            hipLaunchKernelGGL(itergp_var_kernel, dim3(1), dim3(64), 0, c->stream, (const double*)c->it_scal, sg, c->var, (double*)f_var + g0);
+            CGLB_LAUNCH_CHECK(c);
+        }
+        return CGLB_OK;
+    };
+    const int rc = body();
+    (void)hipStreamSynchronize(c->stream);  // before `tmp` releases the buffers the kernels use
+    return rc;
+}
+
+int cglb_grad_kff_multi(cglb_ctx* c, const void* U, const void* V, int S, double* out) {
+    if (c) c->obj_valid = false;
+    if (!c || !U || !V || !out || S < 1) return c ? cglb_fail(c, CGLB_ERR_BAD_ARG, "bad argument") : CGLB_ERR_BAD_ARG;
+    CGLB_TRY(require_multi_ok(c));
+    if (c->dtype != CGLB_F64) return cglb_fail(c, CGLB_ERR_BAD_ARG, "the multi-pair gradient pass needs an fp64 context (-t fp64)");
+    if (!c->have_hypers) return cglb_fail(c, CGLB_ERR_STATE, "set_hypers must precede cglb_grad_kff_multi");
+    HIP_CHECK(c, hipSetDevice(c->device));
+    CGLB_TRY(c->mem.reserve(c, &c->it_scal, &c->it_scal_cap, (size_t)(c->D + 1) * sizeof(double)));
+    CGLB_TRY(launch_grad_kff_multi(c, U, V, S, c->it_scal));
+    return read_scalars(c, c->it_scal, out, c->D + 1);
+}
+
+int cglb_time_grad_kff_multi(cglb_ctx* c, int S, int reps, double* ms_avg) {
+    if (c) c->obj_valid = false;
+    if (!c || !ms_avg || reps <= 0 || S < 1) return c ? cglb_fail(c, CGLB_ERR_BAD_ARG, "bad argument") : CGLB_ERR_BAD_ARG;
+    CGLB_TRY(require_multi_ok(c));
+    if (c->dtype != CGLB_F64) return cglb_fail(c, CGLB_ERR_BAD_ARG, "the multi-pair gradient pass needs an fp64 context (-t fp64)");
+    if (!c->have_hypers) return cglb_fail(c, CGLB_ERR_STATE, "set_hypers must precede timing");
+    HIP_CHECK(c, hipSetDevice(c->device));
+    multi_work w;
+    CGLB_TRY(multi_reserve(c, S, &w));
+    CGLB_TRY(c->mem.reserve(c, &c->it_scal, &c->it_scal_cap, (size_t)(c->D + 1) * sizeof(double)));
+    // operands: S copies of y on both sides (values do not change the instruction stream)
+    for (int b = 0; b < S; ++b) HIP_CHECK(c, hipMemcpyAsync(w.p + (size_t)b * c->N * c->esz, c->y, (size_t)c->N * c->esz, hipMemcpyDeviceToDevice, c->stream));
+    return time_repeated(c, reps, [&]() -> int { return launch_grad_kff_multi(c, w.p, w.p, S, c->it_scal); }, ms_avg);
 }
 
 }  // extern "C"

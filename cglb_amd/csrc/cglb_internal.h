@@ -55,6 +55,14 @@ struct cglb_comm_state {
     cglb_devpool mem;      // owns every device buffer above; released by comm_free
 };
 
+// Per-iteration scalars of a solve, kept for the Lanczos quadrature of the iterative exact-GP class (cglb_api.hip: pcg_solve fills the log its
+// pcg_ops names; csrc/slq_host.h reads it): rz [steps + 1][s], pap [steps][s], column b of iteration j at [j * s + b].
+struct pcg_log {
+    std::vector<double> rz, pap;
+    double* host_pap = nullptr;  // [s] pinned host mirror of the p.Ap scalars of one iteration
+    int host_cap = 0;
+};
+
 struct cglb_ctx {
     cglb_comm_state* comm = nullptr;
     cglb_devpool mem;      // owns every device buffer below but the n2m_* ones; released by cglb_ctx_destroy
@@ -214,6 +222,18 @@ struct cglb_ctx {
     size_t gpr_bytes = 0;                               // device bytes the pool holds (cglb_get_stat "gpr_bytes")
     hipEvent_t gpr_ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};  // start | fill | factor | solves | inverse | gradient of the last evaluation
     int gpr_ev_last = 0;                                // index of the last event that evaluation recorded (2: no solve reached, 3: value only, 5: with gradient)
+    // multi-pair gradient pass (kernels_grad_multi.hip) and the iterative exact-GP class (cglb_itergp_*): fp64, one shard, one rank, one target
+    // column; everything allocated on first use
+    void* gm_uv = nullptr;                              // [N][16] interleaved column-side operands of the multi-pair gradient pass
+    size_t gm_uv_cap = 0;
+    pcg_log it_log;                                     // coefficient logs of the last solve of cglb_itergp_objective_and_grad
+    int it_steps = 0, it_t = 0;                         // ... its step count and number of probes
+    double *it_V = nullptr, *it_eps = nullptr, *it_scal = nullptr;  // [1 + t][N] solutions; [t][k + N] probes; [D + 1 + (1 + t) + 2] device scalars
+    size_t it_V_cap = 0, it_eps_cap = 0, it_scal_cap = 0;
+    double* it_alpha = nullptr;                         // [N] alpha = K^-1 e of the last evaluation (warm start of the predictive solve)
+    bool it_valid = false;                              // it_alpha and the common terms belong to the current data, targets and hyper-parameters
+    hipEvent_t it_ev[4] = {nullptr, nullptr, nullptr, nullptr};  // start | pivots and common terms | solve | gradient of the last evaluation
+    int it_ev_last = 0;                                 // index of the last event that evaluation recorded (0: none, 2: value only, 3: with gradient)
     std::string err;
 };
 
@@ -337,6 +357,10 @@ int launch_tri_rowdot(cglb_ctx* c, const void* Wrows, const void* x, int lower, 
 int launch_scale(cglb_ctx* c, void* x, double a, int64_t n);
 int launch_precond_z_from(cglb_ctx* c, const void* r_local, const void* Ks_local, void* z_local, double* rz_slot);
 int launch_cross_matvec(cglb_ctx* c, const void* Xs_new, const void* xa_new, int64_t n_new, const void* v_full, void* out);
+// kernels_grad_multi.hip: out[d] = sum_b u_b^T (dK_ff/dl_d) v_b, d < D, out[D] = sum_b u_b^T kappa v_b; U, V [S][N]; out dev double[D + 1], overwritten.
+// One evaluation of every kernel value for up to 8 pairs where grad_multi_native(c), S single passes elsewhere.
+bool grad_multi_native(const cglb_ctx* c);
+int launch_grad_kff_multi(cglb_ctx* c, const void* U, const void* V, int S, double* out);
 // kernels_vec.hip
 // dot, update_v_r, update_p: s columns of length n ([s][n], one launch each; per-column device scalars [s]); s = 1 is the one-column form.
 // A zero denominator gives a zero factor.

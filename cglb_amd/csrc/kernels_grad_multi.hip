@@ -1,0 +1,237 @@
+// K5, multi-pair form: out[d] = sum_b u_b^T (dK_ff / dl_d) v_b for every d and out[D] = sum_b u_b^T kappa v_b (the variance entry), b < S
+// pairs of vectors, every kernel value and derivative factor evaluated ONCE per unordered pair (i, j) for a group of up to 8 vector pairs.
+// The gradient of the iterative exact-GP class (cglb_itergp_objective_and_grad) is 1 + t such bilinear forms per evaluation.
+//
+// The decomposition and the direct differences are those of grad_kff_kernel<..., SYM = true> (kernels_grad.hip): a lane owns R rows (x_i, the
+// row-side values u_bi, v_bi and the R x (DP + 1) accumulators live in VGPRs) and streams the columns at or right of its row block; x_j and
+// the column-side values are wave-uniform scalar loads.  The column side is interleaved to UVi[N][2 S_pad] = (u_0j .. u_{S_pad-1,j}, v_0j ..)
+// by a prep kernel (zero padded), so the operands of a column are ONE contiguous scalar load, as multi_operand_kernel does for the product.
+//   diagonal block, columns [rblock, rblock + 256 R): visited in full, w_ij = sum_b u_bi v_bj                      (S_pad fmas)
+//   to its right:                                   visited once,  w_ij = sum_b (u_bi v_bj + u_bj v_bi)            (2 S_pad fmas)
+// then hv = h_ij w_ij, acc_d += hv (x_id - x_jd)^2 and the kappa sum, as in the single pass: about 18 + 4 DP + 2 S_pad vector-fp64
+// instructions per pair against S (18 + 4 DP + 2) for S single passes.
+// Partial sums go to slabs, part[(blockIdx.y * gridDim.x + blockIdx.x) * (DP + 1) + d], written by exactly one workgroup each and summed in
+// fixed order by the finalize kernel: no atomics, bitwise reproducible.  S > 8 runs in groups of 8 whose sums are added in group order.
+// The exponent runs through the range-clamped 2^x like the single direct-difference pass, so the clamped exponent range is native too.
+// Native scope: fp64, Dp <= 32, one rank, one shard covering all rows.  Elsewhere: S single launch_grad_kff passes and the kappa sums from
+// one product (launch_grad_kff_multi below).
+#include "pair_common.h"
+
+// rows per lane: 2 up to padded width 8 and 1 beyond, as the single pass.  The row-resident doubles are R (2 DP + 2 S_pad): at most 64 (DP = 8,
+// S_pad = 8: 202 VGPRs, two waves per SIMD) with two rows and 80 (DP = 32, S_pad = 8: 256 VGPRs) with one; no instance spills.  Register use of
+// every instance: DESIGN.md section 4d.
+static constexpr int grad_multi_rows_per_lane(int dp) { return dp <= 8 ? 2 : 1; }
+
+// UVi[j][b] = U[b][j], UVi[j][sp + b] = V[b][j], zero for the padding pairs b >= s
+__global__ __launch_bounds__(256) void grad_multi_operand_kernel(const double* __restrict__ U, const double* __restrict__ V, int s, int sp, int64_t n,
+                                                                 double* __restrict__ UVi) {
+    const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= n * 2 * sp) return;
+    const int64_t j = idx / (2 * sp);
+    const int q = (int)(idx - j * 2 * sp);
+    const int b = q < sp ? q : q - sp;
+    UVi[idx] = b < s ? (q < sp ? U : V)[(int64_t)b * n + j] : 0.0;
+}
+
+// Columns [j0, j1) against the R rows of a lane.  FULL: both orientations of the pair weight (columns right of the diagonal block).
+template <int KIND, int DP, int R, int SP, int PREC, bool FULL>
+__device__ __forceinline__ void grad_multi_cols(const double* __restrict__ Xh, const double* __restrict__ UVi, const double (&xi)[R][DP],
+                                                const double (&ui)[R][SP], const double (&vi)[R][SP], double (&acc)[R][DP], double (&acck)[R],
+                                                int64_t j0, int64_t j1, const double* __restrict__ tab) {
+    for (int64_t j = j0; j < j1; ++j) {
+        const double* __restrict__ cj = UVi + j * (2 * SP);  // wave-uniform: scalar loads
+        double xj[DP], vj[SP], uj[SP];
+#pragma unroll
+        for (int d = 0; d < DP; ++d) xj[d] = Xh[j * DP + d];
+#pragma unroll
+        for (int b = 0; b < SP; ++b) {
+            vj[b] = cj[SP + b];
+            uj[b] = FULL ? cj[b] : 0.0;
+        }
+#pragma unroll
+        for (int k = 0; k < R; ++k) {
+            double sq[DP], d2 = 0.0;
+#pragma unroll
+            for (int d = 0; d < DP; ++d) {
+                const double df = xi[k][d] - xj[d];
+                sq[d] = df * df;
+                d2 += sq[d];
+            }
+            double w = ui[k][0] * vj[0];
+#pragma unroll
+            for (int b = 1; b < SP; ++b) w = __builtin_fma(ui[k][b], vj[b], w);
+            if (FULL) {
+#pragma unroll
+                for (int b = 0; b < SP; ++b) w = __builtin_fma(vi[k][b], uj[b], w);
+            }
+            double hv;
+            if (KIND == CGLB_RBF) {  // h = kappa
+                hv = exp2_tab<true, PREC>(-0.5 * d2, tab) * w;
+                acck[k] += hv;
+            } else {                 // h = 3 e, kappa = (1 + sqrt3 r) e, e = 2^(-rr / T), sqrt3 r = rr ln 2 / T
+                const double rr = 2.0 * sqrt_pos(d2);
+                const double ew = exp2_tab<true, PREC>(-rr, tab) * w;
+                hv = 3.0 * ew;
+                acck[k] = __builtin_fma(ew, __builtin_fma(rr, CGLB_LN2 / CGLB_HOT_UNITS, 1.0), acck[k]);
+            }
+#pragma unroll
+            for (int d = 0; d < DP; ++d) acc[k][d] = __builtin_fma(hv, sq[d], acc[k][d]);
+        }
+    }
+}
+
+// grid (row blocks of 256 R rows, column chunks of jchunk columns); U, V: [s][n] row side; UVi: interleaved column side
+template <int KIND, int DP, int R, int SP, int PREC>
+__global__ __launch_bounds__(256) void grad_kff_multi_kernel(const double* __restrict__ Xh, const double* __restrict__ U, const double* __restrict__ V,
+                                                             int s, const double* __restrict__ UVi, int64_t n, int64_t jchunk,
+                                                             double* __restrict__ part, const double* __restrict__ exp_tab) {
+    __shared__ double smem[16];
+    __shared__ double tab[CGLB_TAB_SIZE];
+    load_exp_table(tab, exp_tab);
+    const int64_t rblock = (int64_t)blockIdx.x * (256 * R);
+    double xi[R][DP], acc[R][DP], ui[R][SP], vi[R][SP], acck[R];
+#pragma unroll
+    for (int k = 0; k < R; ++k) {
+        const int64_t row = rblock + threadIdx.x + (int64_t)k * 256;
+        const bool live = row < n;
+        const int64_t rr = live ? row : n - 1;
+#pragma unroll
+        for (int d = 0; d < DP; ++d) {
+            xi[k][d] = Xh[rr * DP + d];
+            acc[k][d] = 0.0;
+        }
+#pragma unroll
+        for (int b = 0; b < SP; ++b) {  // padded rows and padded pairs carry zero weight
+            ui[k][b] = (live && b < s) ? U[(int64_t)b * n + rr] : 0.0;
+            vi[k][b] = (live && b < s) ? V[(int64_t)b * n + rr] : 0.0;
+        }
+        acck[k] = 0.0;
+    }
+    int64_t j0 = (int64_t)blockIdx.y * jchunk;
+    const int64_t j1 = (j0 + jchunk < n) ? j0 + jchunk : n;
+    const int64_t sym_from = rblock + 256 * R;
+    if (j0 < rblock) j0 = rblock;
+    const int64_t jd = j1 < sym_from ? j1 : sym_from;  // end of the diagonal block's share of this chunk
+    if (j0 < jd) grad_multi_cols<KIND, DP, R, SP, PREC, false>(Xh, UVi, xi, ui, vi, acc, acck, j0, jd, tab);
+    const int64_t jf = j0 > sym_from ? j0 : sym_from;
+    if (jf < j1) grad_multi_cols<KIND, DP, R, SP, PREC, true>(Xh, UVi, xi, ui, vi, acc, acck, jf, j1, tab);
+    double* __restrict__ out = part + ((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * (DP + 1);
+#pragma unroll
+    for (int d = 0; d <= DP; ++d) {
+        double sum = 0.0;
+#pragma unroll
+        for (int k = 0; k < R; ++k) sum += (d < DP) ? acc[k][d < DP ? d : 0] : acck[k];
+        sum = block_sum(sum, smem);
+        if (threadIdx.x == 0) out[d] = sum;
+    }
+}
+
+// out[d] (+)= scale_d * sum_blk part[blk][d], d < D the lengthscale entries, out[D] (+)= sum_blk part[blk][DP]; one block per entry
+__global__ __launch_bounds__(256) void grad_multi_finalize_kernel(const double* __restrict__ part, int64_t nblk, int DP, int D, ScaleParams sp, double var,
+                                                                  double* __restrict__ out, int accumulate) {
+    __shared__ double smem[16];
+    const int d = blockIdx.x;
+    if (d > D) return;
+    const int col = d < D ? d : DP;
+    double s = 0.0;
+    for (int64_t b = threadIdx.x; b < nblk; b += blockDim.x) s += part[b * (DP + 1) + col];
+    s = block_sum(s, smem);
+    if (threadIdx.x == 0) {
+        const double val = d < D ? s * var * sp.scale[d] : s;  // sp.scale holds 1 / (l_d kscale^2)
+        out[d] = accumulate ? out[d] + val : val;
+    }
+}
+
+template <int KIND, int DP, int SP>
+static int grad_multi_group(cglb_ctx* c, const double* U, const double* V, int s, double* out, int accumulate) {
+    constexpr int R = grad_multi_rows_per_lane(DP);
+    const int64_t n = c->N;
+    ScaleParams sp;
+    const double ks = ((c->kind == CGLB_RBF) ? sqrt(CGLB_LOG2E) : CGLB_SQRT3 * CGLB_LOG2E) * cglb_hot_scale(c);  // the pass runs on the hot operand set
+    for (int d = 0; d < CGLB_MAX_D_NARROW; ++d) {
+        sp.center[d] = 0;
+        sp.scale[d] = d < c->D ? 1.0 / (c->ls[d] * ks * ks) : 0.0;
+    }
+    // the grid rule of the single symmetric pass (launch_grad_kff)
+    const int64_t bx = (n + 256 * R - 1) / (256 * R);
+    int64_t js = 2 * ((8192 + bx - 1) / bx);
+    if (js > 1024) js = 1024;
+    if (js > (n + 63) / 64) js = (n + 63) / 64;
+    if (js < 1) js = 1;
+    const int64_t jchunk = (n + js - 1) / js;
+    const int64_t jsplit = (n + jchunk - 1) / jchunk;
+    const int64_t nblk = bx * jsplit;
+    CGLB_TRY(c->mem.reserve(c, &c->gpart, &c->gpart_cap, (size_t)nblk * (DP + 1) * sizeof(double)));
+    CGLB_TRY(c->mem.reserve(c, &c->gm_uv, &c->gm_uv_cap, (size_t)n * 16 * sizeof(double)));
+    hipLaunchKernelGGL(grad_multi_operand_kernel, dim3((unsigned)((n * 2 * SP + 255) / 256)), dim3(256), 0, c->stream, U, V, s, SP, n, (double*)c->gm_uv);
+    CGLB_LAUNCH_CHECK(c);
+    using T = double;
+    CGLB_DISPATCH_PREC(c, hipLaunchKernelGGL((grad_kff_multi_kernel<KIND, DP, R, SP, PREC>), dim3((unsigned)bx, (unsigned)jsplit), dim3(256), 0, c->stream,
+                                             (const double*)c->Xh, U, V, s, (const double*)c->gm_uv, n, jchunk, c->gpart, (const double*)c->exp_tab));
+    CGLB_LAUNCH_CHECK(c);
+    hipLaunchKernelGGL(grad_multi_finalize_kernel, dim3(c->D + 1), dim3(256), 0, c->stream, (const double*)c->gpart, nblk, DP, c->D, sp, c->var, out,
+                       accumulate);
+    CGLB_LAUNCH_CHECK(c);
+    return CGLB_OK;
+}
+
+bool grad_multi_native(const cglb_ctx* c) {
+    return c->dtype == CGLB_F64 && !is_wide(c) && c->par_world == 1 && !c->comm && c->r0 == 0 && c->r1 == c->N;
+}
+
+// fall-back pieces: out[d] += g[d], d < D;  out[D] += sum_i u_i (w_i - noise v_i) / var with w = (K_ff + noise I) v  (one block, fixed order)
+template <typename T>
+__global__ __launch_bounds__(256) void grad_multi_fallback_kernel(const double* __restrict__ g, int D, const T* __restrict__ u, const T* __restrict__ v,
+                                                                  const T* __restrict__ w, int64_t n, double noise, double var, double* __restrict__ out,
+                                                                  int accumulate) {
+    __shared__ double smem[16];
+    double s = 0.0;
+    for (int64_t i = threadIdx.x; i < n; i += blockDim.x) s += (double)u[i] * ((double)w[i] - noise * (double)v[i]);
+    s = block_sum(s, smem);
+    if (threadIdx.x == 0) {
+        for (int d = 0; d < D; ++d) out[d] = accumulate ? out[d] + g[d] : g[d];
+        out[D] = (accumulate ? out[D] : 0.0) + s / var;
+    }
+}
+
+// out (device double[D + 1], overwritten): sum_b u_b^T (dK_ff/dl_d) v_b, d < D, and sum_b u_b^T kappa v_b.  U, V: device [S][N], pair b contiguous.
+int launch_grad_kff_multi(cglb_ctx* c, const void* U, const void* V, int S, double* out) {
+    if (!grad_multi_native(c)) {
+        // S single passes, and the kappa sums from one product: u_b^T kappa v_b = u_b^T ((K_ff + noise I) v_b - noise v_b) / variance
+        if (c->r0 != 0 || c->r1 != c->N) return cglb_fail(c, CGLB_ERR_BAD_ARG, "the multi-pair gradient pass needs a single shard covering all rows");
+        const size_t stride = (size_t)c->N * c->esz;
+        void* W = nullptr;
+        double* g = nullptr;
+        DevTemps tmp;
+        CGLB_TRY(tmp.alloc(c, &W, (size_t)S * stride));
+        CGLB_TRY(tmp.alloc(c, (void**)&g, sizeof(double) * c->D));
+        auto body = [&]() -> int {
+            CGLB_TRY(launch_kff_matmat(c, V, S, W));
+            for (int b = 0; b < S; ++b) {
+                CGLB_TRY(launch_grad_kff(c, (const char*)V + b * stride, (const char*)U + b * stride, g));
+                CGLB_DISPATCH_T(c->dtype, hipLaunchKernelGGL((grad_multi_fallback_kernel<T>), dim3(1), dim3(256), 0, c->stream, (const double*)g, c->D,
+                                                             (const T*)((const char*)U + b * stride), (const T*)((const char*)V + b * stride),
+                                                             (const T*)((const char*)W + b * stride), c->N, c->noise, c->var, out, b > 0 ? 1 : 0));
+                CGLB_LAUNCH_CHECK(c);
+            }
+            return CGLB_OK;
+        };
+        const int rc = body();
+        (void)hipStreamSynchronize(c->stream);  // before `tmp` releases the buffers the kernels use
+        return rc;
+    }
+    for (int b0 = 0; b0 < S; b0 += 8) {
+        const int sg = std::min(8, S - b0);
+        const double* Ug = (const double*)U + (size_t)b0 * c->N;
+        const double* Vg = (const double*)V + (size_t)b0 * c->N;
+        const int sp = sg <= 1 ? 1 : (sg <= 2 ? 2 : (sg <= 4 ? 4 : 8));
+        const int accumulate = b0 > 0 ? 1 : 0;
+        CGLB_DISPATCH_KIND(c->kind, CGLB_DISPATCH_DP(c->Dp, {
+            if (sp == 1) CGLB_TRY((grad_multi_group<KIND, DP, 1>(c, Ug, Vg, sg, out, accumulate)));
+            else if (sp == 2) CGLB_TRY((grad_multi_group<KIND, DP, 2>(c, Ug, Vg, sg, out, accumulate)));
+            else if (sp == 4) CGLB_TRY((grad_multi_group<KIND, DP, 4>(c, Ug, Vg, sg, out, accumulate)));
+            else CGLB_TRY((grad_multi_group<KIND, DP, 8>(c, Ug, Vg, sg, out, accumulate)));
+        }));
+    }
+    return CGLB_OK;
+}

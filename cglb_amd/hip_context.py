@@ -41,6 +41,17 @@ class GPRResult:
     grad: Optional[dict]  # d lml / d {lengthscales, variance, noise, mean}
 
 
+@dataclass
+class IterGPResult:
+    lml: float        # quad + logdet - N/2 log 2 pi
+    quad: float       # -1/2 e^T alpha
+    logdet: float     # -1/2 log|K|, the stochastic Lanczos estimate
+    logdet_P: float   # log|P| of the preconditioner
+    steps: int
+    residual_error: float
+    grad: Optional[dict]  # the unbiased gradient estimate {lengthscales, variance, noise, mean}: not the derivative of `lml`
+
+
 def _ptr(t: Optional[torch.Tensor]):
     return None if t is None else c_void_p(t.data_ptr())
 
@@ -296,6 +307,56 @@ class HipContext:
         mean, var = self.empty(xn.shape[0]), self.empty(xn.shape[0])
         _lib.check(self.lib.cglb_gpr_predict(self._ctx, _ptr(xn), xn.shape[0], _ptr(mean), _ptr(var)), self._ctx)
         return mean, var
+
+    # -- iterative exact GP (cglb_itergp_*): batched CG with Lanczos log-det, fp64, one rank, one target column; num_inducing is the rank of
+    #    the pivoted-Cholesky preconditioner, re-selected at every evaluation ----
+    def itergp_objective_and_grad(self, eps, v_inout: torch.Tensor, max_error=1.0, max_cg_iter=1000, lanczos_iter=20, with_grad=True) -> IterGPResult:
+        """eps [t, M + N]: the probes' standard-normal draws (the library draws none).  v_inout (device, length N) is the persistent warm start of
+        the data column, updated in place."""
+        if v_inout.device != self.device or v_inout.dtype != self.dtype or v_inout.numel() != self.N or not v_inout.is_contiguous():
+            raise ValueError("v_inout must be a contiguous device vector of length N in the context dtype")
+        e = torch.as_tensor(eps, dtype=torch.float64).reshape(-1, self.M + self.N).contiguous().to(self.device)
+        out4 = (c_double * 4)()
+        g = np.empty(self.D + 3, dtype=np.float64) if with_grad else None
+        steps, half = c_int(), c_double()
+        rc = self.lib.cglb_itergp_objective_and_grad(self._ctx, _ptr(e), int(e.shape[0]), _ptr(v_inout), float(max_error), int(max_cg_iter),
+                                                     int(lanczos_iter), out4, g.ctypes.data_as(ctypes.POINTER(c_double)) if with_grad else None,
+                                                     byref(steps), byref(half))
+        _lib.check(rc, self._ctx)
+        self._itergp_shape = (steps.value, 1 + int(e.shape[0]))
+        D = self.D
+        grad = None if g is None else {"lengthscales": g[:D].copy(), "variance": float(g[D]), "noise": float(g[D + 1]), "mean": float(g[D + 2])}
+        return IterGPResult(out4[0], out4[1], out4[2], out4[3], steps.value, half.value, grad)
+
+    def itergp_coefficients(self) -> Tuple[np.ndarray, np.ndarray]:
+        """(rz [steps + 1, 1 + t], pAp [steps, 1 + t]) of the last itergp_objective_and_grad."""
+        steps, s = self._itergp_shape
+        rz, pap = np.empty((steps + 1, s)), np.empty((steps, s))
+        rc = self.lib.cglb_itergp_get_coefficients(self._ctx, rz.ctypes.data_as(ctypes.POINTER(c_double)), pap.ctypes.data_as(ctypes.POINTER(c_double)))
+        _lib.check(rc, self._ctx)
+        return rz, pap
+
+    def itergp_predict(self, xnew, max_error=1e-3, max_cg_iter=1000) -> Tuple[torch.Tensor, torch.Tensor]:
+        """predict_f mean and variance at xnew [n_new, D]: one solve for alpha and n_new / 8 batched solves for the variances."""
+        xn = torch.as_tensor(xnew, dtype=self.dtype).reshape(-1, self.D).contiguous().to(self.device)
+        mean, var = self.empty(xn.shape[0]), self.empty(xn.shape[0])
+        rc = self.lib.cglb_itergp_predict(self._ctx, _ptr(xn), xn.shape[0], float(max_error), int(max_cg_iter), _ptr(mean), _ptr(var))
+        _lib.check(rc, self._ctx)
+        return mean, var
+
+    def grad_kff_multi(self, U, V) -> np.ndarray:
+        """[sum_b u_b^T (dK_ff / dl_d) v_b for d < D, sum_b u_b^T kappa v_b] for U, V [N, S]: one evaluation of every kernel value for up to 8 pairs."""
+        Ut = self._cols(U)
+        Vt = self._cols(V, Ut.shape[0])
+        out = np.empty(self.D + 1, dtype=np.float64)
+        rc = self.lib.cglb_grad_kff_multi(self._ctx, _ptr(Ut), _ptr(Vt), int(Ut.shape[0]), out.ctypes.data_as(ctypes.POINTER(c_double)))
+        _lib.check(rc, self._ctx)
+        return out
+
+    def time_grad_kff_multi(self, s: int, reps: int) -> float:
+        ms = c_double()
+        _lib.check(self.lib.cglb_time_grad_kff_multi(self._ctx, int(s), int(reps), byref(ms)), self._ctx)
+        return ms.value
 
     def get_stat(self, name: str) -> float:
         out = c_double()

@@ -265,6 +265,46 @@ int cglb_gpr_objective_and_grad(cglb_ctx* ctx, double* out3, double* grad);
  * factors first if there is none. */
 int cglb_gpr_predict(cglb_ctx* ctx, const void* xnew, int64_t n_new, void* f_mean, void* f_var);
 
+/* ---- iterative exact GP regression: model class "itergp" - the "Iterative GP" baseline of the paper (cglb_experiments/cli.py:293-311 and
+ *      pytorch/interface.py:233-260, :561-604 build it on gpytorch: modified batched CG, a pivoted-Cholesky preconditioner of rank _prec_size() = 100,
+ *      stochastic Lanczos quadrature for the log-determinant).  gpytorch's random numbers and stop rule are not reproduced; the estimator is
+ *      defined here and pinned to tests/itergp_ref.py.  O(N) memory.  fp64 contexts with one shard covering all rows, one rank, one target
+ *      column, logdet_bound 0, quad_term 0 and the stored panel; anything else returns CGLB_ERR_BAD_ARG.
+ * K = variance kappa(X, X) + noise I, e = y - mean, s = noise.  The context is created with m = k, the rank of the preconditioner (k <= n_total),
+ * and cglb_set_hypers is called with any Z: every evaluation replaces Z by the k training points the greedy selection of cglb_select_inducing
+ * picks under the CURRENT hyper-parameters (the pivoted Cholesky of K_ff, jitter included) and runs cglb_setup, so that P = Q_ff + s I with
+ * A = L^-1 K_uf / sqrt(s) the stored panel and log|P| = N log s + 2 sum log diag LB.
+ *   probes   z_i = sqrt(s) (A^T eps_i[:k] + eps_i[k:]), i < t, from the caller's eps [t, k + n_total] (any; standard normal entries give z_i ~ N(0, P);
+ *            the library draws no random numbers)
+ *   solve    one batched PCG (cglb_pcg_solve_multi's loop) on [e, z_1 .. z_t]: column 0 warm-started at v_inout (dev [n], overwritten with alpha),
+ *            the probe columns from zero, no restart steps, stop on 1/2 sum_b r_b^T P^-1 r_b <= max_error or max_cg_iter steps; rz_j,b and
+ *            pAp_j,b of every iteration are kept
+ *   log|K|   ~ log|P| + (1/t) sum_i rz_0,i e_1^T log(T_i) e_1, T_i the Lanczos tridiagonal of probe i from gamma_j = rz_j / pAp_j and
+ *            beta_j = rz_{j+1} / rz_j: T[j][j] = 1/gamma_j + beta_{j-1}/gamma_{j-1}, T[j][j+1] = sqrt(beta_j)/gamma_j, of min(steps, lanczos_iter)
+ *            rows, cut at the first zero or non-finite gamma_j or rz_j (csrc/slq_host.h, host)
+ *   out4     {lml, -1/2 e^T alpha, -1/2 log|K| (the estimate), log|P|},  lml = out4[1] + out4[2] - n/2 log 2 pi
+ *   grad     host double[d + 3] = {lengthscales, variance, noise, mean} or NULL: sum_b u_b^T (dK/d theta) v_b with (u_0, v_0) = (alpha / 2, alpha)
+ *            and (u_i, v_i) = (-a_i / (2 t), P^-1 z_i), a_i = K^-1 z_i - the usual unbiased estimate, NOT the derivative of the returned value
+ *            (P is treated as constant); the mean entry is sum alpha.  The 1 + t bilinear forms run through cglb_grad_kff_multi's pass.
+ * Two evaluations with the same inputs return bitwise equal numbers.  CGLB_ERR_NOT_PD if a tridiagonal has an eigenvalue that is not positive. */
+int cglb_itergp_objective_and_grad(cglb_ctx* ctx, const void* eps, int t, void* v_inout, double max_error, int max_cg_iter, int lanczos_iter,
+                                   double* out4, double* grad, int* steps, double* half_rz);
+/* the coefficient logs of the last cglb_itergp_objective_and_grad: rz_log host [steps + 1][1 + t], pap_log host [steps][1 + t] (column 0: the data) */
+int cglb_itergp_get_coefficients(cglb_ctx* ctx, double* rz_log, double* pap_log);
+/* predict_f: f_mean = mean + K_*f alpha with alpha = K^-1 e solved to max_error (warm-started at the alpha of the last evaluation at the current
+ * data and hyper-parameters; without one the preconditioner is built first), f_var = variance - k_*^T K^-1 k_* by batched solves on the columns
+ * of K_f*, 8 new points at a time (each to 1/2 sum_b r_b^T P^-1 r_b <= max_error): n_new / 8 solves - a Lanczos variance cache is not part
+ * of this.  xnew: any [n_new, d], d <= 32; f_mean, f_var: dev [n_new]. */
+int cglb_itergp_predict(cglb_ctx* ctx, const void* xnew, int64_t n_new, double max_error, int max_cg_iter, void* f_mean, void* f_var);
+/* The gradient pass of the class on its own (tests, timing): out host double[d + 1], out[k] = sum_b u_b^T (dK_ff / dl_k) v_b for k < d and
+ * out[d] = sum_b u_b^T kappa v_b (kappa = K_ff / variance), b < S.  U, V: dev [S, n_total], pair b contiguous.  Every kernel value is evaluated
+ * once per unordered pair for up to 8 pairs of vectors (fp64, d <= 32: csrc/kernels_grad_multi.hip; wider inputs run S single passes); S > 8
+ * runs in groups of 8 added in group order.  Bitwise reproducible.  The scope of cglb_matmat, fp64 only. */
+int cglb_grad_kff_multi(cglb_ctx* ctx, const void* U, const void* V, int S, double* out);
+/* average duration (ms) of `reps` back-to-back passes with S pairs (operand prep, pair kernel and fixed-order sum of every group, on the context
+ * stream, no read-back), in the style of cglb_time_kernel(which = 2), which times one single pass */
+int cglb_time_grad_kff_multi(cglb_ctx* ctx, int S, int reps, double* ms_avg);
+
 /* ---- inducing-point initialisation: InducingVariableConfig.init, config.py:55-65 ------------------------
  * The reference calls robustgp.ConditionalVariance(sample=False) (third-party): greedy maximisation of the conditional
  * variance under the INITIAL kernel (pivoted Cholesky of K_ff, lowest index on ties).  Needs set_data only; works on all n rows
@@ -297,7 +337,9 @@ int cglb_time_kernel(cglb_ctx* ctx, int which, int reps, double* ms_avg);
  * "L_diag_ratio": max/min of diag(chol(K_uu + jitter I)) of the last cglb_setup (a cheap proxy of cond(L));
  * "gpr_bytes": device bytes the exact GPR class holds; "gpr_fill_ms" | "gpr_factor_ms" | "gpr_solve_ms" | "gpr_inverse_ms" | "gpr_grad_ms": device
  * time (HIP events on the context stream) of the phases of the last cglb_gpr_objective_and_grad - tiles of K | factorisation | alpha and the
- * scalars | K^-1 | gradient pass; 0 for a phase that evaluation did not run. */
+ * scalars | K^-1 | gradient pass; 0 for a phase that evaluation did not run;
+ * "itergp_select_ms" | "itergp_solve_ms" | "itergp_grad_ms": device time of the phases of the last cglb_itergp_objective_and_grad - pivots and
+ * common terms | right-hand sides and the batched solve | gradient; 0 for a phase that evaluation did not run. */
 int cglb_get_stat(cglb_ctx* ctx, const char* name, double* value);
 /* Tunables: name = "kff_variant" | "kff_jsplit" | "kff_rows" | "sym_chunk" | "precond_mode" | "chol_mode" | "pcg_lookahead" | "sym_order" | "aat_block" | "grad_gram" | "k1_profile" |
  * "grad_trsm" (gradient algebra against L = chol(K_uu): 0 products with the explicit inverse, 1 backward-stable triangular solves, 2 = default:
