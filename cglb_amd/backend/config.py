@@ -105,9 +105,9 @@ CGLBConfig = _record("CGLBConfig", (SGPRConfig,),
                      [("max_error", float, dataclasses.field(default=1.0)), ("joint_optimization", bool, dataclasses.field(default=False)),
                       ("vzero", bool, dataclasses.field(default=False))],
                      namespace={"params": _cglb_params}, doc="Conjugate-gradient lower bound model (reference config.py:110-121).")
-CGLBN2MConfig = _record("CGLBN2MConfig", (CGLBConfig,), doc="Log-det ablation (out of scope).")
-CGLBNM2Config = _record("CGLBNM2Config", (CGLBConfig,), doc="Log-det ablation (out of scope).")
-SGPRN2MConfig = _record("SGPRN2MConfig", (SGPRConfig,), doc="Log-det ablation (out of scope).")
+CGLBN2MConfig = _record("CGLBN2MConfig", (CGLBConfig,), doc="CGLB with the N^2M log-det bound (one rank, fp64).")
+CGLBNM2Config = _record("CGLBNM2Config", (CGLBConfig,), doc="CGLB with the NM^2 log-det bound (one rank).")
+SGPRN2MConfig = _record("SGPRN2MConfig", (SGPRConfig,), doc="SGPR with the N^2M log-det bound (one rank, fp64).")
 
 # registries: the keys are the reference's CLI choices (config.py:139-166)
 GPR_CONFIGS = dict(gpr=GPRConfig, exactgp=ExactGPConfig, itergp=IterGPRConfig)

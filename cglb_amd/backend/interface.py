@@ -173,67 +173,42 @@ class _InitKernel:
         return X[indices].copy()
 
 
+def _likelihood_and_kernel(model_cfg: ModelConfig, data: Data, noise_lower_bound: float = 1e-6):
+    likelihood = GaussianLikelihood(lower_bound=noise_lower_bound)
+    likelihood.noise = model_cfg.params(data)["noise_variance"]
+    return likelihood, create_kernel(model_cfg.kernel, data)
+
+
 def _likelihood_and_kernel_for_sgpr(model_cfg: SGPRConfig, data: Data):
     """interface.py:263-301"""
-    params = model_cfg.params(data)
-    likelihood = GaussianLikelihood(lower_bound=1e-6)
-    likelihood.noise = params["noise_variance"]
-    base_kernel = create_kernel(model_cfg.kernel, data)
-
-    inducing_variable = params["inducing_variable"](_InitKernel(base_kernel))
+    likelihood, base_kernel = _likelihood_and_kernel(model_cfg, data)
+    inducing_variable = model_cfg.params(data)["inducing_variable"](_InitKernel(base_kernel))
     return likelihood, InducingPointKernel(base_kernel, inducing_variable)
 
 
-@create_model.register
-def _create_model_cglb(model_cfg: CGLBConfig, data: Data):
-    """interface.py:315-323.  Like the reference's torch path, max_error / joint_optimization / vzero of the config
-    are not consumed here (the objective uses ConjugateGradient() defaults) unless the backend was configured with
-    config_semantics="tf"."""
-    likelihood, kernel = _likelihood_and_kernel_for_sgpr(model_cfg, data)
-    extra = {}
-    if _STATE["config_semantics"] == "tf":  # the TF twin's create_model hands these to the model (tensorflow/interface.py:244-258)
-        extra = dict(max_error=model_cfg.max_error, joint_optimization=model_cfg.joint_optimization, vzero=model_cfg.vzero)
-    model = CGLB((np.asarray(data[0]), _targets(data[1])), likelihood, kernel, dtype=_STATE["dtype"], **extra)
-    _broadcast_parameters(model)
-    return model
-
-
-def _create_cglb_variant(cls, model_cfg: CGLBConfig, data: Data):
-    likelihood, kernel = _likelihood_and_kernel_for_sgpr(model_cfg, data)
-    extra = {}
-    if _STATE["config_semantics"] == "tf":
-        extra = dict(max_error=model_cfg.max_error, joint_optimization=model_cfg.joint_optimization, vzero=model_cfg.vzero)
-    return cls((np.asarray(data[0]), _targets(data[1])), likelihood, kernel, dtype=_STATE["dtype"], **extra)
-
-
-@create_model.register
-def _create_model_cglbn2m(model_cfg: CGLBN2MConfig, data: Data):
-    """CGLB with the N^2M log-det bound (tensorflow/interface.py:216-292 builds it from the same config fields).  One rank, fp64."""
-    _require_one_rank("cglbn2m")
-    return _create_cglb_variant(CGLBN2M, model_cfg, data)
-
-
-@create_model.register
-def _create_model_cglbnm2(model_cfg: CGLBNM2Config, data: Data):
-    """CGLB with the NM^2 log-det bound.  One rank."""
-    _require_one_rank("cglbnm2")
-    return _create_cglb_variant(CGLBNM2, model_cfg, data)
+# config class -> (model class, one rank only, takes max_error / joint_optimization / vzero under config_semantics="tf")
+_INDUCING_POINT_CLASSES = {CGLBConfig: (CGLB, False, True), CGLBN2MConfig: (CGLBN2M, True, True), CGLBNM2Config: (CGLBNM2, True, True),
+                           SGPRConfig: (SGPR, True, False), SGPRN2MConfig: (SGPRN2M, True, False)}
 
 
 @create_model.register
 def _create_model_sgpr(model_cfg: SGPRConfig, data: Data):
-    """SGPR (Titsias) on the same inducing-point initialisation as CGLB.  One rank."""
-    _require_one_rank("sgpr")
+    """interface.py:315-323 for cglb; tensorflow/interface.py:216-292 builds the other four from the same config fields, on the same
+    inducing-point initialisation.  Like the reference's torch path, max_error / joint_optimization / vzero of a CGLB config are not
+    consumed here (the objective uses ConjugateGradient() defaults) unless the backend was configured with
+    config_semantics="tf": the TF twin's create_model hands these to the model (tensorflow/interface.py:244-258).  Only cglb runs on more
+    than one rank."""
+    cls, one_rank, tf_extras = next(_INDUCING_POINT_CLASSES[c] for c in type(model_cfg).__mro__ if c in _INDUCING_POINT_CLASSES)
+    if one_rank:
+        _require_one_rank(cls.__name__.lower())
     likelihood, kernel = _likelihood_and_kernel_for_sgpr(model_cfg, data)
-    return SGPR((np.asarray(data[0]), _targets(data[1])), likelihood, kernel, dtype=_STATE["dtype"])
-
-
-@create_model.register
-def _create_model_sgprn2m(model_cfg: SGPRN2MConfig, data: Data):
-    """SGPR with the N^2M log-det bound.  One rank, fp64."""
-    _require_one_rank("sgprn2m")
-    likelihood, kernel = _likelihood_and_kernel_for_sgpr(model_cfg, data)
-    return SGPRN2M((np.asarray(data[0]), _targets(data[1])), likelihood, kernel, dtype=_STATE["dtype"])
+    extra = {}
+    if tf_extras and _STATE["config_semantics"] == "tf":
+        extra = dict(max_error=model_cfg.max_error, joint_optimization=model_cfg.joint_optimization, vzero=model_cfg.vzero)
+    model = cls((np.asarray(data[0]), _targets(data[1])), likelihood, kernel, dtype=_STATE["dtype"], **extra)
+    if not one_rank:
+        _broadcast_parameters(model)
+    return model
 
 
 @create_model.register
@@ -241,9 +216,7 @@ def _create_model_gpr(model_cfg: GPRConfig, data: Data):
     """tensorflow/interface.py:200-206: noise 1.0, constant mean, the kernel of the kernel config; no inducing points.  One rank, fp64 (an fp32
     default float is refused with the library's message, which names `-t fp64`)."""
     _require_one_rank("gpr")
-    likelihood = GaussianLikelihood(lower_bound=1e-6)
-    likelihood.noise = model_cfg.params(data)["noise_variance"]
-    kernel = create_kernel(model_cfg.kernel, data)
+    likelihood, kernel = _likelihood_and_kernel(model_cfg, data)
     return ExactGPR((np.asarray(data[0]), _targets(data[1])), likelihood, kernel, dtype=_STATE["dtype"])
 
 
@@ -260,9 +233,7 @@ def _create_model_itergp(model_cfg: IterGPRConfig, data: Data):
     _require_one_rank("itergp")
     if _STATE["dtype"] != torch.float64:
         raise ValueError("model class 'itergp' needs fp64: run with -t fp64")
-    likelihood = GaussianLikelihood(lower_bound=1e-4)
-    likelihood.noise = model_cfg.params(data)["noise_variance"]
-    kernel = create_kernel(model_cfg.kernel, data)
+    likelihood, kernel = _likelihood_and_kernel(model_cfg, data, noise_lower_bound=1e-4)
     return IterGPR((np.asarray(data[0]), _targets(data[1])), likelihood, kernel, dtype=_STATE["dtype"], num_probes=model_cfg.num_probes,
                    prec_size=model_cfg.prec_size, max_error=model_cfg.max_error, max_cg_iter=model_cfg.max_cg_iter,
                    lanczos_iter=model_cfg.lanczos_iter, seed=model_cfg.seed)
@@ -369,50 +340,63 @@ def _assert_ranks_agree(model: CGLB, what: str):
         raise RuntimeError(f"ranks disagree {what}: (bound, parameter checksum) per rank = {vals.tolist()}")
 
 
-def _optimize_cglb_impl(model: CGLB, dataset, num_steps: int, logger: Logger, optimize: str = "scipy"):
-    """interface.py:445-543: warm-up evaluation outside the clock, then up to four L-BFGS-B rounds, the last two
-    without the inducing points."""
-    _require_scipy(model, optimize)
-    lbfgs = Scipy()
-    lower_bound = LowerBoundCG(model)
-    results = []
-
-    def lbfgs_closure() -> Tensor:
-        loss = -lower_bound(None)
-        stats = model.cg_stats                              # None when CG never ran (TF-twin vzero / joint_optimization)
-        # steps-per-feval / residual_error-per-feval (:476); without CG the TF optimize logs zeros (tensorflow/interface.py:296-337)
-        logger.log_for_feval(**(asdict(stats) if stats is not None else dict(steps=0, residual_error=0.0)))
-        return loss
-
-    def step_callback(*args):
-        lower_bound.cached_v_vec = False                    # :480
-        logger(*args)
-
-    def optimize_fn(params, maxiter: int, ftol: float = 0.0, gtol: float = 0.0, disp: bool = False):
-        options = dict(maxiter=maxiter, ftol=ftol, gtol=gtol, disp=disp)
-        return lbfgs.minimize(lbfgs_closure, params, options=options, step_callback=step_callback)
-
-    params = list(model.parameters())
-    with logger.no_recording():                             # :494-501
-        _loss = lbfgs_closure()
-        _grads = torch.autograd.grad(_loss, params)
+def _warm_up(evaluate, params, logger: Logger):
+    """interface.py:494-501: one evaluation with its gradient outside the recording and the clock, which starts here."""
+    with logger.no_recording():
+        torch.autograd.grad(evaluate(), params)
         if torch.cuda.is_available():                       # :499-501
             torch.cuda.synchronize()
     logger.timer.reset()
     logger.timer.start()
 
-    remaining = num_steps
+
+def _lbfgs_rounds(model: GPR, objective, num_steps: int, logger: Logger, on_evaluation=None, on_step=None):
+    """interface.py:445-543: warm-up evaluation outside the clock, then up to four L-BFGS-B rounds on loss = -objective, the last two
+    without the inducing points (if the model has any).  `on_evaluation` runs after every evaluation, `on_step` before the logger at
+    every accepted step."""
+    lbfgs = Scipy()
+
+    def closure() -> Tensor:
+        loss = -objective(None)
+        if on_evaluation is not None:
+            on_evaluation()
+        return loss
+
+    def step_callback(*args):
+        if on_step is not None:
+            on_step()
+        logger(*args)
+
+    params = list(model.parameters())
+    _warm_up(closure, params, logger)
+    results, remaining = [], num_steps
     for round_id in range(4):                               # :507-543
         if remaining <= 0:
             break
-        if round_id == 2:
-            ips = model.covar_module.inducing_points
-            params = [p for p in model.parameters() if id(p) != id(ips)]
-        result = optimize_fn(params, remaining)
+        ips = getattr(model.covar_module, "inducing_points", None)
+        if round_id == 2 and ips is not None:
+            params = [p for p in model.parameters() if p is not ips]
+        result = lbfgs.minimize(closure, params, options=dict(maxiter=remaining, ftol=0.0, gtol=0.0, disp=False), step_callback=step_callback)
         remaining -= result.nit
         results.append(result)
         _assert_ranks_agree(model, f"after optimisation round {round_id}")
     return results
+
+
+def _optimize_cglb_impl(model: CGLB, dataset, num_steps: int, logger: Logger, optimize: str = "scipy"):
+    """The rounds of `_lbfgs_rounds` with the CG statistics logged at every evaluation and the cached v dropped at every step (:476-481)."""
+    _require_scipy(model, optimize)
+    lower_bound = LowerBoundCG(model)
+
+    def log_cg_stats():
+        stats = model.cg_stats                              # None when CG never ran (TF-twin vzero / joint_optimization)
+        # steps-per-feval / residual_error-per-feval (:476); without CG the TF optimize logs zeros (tensorflow/interface.py:296-337)
+        logger.log_for_feval(**(asdict(stats) if stats is not None else dict(steps=0, residual_error=0.0)))
+
+    def drop_cached_v():
+        lower_bound.cached_v_vec = False                    # :480
+
+    return _lbfgs_rounds(model, lower_bound, num_steps, logger, log_cg_stats, drop_cached_v)
 
 
 @optimize.register
@@ -421,56 +405,15 @@ def _optimize_sgpr(model: SGPR, dataset, num_steps: int, logger: Logger, optimiz
     tensorflow/interface.py:296-337)."""
     _require_scipy(model, optimize)
     with _narrow_host_pools():
-        lbfgs = Scipy()
-        bound = LowerBoundSGPR(model)
-
-        def closure() -> Tensor:
-            return -bound(None)
-
-        params = list(model.parameters())
-        with logger.no_recording():
-            torch.autograd.grad(closure(), params)
-            torch.cuda.synchronize()
-        logger.timer.reset()
-        logger.timer.start()
-        results, remaining = [], num_steps
-        for round_id in range(4):
-            if remaining <= 0:
-                break
-            if round_id == 2:
-                ips = model.covar_module.inducing_points
-                params = [p for p in model.parameters() if id(p) != id(ips)]
-            result = lbfgs.minimize(closure, params, options=dict(maxiter=remaining, ftol=0.0, gtol=0.0, disp=False), step_callback=logger)
-            remaining -= result.nit
-            results.append(result)
-        return results
+        return _lbfgs_rounds(model, LowerBoundSGPR(model), num_steps, logger)
 
 
 @optimize.register
 def _optimize_gpr(model: ExactGPR, dataset, num_steps: int, logger: Logger, optimize: str = "scipy"):
-    """The L-BFGS-B rounds of `_optimize_sgpr` on loss = -lml; there are no inducing points to leave out of the later rounds."""
+    """The same rounds on loss = -lml; there are no inducing points to leave out of the later rounds."""
     _require_scipy(model, optimize)
     with _narrow_host_pools():
-        lbfgs = Scipy()
-        lml = LogMarginalLikelihood(model)
-
-        def closure() -> Tensor:
-            return -lml(None)
-
-        params = list(model.parameters())
-        with logger.no_recording():
-            torch.autograd.grad(closure(), params)
-            torch.cuda.synchronize()
-        logger.timer.reset()
-        logger.timer.start()
-        results, remaining = [], num_steps
-        for _round in range(4):
-            if remaining <= 0:
-                break
-            result = lbfgs.minimize(closure, params, options=dict(maxiter=remaining, ftol=0.0, gtol=0.0, disp=False), step_callback=logger)
-            remaining -= result.nit
-            results.append(result)
-        return results
+        return _lbfgs_rounds(model, LogMarginalLikelihood(model), num_steps, logger)
 
 
 def _require_scipy(model, optimizer: str):
@@ -505,11 +448,7 @@ def _optimize_itergp(model: IterGPR, dataset, num_steps: int, logger: Logger, op
         lml = StochasticLogMarginalLikelihood(model)
         params = list(model.parameters())
         adam = torch.optim.Adam(params, lr=lr)
-        with logger.no_recording():
-            torch.autograd.grad(-lml(None), params)
-            torch.cuda.synchronize()
-        logger.timer.reset()
-        logger.timer.start()
+        _warm_up(lambda: -lml(None), params, logger)
         losses = []
         for step in range(num_steps):
             adam.zero_grad()
@@ -531,66 +470,76 @@ def _save(model: GPR, logdir: str):  # interface.py:546-551: json_tricks.dump(mo
         jsonio.dump(params, file)
 
 
+def _load_hypers(model: GPR, kernel: ScaleKernel, filepath: str) -> dict:
+    """The entries every model class has, assigned from a model.json written by `save`; returns all of them."""
+    params = jsonio.load(filepath)   # decodes the __ndarray__ objects json_tricks / `save` write; plain lists work too
+    model.likelihood.noise_covar._noise.set(params[".likelihood.variance"], exact=True)   # exact: the values `save` wrote, bit for bit
+    with torch.no_grad():
+        model.mean_module.constant.copy_(torch.as_tensor(np.asarray(params[".mean_function.c"]), dtype=torch.float64).reshape(()))
+    kernel.base_kernel._lengthscale.set(params[".kernel.lengthscales"], exact=True)
+    kernel._outputscale.set(params[".kernel.variance"], exact=True)
+    return params
+
+
 @load.register
 def _load(model: GPR, filepath: str):
     """Reads a model.json written by `save` (the reference's torch `load` expects a state_dict and is asymmetric
     with its own `save`; here the pair round-trips)."""
-    params = jsonio.load(filepath)   # decodes the __ndarray__ objects json_tricks / `save` write; plain lists work too
-    model.likelihood.noise = params[".likelihood.variance"]
+    params = _load_hypers(model, model.covar_module.base_kernel, filepath)
     with torch.no_grad():
-        model.mean_module.constant.copy_(torch.as_tensor(np.asarray(params[".mean_function.c"]), dtype=torch.float64).reshape(()))
         model.covar_module.inducing_points.copy_(torch.as_tensor(np.asarray(params[".inducing_variable.Z"]), dtype=torch.float64))
-    model.covar_module.base_kernel.base_kernel.lengthscale = params[".kernel.lengthscales"]
-    model.covar_module.base_kernel.outputscale = params[".kernel.variance"]
     return model
 
 
-@load.register
-def _load_gpr(model: ExactGPR, filepath: str):
+@load.register(ExactGPR)
+@load.register(IterGPR)   # the same module tree and parameter keys
+def _load_gpr(model: GPR, filepath: str):
     """Parameters saved by ANY model class (cli.py:166-181 evaluates the exact metrics at hyper-parameters a sparse model was trained to): an
     inducing-point entry is ignored."""
-    params = jsonio.load(filepath)
-    model.likelihood.noise = params[".likelihood.variance"]
-    with torch.no_grad():
-        model.mean_module.constant.copy_(torch.as_tensor(np.asarray(params[".mean_function.c"]), dtype=torch.float64).reshape(()))
-    model.covar_module.base_kernel.lengthscale = params[".kernel.lengthscales"]
-    model.covar_module.outputscale = params[".kernel.variance"]
+    _load_hypers(model, model.covar_module, filepath)
     return model
 
 
-load.register(IterGPR, _load_gpr)   # the same module tree and parameter keys
+def _rmse_and_lpd_fn(model: GPR, predictor_cls, dataset_bundle, max_batch: int = int(1e6)):
+    """interface.py:627-655: rmse / nlpd of `predictor_cls(model)` on the train and test sets, over all outputs, predicted in one pass of
+    at most `max_batch` rows at a time."""
+    train, test = dataset_bundle
+    x_full = np.concatenate([np.asarray(train[0]), np.asarray(test[0])], axis=0)
+    y_full = np.concatenate([_targets_2d(train[1]), _targets_2d(test[1])], axis=0)  # [n, P]
+    n = np.asarray(train[0]).shape[0]
+
+    def error_and_logdensity():
+        predict_f = predictor_cls(model)
+        lpds, errs = [], []
+        with torch.no_grad():
+            for i in range(0, int(x_full.shape[0]), max_batch):
+                f_mean, f_var = predict_f(torch.as_tensor(x_full[i: i + max_batch]))
+                y_batch = torch.as_tensor(y_full[i: i + max_batch], dtype=f_mean.dtype, device=f_mean.device)
+                lpds.append(_numpy(log_density(model, y_batch, f_mean, f_var)))
+                errs.append(_numpy(y_batch - f_mean))
+        err, lpd = np.concatenate(errs, axis=0), np.concatenate(lpds, axis=0)
+        return (err[:n], err[n:]), (lpd[:n], lpd[n:])
+
+    return metric.rmse_and_lpd_fn(error_and_logdensity)
 
 
 @metrics_fn.register
 def _compute_metrics_gpr(model: ExactGPR, dataset_bundle):
     """tensorflow/interface.py:386-395: lml, loss = -lml, and rmse / nlpd of the exact predictive on the train and test sets."""
-    train, test = dataset_bundle
 
     def gpr_metrics():
         with torch.no_grad():
             lml = _numpy(LogMarginalLikelihood(model)(None))
         return dict(lml=lml, loss=-lml)
 
-    x_full = np.concatenate([np.asarray(train[0]), np.asarray(test[0])], axis=0)
-    y_full = np.concatenate([np.asarray(train[1]).reshape(-1), np.asarray(test[1]).reshape(-1)], axis=0).reshape(-1, 1)
-
-    def error_and_logdensity():
-        predict_f = PredictGPR(model)
-        with torch.no_grad():
-            f_mean, f_var = predict_f(torch.as_tensor(x_full))   # the library works through the new points in batches of 4096
-            y = torch.as_tensor(y_full, dtype=f_mean.dtype, device=f_mean.device)
-            lpd, err = _numpy(log_density(model, y, f_mean, f_var)), _numpy(y - f_mean)
-        n = np.asarray(train[0]).shape[0]
-        return (err[:n], err[n:]), (lpd[:n], lpd[n:])
-
-    return lambda: metric.call_metric_fns(gpr_metrics, metric.rmse_and_lpd_fn(error_and_logdensity))
+    rmse_lpd_metrics = _rmse_and_lpd_fn(model, PredictGPR, dataset_bundle)
+    return lambda: metric.call_metric_fns(gpr_metrics, rmse_lpd_metrics)
 
 
 @metrics_fn.register
 def _compute_metrics_itergp(model: IterGPR, dataset_bundle):
     """The metrics of the exact class from the iterative estimator: lml (one draw of the probes), loss = -lml, and rmse / nlpd of the predictive
     on the train and test sets; the variances cost (n_train + n_test) / 8 batched solves."""
-    train, test = dataset_bundle
 
     def itergp_metrics():
         with torch.no_grad():
@@ -598,19 +547,8 @@ def _compute_metrics_itergp(model: IterGPR, dataset_bundle):
         stats = model.cg_stats
         return {"lml": lml, "loss": -lml, "cg/steps": stats.steps, "cg/error": stats.residual_error}
 
-    x_full = np.concatenate([np.asarray(train[0]), np.asarray(test[0])], axis=0)
-    y_full = np.concatenate([np.asarray(train[1]).reshape(-1), np.asarray(test[1]).reshape(-1)], axis=0).reshape(-1, 1)
-
-    def error_and_logdensity():
-        predict_f = PredictIterGPR(model)
-        with torch.no_grad():
-            f_mean, f_var = predict_f(torch.as_tensor(x_full))
-            y = torch.as_tensor(y_full, dtype=f_mean.dtype, device=f_mean.device)
-            lpd, err = _numpy(log_density(model, y, f_mean, f_var)), _numpy(y - f_mean)
-        n = np.asarray(train[0]).shape[0]
-        return (err[:n], err[n:]), (lpd[:n], lpd[n:])
-
-    return lambda: metric.call_metric_fns(itergp_metrics, metric.rmse_and_lpd_fn(error_and_logdensity))
+    rmse_lpd_metrics = _rmse_and_lpd_fn(model, PredictIterGPR, dataset_bundle)
+    return lambda: metric.call_metric_fns(itergp_metrics, rmse_lpd_metrics)
 
 
 @metrics_fn.register
@@ -622,59 +560,27 @@ def _compute_metrics_cglb(model: CGLB, dataset_bundle):
             return {"cg/steps": _numpy(model.cg_stats.steps), "cg/error": _numpy(model.cg_stats.residual_error)}
         return {}
 
-    train, test = dataset_bundle
-
     def cglb_metrics():
         with torch.no_grad():
             lower_bound = LowerBoundCG(model, use_cache=True, cached_v_vec_initial=True)  # no CG: reuse model.v_vec (:619-625)
             loss = -lower_bound(None)
             return dict(loss=_numpy(loss))
 
-    x_full = np.concatenate([np.asarray(train[0]), np.asarray(test[0])], axis=0)
-    y_full = np.concatenate([_targets_2d(train[1]), _targets_2d(test[1])], axis=0)  # [n, P]: rmse / lpd over all outputs
-    total = int(x_full.shape[0])
-
-    def error_and_logdensity():
-        predict_f = PredictCG(model)
-        lpds, errs = [], []
-        max_batch = int(1e6)
-        with torch.no_grad():
-            for i in range(0, total, max_batch):
-                f_mean, f_var = predict_f(torch.as_tensor(x_full[i: i + max_batch]))
-                y_batch = torch.as_tensor(y_full[i: i + max_batch], dtype=f_mean.dtype, device=f_mean.device)
-                lpds.append(_numpy(log_density(model, y_batch, f_mean, f_var)))
-                errs.append(_numpy(y_batch - f_mean))
-        err, lpd = np.concatenate(errs, axis=0), np.concatenate(lpds, axis=0)
-        n = np.asarray(train[0]).shape[0]
-        return (err[:n], err[n:]), (lpd[:n], lpd[n:])
-
-    rmse_lpd_metrics = metric.rmse_and_lpd_fn(error_and_logdensity)
+    rmse_lpd_metrics = _rmse_and_lpd_fn(model, PredictCG, dataset_bundle)
     return lambda: metric.call_metric_fns(cglb_cg_params, cglb_metrics, rmse_lpd_metrics)
 
 
 @metrics_fn.register
 def _compute_metrics_sgpr(model: SGPR, dataset_bundle):
     """tensorflow/interface.py:395-408 without titsias_upper_bound: loss = -elbo, and rmse / nlpd of the Titsias predictive."""
-    train, test = dataset_bundle
 
     def sgpr_metrics():
         with torch.no_grad():
             elbo = _numpy(LowerBoundSGPR(model)(None))
         return dict(elbo=elbo, loss=-elbo)
 
-    x_full = np.concatenate([np.asarray(train[0]), np.asarray(test[0])], axis=0)
-    y_full = np.concatenate([np.asarray(train[1]).reshape(-1), np.asarray(test[1]).reshape(-1)], axis=0).reshape(-1, 1)
-
-    def error_and_logdensity():
-        predict_f = PredictSGPR(model)
-        with torch.no_grad():
-            f_mean, f_var = predict_f(torch.as_tensor(x_full))
-            y = torch.as_tensor(y_full, dtype=f_mean.dtype, device=f_mean.device)
-            lpd, err = _numpy(log_density(model, y, f_mean, f_var)), _numpy(y - f_mean)
-        n = np.asarray(train[0]).shape[0]
-        return (err[:n], err[n:]), (lpd[:n], lpd[n:])
-
-    return lambda: metric.call_metric_fns(sgpr_metrics, metric.rmse_and_lpd_fn(error_and_logdensity))
+    rmse_lpd_metrics = _rmse_and_lpd_fn(model, PredictSGPR, dataset_bundle)
+    return lambda: metric.call_metric_fns(sgpr_metrics, rmse_lpd_metrics)
 
 
 def _numpy(tensor) -> np.ndarray:

@@ -45,12 +45,24 @@ class _Constrained(nn.Module):
     def value(self) -> Tensor:
         return F.softplus(self.raw) + self.lower_bound
 
-    def set(self, value):
-        v = torch.as_tensor(value, dtype=torch.float64).reshape(self.raw.shape) - self.lower_bound
+    def set(self, value, exact: bool = False):
+        """raw = inv_softplus(value - lower_bound), which gives `value` back to a unit in the last place.  `exact` (what `load` asks for, so
+        that a saved model loads bit for bit): the raw that gives it back exactly, wherever there is one within 1e-9 of that."""
+        target = torch.as_tensor(value, dtype=torch.float64).reshape(self.raw.shape)
+        v = target - self.lower_bound
         if (v <= 0).any():
             raise ValueError(f"value must exceed the lower bound {self.lower_bound}")
+        raw = _inv_softplus(v)
+        if exact:   # bisection for the smallest raw whose value is not below the target; kept if its value is the target
+            width = 1e-9 * raw.abs().clamp(min=1.0)
+            lo, hi = raw - width, raw + width
+            for _ in range(64):
+                mid = lo + (hi - lo) / 2
+                below = F.softplus(mid) + self.lower_bound < target
+                lo, hi = torch.where(below, mid, lo), torch.where(below, hi, mid)
+            raw = torch.where(F.softplus(hi) + self.lower_bound == target, hi, raw)
         with torch.no_grad():
-            self.raw.copy_(_inv_softplus(v))
+            self.raw.copy_(raw)
 
 
 class BaseKernel(nn.Module):
@@ -144,42 +156,6 @@ class GPR(nn.Module):
     def num_outputs(self) -> int:
         return int(self.train_targets.shape[1]) if self.train_targets.dim() == 2 else 1
 
-
-def _variant_context(model, data_x, data_y, num_inducing: int, kind: str, dtype, device, context):
-    """The HIP context of a model whose bound is not plain CGLB: one rank only (the N-rank path implements the Jensen / CG bound), with the
-    two bound options set on it (include/cglb_hip.h "logdet_bound", "quad_term")."""
-    name = type(model).__name__
-    if context is None:
-        import torch.distributed as dist
-        if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
-            raise NotImplementedError(f"{name} is not available on more than one rank (only CGLB runs row-sharded); "
-                                      f"run it as a single process")
-        context = HipContext(data_x, data_y, num_inducing, kind, dtype=dtype, device=device)
-    elif getattr(context, "world", 1) > 1:
-        raise NotImplementedError(f"{name} is not available on more than one rank (only CGLB runs row-sharded)")
-    context.set_option("logdet_bound", model.LOGDET_BOUND)
-    context.set_option("quad_term", model.QUAD_TERM)
-    return context
-
-
-class SGPR(GPR):
-    """Titsias' collapsed bound (tensorflow/models.py:353-413 with the NM^2 trace term): the exact quadratic term at v = 0 - no solve, no
-    N^2 work - and the log-det bound of option LOGDET_BOUND (1: NM^2, the SGPR ELBO; 2: N^2M, SGPRN2M).  Same module tree and parameter
-    keys as CGLB; no v_vec, no cg_stats."""
-
-    LOGDET_BOUND = 1
-    QUAD_TERM = 1
-
-    def __init__(self, data: Data, likelihood: GaussianLikelihood, kernel: InducingPointKernel, dtype: torch.dtype = torch.float64,
-                 device: Optional[torch.device] = None, context=None):
-        super().__init__(data, likelihood, kernel)
-        self.dtype = dtype
-        if self.num_outputs > 1:
-            raise NotImplementedError(f"{type(self).__name__} is not available for more than one target column (only CGLB takes [N, P] targets)")
-        kind = kernel.base_kernel.base_kernel.kind
-        self.hip = _variant_context(self, self.train_inputs[0], self.train_targets, kernel.inducing_points.shape[0], kind, dtype, device, context)
-        self._zero_v = torch.zeros(self.hip.N, dtype=dtype, device=self.hip.device)  # the library treats v as 0 (quad_term 1); shape check only
-
     def check_same_data(self, data: Data) -> None:
         """ValueError unless (x, y) is the training set the HIP context was built on (same shapes and content).  The full comparison
         runs once per data object: the last accepted pair is remembered (weakly), so an
@@ -208,6 +184,49 @@ class SGPR(GPR):
             self._accepted_data = (weakref.ref(x_in), weakref.ref(y_in))
         except TypeError:  # lists / scalars cannot be weakly referenced: compared in full every time
             self._accepted_data = None
+
+
+_ONE_RANK = "{name} is not available on more than one rank (only CGLB runs row-sharded)"
+
+
+def _one_rank_context(name: str, context, data_x, data_y, num_inducing: int, kind: str, dtype, device):
+    """The HIP context of a class that runs on one rank only: the one handed in, or a new `HipContext`; refused on more than one rank."""
+    if context is None:
+        import torch.distributed as dist
+        if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+            raise NotImplementedError(_ONE_RANK.format(name=name) + "; run it as a single process")
+        return HipContext(data_x, data_y, num_inducing, kind, dtype=dtype, device=device)
+    if getattr(context, "world", 1) > 1:
+        raise NotImplementedError(_ONE_RANK.format(name=name))
+    return context
+
+
+def _variant_context(model, data_x, data_y, num_inducing: int, kind: str, dtype, device, context):
+    """The HIP context of a model whose bound is not plain CGLB: one rank only (the N-rank path implements the Jensen / CG bound), with the
+    two bound options set on it (include/cglb_hip.h "logdet_bound", "quad_term")."""
+    context = _one_rank_context(type(model).__name__, context, data_x, data_y, num_inducing, kind, dtype, device)
+    context.set_option("logdet_bound", model.LOGDET_BOUND)
+    context.set_option("quad_term", model.QUAD_TERM)
+    return context
+
+
+class SGPR(GPR):
+    """Titsias' collapsed bound (tensorflow/models.py:353-413 with the NM^2 trace term): the exact quadratic term at v = 0 - no solve, no
+    N^2 work - and the log-det bound of option LOGDET_BOUND (1: NM^2, the SGPR ELBO; 2: N^2M, SGPRN2M).  Same module tree and parameter
+    keys as CGLB; no v_vec, no cg_stats."""
+
+    LOGDET_BOUND = 1
+    QUAD_TERM = 1
+
+    def __init__(self, data: Data, likelihood: GaussianLikelihood, kernel: InducingPointKernel, dtype: torch.dtype = torch.float64,
+                 device: Optional[torch.device] = None, context=None):
+        super().__init__(data, likelihood, kernel)
+        self.dtype = dtype
+        if self.num_outputs > 1:
+            raise NotImplementedError(f"{type(self).__name__} is not available for more than one target column (only CGLB takes [N, P] targets)")
+        kind = kernel.base_kernel.base_kernel.kind
+        self.hip = _variant_context(self, self.train_inputs[0], self.train_targets, kernel.inducing_points.shape[0], kind, dtype, device, context)
+        self._zero_v = torch.zeros(self.hip.N, dtype=dtype, device=self.hip.device)  # the library treats v as 0 (quad_term 1); shape check only
 
     # constrained hyper-parameters, as tensors attached to the raw parameters
     def hyper_tensors(self):
@@ -301,6 +320,81 @@ class CGLBNM2(CGLB):
     LOGDET_BOUND = 1
 
 
+class _NoInducingGPR(GPR):
+    """The module tree and parameter keys of the SGPR family without the inducing points: `covar_module` is the ScaleKernel itself."""
+
+    def hyper_tensors(self):
+        k = self.covar_module
+        return (k.base_kernel.lengthscale.reshape(-1), k.outputscale.reshape(()), self.likelihood.noise.reshape(()),
+                self.mean_module.constant.reshape(()))
+
+
+class ExactGPR(_NoInducingGPR):
+    """Exact GP regression (GPRConfig: tensorflow/interface.py:200-206 builds gpflow's GPR with a constant mean; pytorch/interface.py:561-604
+    trains it on ExactMarginalLogLikelihood times n).  The N x N kernel matrix is factored on the GPU (cglb_gpr_*: fp64, one rank, one
+    target column)."""
+
+    def __init__(self, data: Data, likelihood: GaussianLikelihood, kernel: ScaleKernel, dtype: torch.dtype = torch.float64,
+                 device: Optional[torch.device] = None, context=None):
+        super().__init__(data, likelihood, kernel)
+        self.dtype = dtype
+        if self.num_outputs > 1:
+            raise NotImplementedError("ExactGPR is not available for more than one target column (only CGLB takes [N, P] targets)")
+        # M = 1: placeholder
+        self.hip = _one_rank_context("ExactGPR", context, self.train_inputs[0], self.train_targets, 1, kernel.base_kernel.kind, dtype, device)
+        self.push_hypers()   # an fp32 context is refused here, with the library's message, not at the first evaluation
+
+    def push_hypers(self):
+        ls, var, noise, mean = [t.detach() for t in self.hyper_tensors()]
+        self.hip.gpr_set_hypers(ls.cpu().numpy(), float(var), float(noise), float(mean))
+
+
+class IterGPR(_NoInducingGPR):
+    """Iterative exact GP regression: the "Iterative GP" baseline (pytorch/interface.py:233-260 builds it on gpytorch's ExactGP with a
+    pivoted-Cholesky preconditioner of rank `_prec_size()` = 100, batched CG and stochastic Lanczos quadrature).  The module tree and parameter
+    keys of ExactGPR; O(N) memory.  The estimator is the library's (cglb_itergp_*: fp64, one rank, one target column): `num_probes` probe
+    vectors drawn on the host from this model's generator, one batched solve warm-started at the persistent `v_vec`, the log-determinant from
+    the Lanczos coefficients of the solve.  gpytorch's random numbers and stop rule are not reproduced."""
+
+    def __init__(self, data: Data, likelihood: GaussianLikelihood, kernel: ScaleKernel, dtype: torch.dtype = torch.float64,
+                 device: Optional[torch.device] = None, context=None, num_probes: int = 10, prec_size: int = 100, max_error: float = 1.0,
+                 max_cg_iter: int = 1000, lanczos_iter: int = 20, seed: int = 0, deterministic_probes: bool = False):
+        super().__init__(data, likelihood, kernel)
+        self.dtype = dtype
+        if self.num_outputs > 1:
+            raise NotImplementedError("IterGPR is not available for more than one target column (only CGLB takes [N, P] targets)")
+        if dtype != torch.float64:
+            raise ValueError("the iterative exact GP class needs fp64 (-t fp64)")
+        n = int(self.train_inputs[0].shape[0])
+        self.num_probes, self.prec_size = int(num_probes), min(int(prec_size), n)
+        self.max_error, self.max_cg_iter, self.lanczos_iter = float(max_error), int(max_cg_iter), int(lanczos_iter)
+        context = _one_rank_context("IterGPR", context, self.train_inputs[0], self.train_targets, self.prec_size, kernel.base_kernel.kind, dtype, device)
+        self.hip = context
+        self.register_buffer("v_vec", torch.zeros(n, dtype=dtype, device=context.device), persistent=False)   # the warm start of the data column
+        self.generator = torch.Generator(device="cpu")
+        self.generator.manual_seed(int(seed))
+        self.deterministic_probes = bool(deterministic_probes)
+        self._eps = None
+        self.cg_stats: Optional[ConjugateGradientStats] = None
+        self._placeholder_Z = self.train_inputs[0][:self.prec_size].detach().cpu().to(torch.float64)   # replaced by the pivots at every evaluation
+        self._pushed = None
+
+    def probes(self) -> Tensor:
+        """[num_probes, prec_size + N] standard-normal draws: fresh at every call, or one draw kept when `deterministic_probes`."""
+        if self._eps is None or not self.deterministic_probes:
+            self._eps = torch.randn(self.num_probes, self.prec_size + self.hip.N, dtype=torch.float64, generator=self.generator)
+        return self._eps
+
+    def push_hypers(self, jitter: float):
+        """Hands the hyper-parameters to the library unless these very values are already there: a new set_hypers would make the library
+        forget the preconditioner and the alpha of its last evaluation, which the predictive solve starts from."""
+        ls, var, noise, mean = [t.detach() for t in self.hyper_tensors()]
+        key = (ls.cpu().numpy().tobytes(), float(var), float(noise), float(mean), float(jitter))
+        if key != self._pushed:
+            self.hip.set_hypers(ls.cpu().numpy(), float(var), float(noise), float(mean), self._placeholder_Z, jitter)
+            self._pushed = key
+
+
 @dataclass
 class Bounds:
     upper_bound: Tensor
@@ -318,44 +412,16 @@ def get_cholesky_jitter() -> float:
     return _DEFAULT_JITTER["value"]
 
 
-class _BoundFunction(torch.autograd.Function):
-    """bound(lengthscales, variance, noise, mean, Z) with the analytic gradient from the GPU (row G of SURVEY 8a)."""
+class _Evaluation(torch.autograd.Function):
+    """value(*inputs) with the analytic gradient from the GPU (row G of SURVEY 8a).  `evaluate(needs)` makes the library call at the model's
+    current hyper-parameters, which `inputs` are, and returns (value, gradient dict or None, gradient of a trainable v or None); `needs`
+    says which inputs want a gradient.  The inputs come in the order lengthscales, variance, noise, mean[, Z[, v]]."""
 
     @staticmethod
-    def forward(ctx, owner, ls, var, noise, mean, Z, v_param=None):
-        model = owner.model
-        hip = model.hip
-        hip.set_hypers(ls.detach().cpu().numpy(), float(var), float(noise), float(mean), Z.detach().cpu(), get_cholesky_jitter())
-        need_grad = any(ctx.needs_input_grad[1:])
-        multi = getattr(model, "num_outputs", 1) > 1
-        v = model.v_vec.detach() if multi else model.v_vec.detach().reshape(-1)   # [N, P] as it is; one output: the flat vector
-        run_cg = not (owner._use_cache and owner.cached_v_vec)          # models.py:263
-        if model.joint_optimization or model.vzero:                     # tensorflow/models.py:161-164: v0 is used as it stands
-            run_cg = False
-        cg = owner.cg_opt
-        if run_cg and multi and type(cg) is not ConjugateGradient:
-            raise NotImplementedError("a plug-in solver is not available for more than one target column (the batched PCG runs in the library)")
-        if run_cg and type(cg) is not ConjugateGradient:
-            # foreign plug-in solver through the seam (models.py:266-271): cg_opt(A, b, v, precond)
-            hip.setup()
-            err = (hip.y - float(mean)).reshape(-1, 1)
-            new_v, stats = cg(KernelOperator(hip), err, model.v_vec, NystromPreconditioner(hip))
-            model.cg_stats = stats
-            model.v_vec.data.copy_(new_v.reshape(model.v_vec.shape))
-            res = hip.objective_and_grad(v, False, with_grad=need_grad)
-        else:
-            res = hip.objective_and_grad(v, run_cg, cg.max_error, cg.max_cg_iter, cg.restart_cg_iter, with_grad=need_grad)
-            if run_cg:
-                model.cg_stats = ConjugateGradientStats(res.steps, torch.tensor(res.residual_error, dtype=torch.float64))
-        if run_cg:
-            owner.cached_v_vec = owner._use_cache                       # models.py:278
-        owner.last_bounds = Bounds(upper_bound=torch.tensor(-res.upper), lower_bound=torch.tensor(-res.lower))  # models.py:286
-        model.last_bound = float(res.bound)  # value of the most recent evaluation (diagnostics / tests)
-        ctx.grads = res.grad
-        ctx.grad_v = None
-        if v_param is not None and ctx.needs_input_grad[6]:            # joint optimisation: d bound / d v = K w - r, one more mat-vec
-            ctx.grad_v = hip.objective_grad_v().reshape(v_param.shape)
-        return torch.tensor(res.bound, dtype=torch.float64)
+    def forward(ctx, evaluate, *inputs):
+        value, ctx.grads, ctx.grad_v = evaluate(ctx.needs_input_grad[1:])
+        ctx.with_v = len(inputs) > 5
+        return torch.tensor(value, dtype=torch.float64)
 
     @staticmethod
     def backward(ctx, gout):
@@ -363,20 +429,51 @@ class _BoundFunction(torch.autograd.Function):
         if g is None:
             raise RuntimeError("gradient was not requested in forward")
         gout = gout.to(torch.float64)
-        gv = None if ctx.grad_v is None else gout.to(ctx.grad_v.device) * ctx.grad_v
-        return (None, gout * torch.from_numpy(g["lengthscales"]), gout * g["variance"], gout * g["noise"], gout * g["mean"],
-                gout * torch.from_numpy(g["Z"]), gv)
+        grads = [gout * (torch.from_numpy(g[key]) if key in ("lengthscales", "Z") else g[key])
+                 for key in ("lengthscales", "variance", "noise", "mean", "Z") if key in g]
+        if ctx.with_v:
+            grads.append(None if ctx.grad_v is None else gout.to(ctx.grad_v.device) * ctx.grad_v)
+        return (None, *grads)
 
 
-class LowerBoundCG(nn.Module):
+class _Objective(nn.Module):
+    """`Objective(model)(data)`: the model class's training objective through `_Evaluation`.  A subclass names the model class it takes
+    (MODEL, and NOT_MODEL for the subclasses of it that it refuses) and makes the library call in `evaluate`.  `data` must be None or the
+    model's own training set."""
+
+    MODEL: type = GPR
+    NOT_MODEL: tuple = ()
+    EXPECTED = "GPR"
+
+    def __init__(self, model):
+        if not isinstance(model, self.MODEL) or isinstance(model, self.NOT_MODEL):
+            raise ValueError(f"{self.EXPECTED} model expected in the constructor of the {self.__class__}")
+        super().__init__()
+        object.__setattr__(self, "model", model)  # not a sub-module: parameters stay owned by the model
+
+    def inputs(self):
+        return self.model.hyper_tensors()
+
+    def evaluate(self, needs):
+        raise NotImplementedError()
+
+    def forward(self, data: Optional[Tuple[Tensor, Tensor]] = None, *params) -> Tensor:
+        """The reference evaluates the bound on the `data` it is given (models.py:151-169); here the training set lives in the
+        model's HIP context, so `data` must be None or that same training set: anything else (a subset, a held-out set) raises
+        instead of silently returning the bound of the training data."""
+        if data is not None:
+            self.model.check_same_data(data)
+        return _Evaluation.apply(self.evaluate, *self.inputs())
+
+
+class LowerBoundCG(_Objective):
     """models.py:104-286.  `LowerBoundCG(model)(data)` returns the lower bound on the log marginal likelihood."""
+
+    MODEL, EXPECTED = SGPR, "CGLB"  # models.py:112-113
 
     def __init__(self, model: SGPR, cg_opt: Optional[ConjugateGradient] = None, use_cache: bool = False,
                  cached_v_vec_initial: bool = False):
-        if not isinstance(model, SGPR):
-            raise ValueError(f"CGLB model expected in the constructor of the {self.__class__}")  # models.py:112-113
-        super().__init__()
-        object.__setattr__(self, "model", model)  # not a sub-module: parameters stay owned by the model
+        super().__init__(model)
         if cg_opt is None:  # the model carries a tolerance only under the TF twin's config semantics (tensorflow/models.py:36-51)
             tol = getattr(model, "max_error", None)
             cg_opt = ConjugateGradient() if tol is None else ConjugateGradient(max_error=float(tol))
@@ -409,15 +506,91 @@ class LowerBoundCG(nn.Module):
     def noise(self) -> Tensor:
         return self.likelihood.noise.squeeze()
 
-    def forward(self, data: Optional[Tuple[Tensor, Tensor]] = None, *params) -> Tensor:
-        """The reference evaluates the bound on the `data` it is given (models.py:151-169); here the training set lives in the
-        model's HIP context, so `data` must be None or that same training set: anything else (a subset, a held-out set) raises
-        instead of silently returning the bound of the training data."""
-        if data is not None:
-            self.model.check_same_data(data)
-        ls, var, noise, mean, Z = self.model.hyper_tensors()
-        v_param = self.model.v_vec if isinstance(self.model.v_vec, nn.Parameter) else None
-        return _BoundFunction.apply(self, ls, var, noise, mean, Z, v_param)
+    def inputs(self):
+        v_vec = self.model.v_vec
+        return (*self.model.hyper_tensors(), v_vec if isinstance(v_vec, nn.Parameter) else None)
+
+    def evaluate(self, needs):
+        model, hip = self.model, self.model.hip
+        model.push_hypers(get_cholesky_jitter())
+        need_grad = any(needs)
+        multi = getattr(model, "num_outputs", 1) > 1
+        v = model.v_vec.detach() if multi else model.v_vec.detach().reshape(-1)   # [N, P] as it is; one output: the flat vector
+        run_cg = not (self._use_cache and self.cached_v_vec)            # models.py:263
+        if model.joint_optimization or model.vzero:                     # tensorflow/models.py:161-164: v0 is used as it stands
+            run_cg = False
+        cg = self.cg_opt
+        if run_cg and multi and type(cg) is not ConjugateGradient:
+            raise NotImplementedError("a plug-in solver is not available for more than one target column (the batched PCG runs in the library)")
+        if run_cg and type(cg) is not ConjugateGradient:
+            # foreign plug-in solver through the seam (models.py:266-271): cg_opt(A, b, v, precond)
+            hip.setup()
+            err = (hip.y - float(model.mean_module.constant)).reshape(-1, 1)
+            new_v, stats = cg(KernelOperator(hip), err, model.v_vec, NystromPreconditioner(hip))
+            model.cg_stats = stats
+            model.v_vec.data.copy_(new_v.reshape(model.v_vec.shape))
+            res = hip.objective_and_grad(v, False, with_grad=need_grad)
+        else:
+            res = hip.objective_and_grad(v, run_cg, cg.max_error, cg.max_cg_iter, cg.restart_cg_iter, with_grad=need_grad)
+            if run_cg:
+                model.cg_stats = ConjugateGradientStats(res.steps, torch.tensor(res.residual_error, dtype=torch.float64))
+        if run_cg:
+            self.cached_v_vec = self._use_cache                         # models.py:278
+        self.last_bounds = Bounds(upper_bound=torch.tensor(-res.upper), lower_bound=torch.tensor(-res.lower))  # models.py:286
+        model.last_bound = float(res.bound)  # value of the most recent evaluation (diagnostics / tests)
+        grad_v = None
+        if isinstance(model.v_vec, nn.Parameter) and needs[5]:          # joint optimisation: d bound / d v = K w - r, one more mat-vec
+            grad_v = hip.objective_grad_v().reshape(model.v_vec.shape)
+        return res.bound, res.grad, grad_v
+
+
+class LowerBoundSGPR(_Objective):
+    """`LowerBoundSGPR(model)(data)`: the collapsed bound of an SGPR / SGPRN2M model (tensorflow/models.py:353-413), the `elbo` of the TF
+    twin: no v, no solve."""
+
+    MODEL, NOT_MODEL, EXPECTED = SGPR, (CGLB,), "SGPR"
+
+    def evaluate(self, needs):
+        model = self.model
+        model.push_hypers(get_cholesky_jitter())
+        res = model.hip.objective_and_grad(model._zero_v, False, with_grad=any(needs))
+        model.last_bound = float(res.bound)
+        return res.bound, res.grad, None
+
+
+class LogMarginalLikelihood(_Objective):
+    """`LogMarginalLikelihood(model)(data)`: the exact log marginal likelihood of an ExactGPR model (gpflow GPR.log_marginal_likelihood)."""
+
+    MODEL, EXPECTED = ExactGPR, "ExactGPR"
+
+    def evaluate(self, needs):
+        model = self.model
+        model.push_hypers()
+        res = model.hip.gpr_objective_and_grad(with_grad=any(needs))
+        model.last_bound = float(res.lml)
+        return res.lml, res.grad, None
+
+
+class StochasticLogMarginalLikelihood(_Objective):
+    """`StochasticLogMarginalLikelihood(model)(data)`: the iterative estimate of the log marginal likelihood of an IterGPR model, with the
+    library's unbiased gradient estimate: the backward is NOT the derivative of the forward value (the log-determinant estimate and its
+    gradient use the same probes in different estimators)."""
+
+    MODEL, EXPECTED = IterGPR, "IterGPR"
+
+    def evaluate(self, needs):
+        model = self.model
+        model.push_hypers(get_cholesky_jitter())
+        res = model.hip.itergp_objective_and_grad(model.probes(), model.v_vec, model.max_error, model.max_cg_iter, model.lanczos_iter,
+                                                  with_grad=any(needs))
+        model.last_bound = float(res.lml)
+        model.cg_stats = ConjugateGradientStats(steps=res.steps, residual_error=res.residual_error)
+        return res.lml, res.grad, None
+
+
+def _refuse_full_cov(full_cov: bool):
+    if full_cov:
+        raise NotImplementedError("The predict_f method currently  supports only `full_cov=False` option")  # models.py:311-314
 
 
 class PredictCG(LowerBoundCG):
@@ -438,8 +611,7 @@ class PredictCG(LowerBoundCG):
         self.cached = False
 
     def forward(self, xnew: Tensor, full_cov: bool = False, full_output_cov: bool = False) -> Tuple[Tensor, Tensor]:
-        if full_cov:
-            raise NotImplementedError("The predict_f method currently  supports only `full_cov=False` option")  # models.py:311-314
+        _refuse_full_cov(full_cov)
         model, hip = self.model, self.model.hip
         with torch.no_grad():
             if not self.cached:
@@ -463,15 +635,92 @@ class PredictCG(LowerBoundCG):
         return f_mean.reshape(-1, 1), f_var.reshape(-1, 1)
 
 
-class PredictLogdensityCG(PredictCG):
+class _Predict(nn.Module):
+    """`Predict(model)(xnew)`: predict_f mean and variance, each [n_new, 1].  A subclass names the model class it takes (MODEL; None: any)
+    and makes the library call in `mean_and_variance`."""
+
+    MODEL: Optional[type] = None
+
+    def __init__(self, model):
+        if self.MODEL is not None and not isinstance(model, self.MODEL):
+            raise ValueError(f"{self.MODEL.__name__} model expected in the constructor of the {self.__class__}")
+        super().__init__()
+        object.__setattr__(self, "model", model)
+
+    def mean_and_variance(self, xnew):
+        raise NotImplementedError()
+
+    def forward(self, xnew: Tensor, full_cov: bool = False, full_output_cov: bool = False) -> Tuple[Tensor, Tensor]:
+        _refuse_full_cov(full_cov)
+        with torch.no_grad():
+            f_mean, f_var = self.mean_and_variance(xnew)
+        return f_mean.reshape(-1, 1), f_var.reshape(-1, 1)
+
+
+class PredictSGPR(_Predict):
+    """Titsias' predictive: PredictCG's formula (models.py:333-354) at v = 0, without a solve (cg_mean = 0, res = e)."""
+
+    def __init__(self, model: SGPR):
+        super().__init__(model)
+        self.cached = False
+
+    def mean_and_variance(self, xnew):
+        model = self.model
+        if not self.cached:
+            model.push_hypers(get_cholesky_jitter())
+            model.hip.setup()
+            self.cached = True
+        return model.hip.predict(model._zero_v, xnew)
+
+
+class PredictGPR(_Predict):
+    """predict_f of the exact model: mean c + K_*f K^-1 e, variance f - |L^-1 K_f*|^2.  The library keeps the factor of the last evaluation at
+    the current hyper-parameters and factors first if there is none."""
+
+    MODEL = ExactGPR
+
+    def mean_and_variance(self, xnew):
+        self.model.push_hypers()
+        return self.model.hip.gpr_predict(xnew)
+
+
+class PredictIterGPR(_Predict):
+    """predict_f of the iterative model: mean c + K_*f alpha from one solve at `max_error` (1e-3 like PredictCG), warm-started at the alpha of
+    the last evaluation, and the variances f - k_*^T K^-1 k_* by batched solves, 8 new points at a time: n_new / 8 solves per call."""
+
+    MODEL = IterGPR
+
+    def __init__(self, model: IterGPR, max_error: float = 1e-3):
+        super().__init__(model)
+        self.max_error = float(max_error)
+
+    def mean_and_variance(self, xnew):
+        self.model.push_hypers(get_cholesky_jitter())
+        return self.model.hip.itergp_predict(xnew, self.max_error, self.model.max_cg_iter)
+
+
+class _PredictLogdensity:
+    """Mixed in before a predictor: `forward((x, y))` is the log density of y under that predictor's predictive at x, summed over the outputs."""
+
     def forward(self, data: Tuple[Tensor, Tensor], full_cov: bool = False, full_output_cov: bool = False):
         if full_cov or full_output_cov:
             raise NotImplementedError(
                 "The predict_log_density method currently supports only the argument values full_cov=False and full_output_cov=False")
         x, y = data
         f_mean, f_var = super().forward(x, full_cov=full_cov, full_output_cov=full_output_cov)
-        y = torch.as_tensor(y, dtype=f_mean.dtype, device=f_mean.device)
-        return gaussian(y, f_mean, f_var + self.noise.to(f_mean.device)).sum(axis=-1)
+        return log_density(self.model, y, f_mean, f_var)
+
+
+class PredictLogdensityCG(_PredictLogdensity, PredictCG):
+    pass
+
+
+class PredictLogdensityGPR(_PredictLogdensity, PredictGPR):
+    pass
+
+
+class PredictLogdensityIterGPR(_PredictLogdensity, PredictIterGPR):
+    pass
 
 
 def log_density(m, y, f_mean, f_var) -> Tensor:  # models.py:370-372
@@ -484,283 +733,3 @@ def gaussian(x, mu, var):  # models.py:375-379
     pi2 = math.log(2 * math.pi)
     x = x.reshape(*mu.shape)
     return -0.5 * (pi2 + torch.log(var) + (mu - x) ** 2 / var)
-
-
-class _SGPRBoundFunction(torch.autograd.Function):
-    """bound(lengthscales, variance, noise, mean, Z) of the SGPR family with the analytic gradient from the GPU (no v, no solve)."""
-
-    @staticmethod
-    def forward(ctx, model, ls, var, noise, mean, Z):
-        hip = model.hip
-        hip.set_hypers(ls.detach().cpu().numpy(), float(var), float(noise), float(mean), Z.detach().cpu(), get_cholesky_jitter())
-        res = hip.objective_and_grad(model._zero_v, False, with_grad=any(ctx.needs_input_grad[1:]))
-        model.last_bound = float(res.bound)
-        ctx.grads = res.grad
-        return torch.tensor(res.bound, dtype=torch.float64)
-
-    @staticmethod
-    def backward(ctx, gout):
-        g = ctx.grads
-        if g is None:
-            raise RuntimeError("gradient was not requested in forward")
-        gout = gout.to(torch.float64)
-        return (None, gout * torch.from_numpy(g["lengthscales"]), gout * g["variance"], gout * g["noise"], gout * g["mean"],
-                gout * torch.from_numpy(g["Z"]))
-
-
-class LowerBoundSGPR(nn.Module):
-    """`LowerBoundSGPR(model)(data)`: the collapsed bound of an SGPR / SGPRN2M model (tensorflow/models.py:353-413), the `elbo` of the TF
-    twin.  `data` must be None or the model's own training set, as for LowerBoundCG."""
-
-    def __init__(self, model: SGPR):
-        if not isinstance(model, SGPR) or isinstance(model, CGLB):
-            raise ValueError(f"SGPR model expected in the constructor of the {self.__class__}")
-        super().__init__()
-        object.__setattr__(self, "model", model)
-
-    def forward(self, data: Optional[Tuple[Tensor, Tensor]] = None) -> Tensor:
-        if data is not None:
-            self.model.check_same_data(data)
-        ls, var, noise, mean, Z = self.model.hyper_tensors()
-        return _SGPRBoundFunction.apply(self.model, ls, var, noise, mean, Z)
-
-
-class PredictSGPR(nn.Module):
-    """Titsias' predictive: PredictCG's formula (models.py:333-354) at v = 0, without a solve (cg_mean = 0, res = e)."""
-
-    def __init__(self, model: SGPR):
-        super().__init__()
-        object.__setattr__(self, "model", model)
-        self.cached = False
-
-    def forward(self, xnew: Tensor, full_cov: bool = False, full_output_cov: bool = False) -> Tuple[Tensor, Tensor]:
-        if full_cov:
-            raise NotImplementedError("The predict_f method currently  supports only `full_cov=False` option")
-        model, hip = self.model, self.model.hip
-        with torch.no_grad():
-            if not self.cached:
-                model.push_hypers(get_cholesky_jitter())
-                hip.setup()
-                self.cached = True
-            f_mean, f_var = hip.predict(model._zero_v, xnew)
-        return f_mean.reshape(-1, 1), f_var.reshape(-1, 1)
-
-
-class ExactGPR(GPR):
-    """Exact GP regression (GPRConfig: tensorflow/interface.py:200-206 builds gpflow's GPR with a constant mean; pytorch/interface.py:561-604
-    trains it on ExactMarginalLogLikelihood times n).  The module tree and parameter keys of the SGPR family without the inducing points:
-    `covar_module` is the ScaleKernel itself.  The N x N kernel matrix is factored on the GPU (cglb_gpr_*: fp64, one rank, one target column)."""
-
-    def __init__(self, data: Data, likelihood: GaussianLikelihood, kernel: ScaleKernel, dtype: torch.dtype = torch.float64,
-                 device: Optional[torch.device] = None, context=None):
-        super().__init__(data, likelihood, kernel)
-        self.dtype = dtype
-        if self.num_outputs > 1:
-            raise NotImplementedError("ExactGPR is not available for more than one target column (only CGLB takes [N, P] targets)")
-        if context is None:
-            import torch.distributed as dist
-            if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
-                raise NotImplementedError("ExactGPR is not available on more than one rank (only CGLB runs row-sharded); run it as a single process")
-            context = HipContext(self.train_inputs[0], self.train_targets, 1, kernel.base_kernel.kind, dtype=dtype, device=device)  # M = 1: placeholder
-        elif getattr(context, "world", 1) > 1:
-            raise NotImplementedError("ExactGPR is not available on more than one rank (only CGLB runs row-sharded)")
-        self.hip = context
-        self.push_hypers()   # an fp32 context is refused here, with the library's message, not at the first evaluation
-
-    check_same_data = SGPR.check_same_data
-
-    def hyper_tensors(self):
-        k = self.covar_module
-        return (k.base_kernel.lengthscale.reshape(-1), k.outputscale.reshape(()), self.likelihood.noise.reshape(()),
-                self.mean_module.constant.reshape(()))
-
-    def push_hypers(self):
-        ls, var, noise, mean = [t.detach() for t in self.hyper_tensors()]
-        self.hip.gpr_set_hypers(ls.cpu().numpy(), float(var), float(noise), float(mean))
-
-
-class _GPRFunction(torch.autograd.Function):
-    """lml(lengthscales, variance, noise, mean) of the exact model with the analytic gradient from the GPU."""
-
-    @staticmethod
-    def forward(ctx, model, ls, var, noise, mean):
-        hip = model.hip
-        hip.gpr_set_hypers(ls.detach().cpu().numpy(), float(var), float(noise), float(mean))
-        res = hip.gpr_objective_and_grad(with_grad=any(ctx.needs_input_grad[1:]))
-        model.last_bound = float(res.lml)
-        ctx.grads = res.grad
-        return torch.tensor(res.lml, dtype=torch.float64)
-
-    @staticmethod
-    def backward(ctx, gout):
-        g = ctx.grads
-        if g is None:
-            raise RuntimeError("gradient was not requested in forward")
-        gout = gout.to(torch.float64)
-        return (None, gout * torch.from_numpy(g["lengthscales"]), gout * g["variance"], gout * g["noise"], gout * g["mean"])
-
-
-class LogMarginalLikelihood(nn.Module):
-    """`LogMarginalLikelihood(model)(data)`: the exact log marginal likelihood of an ExactGPR model (gpflow GPR.log_marginal_likelihood).
-    `data` must be None or the model's own training set, as for LowerBoundCG."""
-
-    def __init__(self, model: ExactGPR):
-        if not isinstance(model, ExactGPR):
-            raise ValueError(f"ExactGPR model expected in the constructor of the {self.__class__}")
-        super().__init__()
-        object.__setattr__(self, "model", model)
-
-    def forward(self, data: Optional[Tuple[Tensor, Tensor]] = None) -> Tensor:
-        if data is not None:
-            self.model.check_same_data(data)
-        ls, var, noise, mean = self.model.hyper_tensors()
-        return _GPRFunction.apply(self.model, ls, var, noise, mean)
-
-
-class PredictGPR(nn.Module):
-    """predict_f of the exact model: mean c + K_*f K^-1 e, variance f - |L^-1 K_f*|^2.  The library keeps the factor of the last evaluation at
-    the current hyper-parameters and factors first if there is none."""
-
-    def __init__(self, model: ExactGPR):
-        if not isinstance(model, ExactGPR):
-            raise ValueError(f"ExactGPR model expected in the constructor of the {self.__class__}")
-        super().__init__()
-        object.__setattr__(self, "model", model)
-
-    def forward(self, xnew: Tensor, full_cov: bool = False, full_output_cov: bool = False) -> Tuple[Tensor, Tensor]:
-        if full_cov:
-            raise NotImplementedError("The predict_f method currently  supports only `full_cov=False` option")
-        with torch.no_grad():
-            self.model.push_hypers()
-            f_mean, f_var = self.model.hip.gpr_predict(xnew)
-        return f_mean.reshape(-1, 1), f_var.reshape(-1, 1)
-
-
-class PredictLogdensityGPR(PredictGPR):
-    def forward(self, data: Tuple[Tensor, Tensor], full_cov: bool = False, full_output_cov: bool = False):
-        if full_cov or full_output_cov:
-            raise NotImplementedError(
-                "The predict_log_density method currently supports only the argument values full_cov=False and full_output_cov=False")
-        x, y = data
-        f_mean, f_var = super().forward(x, full_cov=full_cov, full_output_cov=full_output_cov)
-        return log_density(self.model, y, f_mean, f_var)
-
-
-class IterGPR(GPR):
-    """Iterative exact GP regression: the "Iterative GP" baseline (pytorch/interface.py:233-260 builds it on gpytorch's ExactGP with a
-    pivoted-Cholesky preconditioner of rank `_prec_size()` = 100, batched CG and stochastic Lanczos quadrature).  The module tree and parameter
-    keys of ExactGPR; O(N) memory.  The estimator is the library's (cglb_itergp_*: fp64, one rank, one target column): `num_probes` probe
-    vectors drawn on the host from this model's generator, one batched solve warm-started at the persistent `v_vec`, the log-determinant from
-    the Lanczos coefficients of the solve.  gpytorch's random numbers and stop rule are not reproduced."""
-
-    def __init__(self, data: Data, likelihood: GaussianLikelihood, kernel: ScaleKernel, dtype: torch.dtype = torch.float64,
-                 device: Optional[torch.device] = None, context=None, num_probes: int = 10, prec_size: int = 100, max_error: float = 1.0,
-                 max_cg_iter: int = 1000, lanczos_iter: int = 20, seed: int = 0, deterministic_probes: bool = False):
-        super().__init__(data, likelihood, kernel)
-        self.dtype = dtype
-        if self.num_outputs > 1:
-            raise NotImplementedError("IterGPR is not available for more than one target column (only CGLB takes [N, P] targets)")
-        if dtype != torch.float64:
-            raise ValueError("the iterative exact GP class needs fp64 (-t fp64)")
-        n = int(self.train_inputs[0].shape[0])
-        self.num_probes, self.prec_size = int(num_probes), min(int(prec_size), n)
-        self.max_error, self.max_cg_iter, self.lanczos_iter = float(max_error), int(max_cg_iter), int(lanczos_iter)
-        if context is None:
-            import torch.distributed as dist
-            if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
-                raise NotImplementedError("IterGPR is not available on more than one rank (only CGLB runs row-sharded); run it as a single process")
-            context = HipContext(self.train_inputs[0], self.train_targets, self.prec_size, kernel.base_kernel.kind, dtype=dtype, device=device)
-        elif getattr(context, "world", 1) > 1:
-            raise NotImplementedError("IterGPR is not available on more than one rank (only CGLB runs row-sharded)")
-        self.hip = context
-        self.register_buffer("v_vec", torch.zeros(n, dtype=dtype, device=context.device), persistent=False)   # the warm start of the data column
-        self.generator = torch.Generator(device="cpu")
-        self.generator.manual_seed(int(seed))
-        self.deterministic_probes = bool(deterministic_probes)
-        self._eps = None
-        self.cg_stats: Optional[ConjugateGradientStats] = None
-        self._placeholder_Z = self.train_inputs[0][:self.prec_size].detach().cpu().to(torch.float64)   # replaced by the pivots at every evaluation
-        self._pushed = None
-
-    check_same_data = SGPR.check_same_data
-    hyper_tensors = ExactGPR.hyper_tensors
-
-    def probes(self) -> Tensor:
-        """[num_probes, prec_size + N] standard-normal draws: fresh at every call, or one draw kept when `deterministic_probes`."""
-        if self._eps is None or not self.deterministic_probes:
-            self._eps = torch.randn(self.num_probes, self.prec_size + self.hip.N, dtype=torch.float64, generator=self.generator)
-        return self._eps
-
-    def push_hypers(self, jitter: float):
-        """Hands the hyper-parameters to the library unless these very values are already there: a new set_hypers would make the library
-        forget the preconditioner and the alpha of its last evaluation, which the predictive solve starts from."""
-        ls, var, noise, mean = [t.detach() for t in self.hyper_tensors()]
-        key = (ls.cpu().numpy().tobytes(), float(var), float(noise), float(mean), float(jitter))
-        if key != self._pushed:
-            self.hip.set_hypers(ls.cpu().numpy(), float(var), float(noise), float(mean), self._placeholder_Z, jitter)
-            self._pushed = key
-
-
-class _IterGPRFunction(torch.autograd.Function):
-    """The stochastic estimate of lml(lengthscales, variance, noise, mean) with the library's unbiased gradient estimate: the backward is NOT
-    the derivative of the forward value (the log-determinant estimate and its gradient use the same probes in different estimators)."""
-
-    @staticmethod
-    def forward(ctx, model, ls, var, noise, mean):
-        hip = model.hip
-        model.push_hypers(get_cholesky_jitter())
-        res = hip.itergp_objective_and_grad(model.probes(), model.v_vec, model.max_error, model.max_cg_iter, model.lanczos_iter,
-                                            with_grad=any(ctx.needs_input_grad[1:]))
-        model.last_bound = float(res.lml)
-        model.cg_stats = ConjugateGradientStats(steps=res.steps, residual_error=res.residual_error)
-        ctx.grads = res.grad
-        return torch.tensor(res.lml, dtype=torch.float64)
-
-    backward = _GPRFunction.backward
-
-
-class StochasticLogMarginalLikelihood(nn.Module):
-    """`StochasticLogMarginalLikelihood(model)(data)`: the iterative estimate of the log marginal likelihood of an IterGPR model.  `data` must
-    be None or the model's own training set, as for LowerBoundCG."""
-
-    def __init__(self, model: IterGPR):
-        if not isinstance(model, IterGPR):
-            raise ValueError(f"IterGPR model expected in the constructor of the {self.__class__}")
-        super().__init__()
-        object.__setattr__(self, "model", model)
-
-    def forward(self, data: Optional[Tuple[Tensor, Tensor]] = None) -> Tensor:
-        if data is not None:
-            self.model.check_same_data(data)
-        ls, var, noise, mean = self.model.hyper_tensors()
-        return _IterGPRFunction.apply(self.model, ls, var, noise, mean)
-
-
-class PredictIterGPR(nn.Module):
-    """predict_f of the iterative model: mean c + K_*f alpha from one solve at `max_error` (1e-3 like PredictCG), warm-started at the alpha of
-    the last evaluation, and the variances f - k_*^T K^-1 k_* by batched solves, 8 new points at a time: n_new / 8 solves per call."""
-
-    def __init__(self, model: IterGPR, max_error: float = 1e-3):
-        if not isinstance(model, IterGPR):
-            raise ValueError(f"IterGPR model expected in the constructor of the {self.__class__}")
-        super().__init__()
-        object.__setattr__(self, "model", model)
-        self.max_error = float(max_error)
-
-    def forward(self, xnew: Tensor, full_cov: bool = False, full_output_cov: bool = False) -> Tuple[Tensor, Tensor]:
-        if full_cov:
-            raise NotImplementedError("The predict_f method currently  supports only `full_cov=False` option")
-        with torch.no_grad():
-            self.model.push_hypers(get_cholesky_jitter())
-            f_mean, f_var = self.model.hip.itergp_predict(xnew, self.max_error, self.model.max_cg_iter)
-        return f_mean.reshape(-1, 1), f_var.reshape(-1, 1)
-
-
-class PredictLogdensityIterGPR(PredictIterGPR):
-    def forward(self, data: Tuple[Tensor, Tensor], full_cov: bool = False, full_output_cov: bool = False):
-        if full_cov or full_output_cov:
-            raise NotImplementedError(
-                "The predict_log_density method currently supports only the argument values full_cov=False and full_output_cov=False")
-        x, y = data
-        f_mean, f_var = super().forward(x, full_cov=full_cov, full_output_cov=full_output_cov)
-        return log_density(self.model, y, f_mean, f_var)

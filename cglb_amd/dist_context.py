@@ -22,7 +22,7 @@ import torch
 
 from . import _lib
 from .distributed import Comm, row_partition
-from .hip_context import HipContext, ObjectiveResult, _ptr, _wrap_device_pointer, grad_len
+from .hip_context import HipContext, ObjectiveResult, _ptr, _wrap_device_pointer, check_v_inout, grad_len
 
 try:
     import torch.distributed as dist
@@ -139,8 +139,7 @@ class DistHipContext(HipContext):
 
     def objective_and_grad(self, v_inout: torch.Tensor, run_cg=True, max_error=1.0, max_cg_iter=100, restart_cg_iter=40,
                            with_grad=True) -> ObjectiveResult:
-        if v_inout.device != self.device or v_inout.dtype != self.dtype or v_inout.numel() != self.N or not v_inout.is_contiguous():
-            raise ValueError("v_inout must be a contiguous device vector of length N in the context dtype")
+        check_v_inout(v_inout, self)
         out4 = (c_double * 4)()
         g = np.empty(grad_len(self.D, self.M), dtype=np.float64) if with_grad else None
         steps, half = c_int(), c_double()
@@ -153,7 +152,7 @@ class DistHipContext(HipContext):
         raise NotImplementedError("joint optimisation of v (the TF twin's opt-in) is not available on more than one rank")
 
     def predict(self, v_full, xnew):
-        xn = torch.as_tensor(xnew, dtype=self.dtype).reshape(-1, self.D).contiguous().to(self.device)
+        xn = self._xnew(xnew)
         v = self._dev(v_full, self.N)
         mean, var = self.empty(xn.shape[0]), self.empty(xn.shape[0])
         self._check(self.lib.cglb_dist_predict(self._ctx, _ptr(v), _ptr(xn), xn.shape[0], _ptr(mean), _ptr(var)))

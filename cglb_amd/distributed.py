@@ -303,7 +303,7 @@ class HipSymLocalOps(HipLocalOps, SymLocalOps):
     def predict_u(self, Kv_local, u_out): self._ck(self.lib.cglb_shard_predict_u(self.h, self._p(Kv_local), self._p(u_out)))
 
     def predict_rows(self, v_full, u, xnew):
-        xn = torch.as_tensor(xnew, dtype=self.dtype).reshape(-1, self.D).contiguous().to(self.device)
+        xn = self.ctx._xnew(xnew)
         n = int(xn.shape[0])
         mean, var = torch.empty(max(n, 1), dtype=self.dtype, device=self.device), torch.empty(max(n, 1), dtype=self.dtype, device=self.device)
         self._ck(self.lib.cglb_shard_predict_rows(self.h, self._p(v_full), self._p(u), self._p(xn) if n else None, n, self._p(mean), self._p(var)))
@@ -566,18 +566,14 @@ class PyDistContext:
         return self.drv.v.clone(), steps, half
 
     def objective_and_grad(self, v_inout, run_cg=True, max_error=1.0, max_cg_iter=100, restart_cg_iter=40, with_grad=True):
-        from .hip_context import ObjectiveResult
+        from .hip_context import ObjectiveResult, unpack_grad
         if v_inout.numel() != self.N:
             raise ValueError("v_inout must be a vector of length N")
         self.drv.v.copy_(v_inout.reshape(-1))
         res = self.drv.objective_and_grad(run_cg, max_error, max_cg_iter, restart_cg_iter, with_grad)
         if run_cg:
             v_inout.reshape(-1).copy_(self.drv.v)
-        grad = None
-        if res.grad is not None:
-            D, M, g = self.D, self.M, res.grad
-            grad = {"lengthscales": g[:D].copy(), "variance": float(g[D]), "noise": float(g[D + 1]), "mean": float(g[D + 2]),
-                    "Z": g[D + 3:].reshape(M, D).copy()}
+        grad = None if res.grad is None else unpack_grad(res.grad, self.D, self.M)
         return ObjectiveResult(res.bound, res.lower, res.upper, res.logdet, res.steps, res.residual_error, grad)
 
     def objective_grad_v(self):

@@ -56,6 +56,20 @@ def _ptr(t: Optional[torch.Tensor]):
     return None if t is None else c_void_p(t.data_ptr())
 
 
+def unpack_grad(g: np.ndarray, D: int, M: int = 0) -> dict:
+    """The dict of a packed constrained-space gradient [lengthscales (D), variance, noise, mean, Z (M * D)]; no "Z" entry for M = 0."""
+    grad = {"lengthscales": g[:D].copy(), "variance": float(g[D]), "noise": float(g[D + 1]), "mean": float(g[D + 2])}
+    if M:
+        grad["Z"] = g[D + 3:].reshape(M, D).copy()
+    return grad
+
+
+def check_v_inout(v_inout: torch.Tensor, ctx):
+    """ValueError unless v_inout is what the library reads and writes in place: a contiguous device vector of length N in the context dtype."""
+    if v_inout.device != ctx.device or v_inout.dtype != ctx.dtype or v_inout.numel() != ctx.N or not v_inout.is_contiguous():
+        raise ValueError("v_inout must be a contiguous device vector of length N in the context dtype")
+
+
 class HipContext:
     def __init__(self, X, y, num_inducing: int, kind, dtype: torch.dtype = torch.float64, device: Optional[torch.device] = None,
                  row_range: Optional[Tuple[int, int]] = None):
@@ -113,12 +127,18 @@ class HipContext:
     def empty(self, n) -> torch.Tensor:
         return torch.empty(n, dtype=self.dtype, device=self.device)
 
+    def _xnew(self, xnew) -> torch.Tensor:
+        return torch.as_tensor(xnew, dtype=self.dtype).reshape(-1, self.D).contiguous().to(self.device)
+
+    def _ls(self, lengthscales) -> np.ndarray:
+        return np.ascontiguousarray(np.broadcast_to(np.asarray(lengthscales, dtype=np.float64).reshape(-1), (self.D,)))
+
     def set_option(self, name: str, value: int):
         _lib.check(self.lib.cglb_set_option(self._ctx, name.encode(), int(value)), self._ctx)
 
     # -- hypers / common terms -----------------------------------------------------------------------
     def set_hypers(self, lengthscales, variance, noise, mean, Z, jitter=1e-6):
-        ls = np.ascontiguousarray(np.broadcast_to(np.asarray(lengthscales, dtype=np.float64).reshape(-1), (self.D,)))
+        ls = self._ls(lengthscales)
         Zd = torch.as_tensor(Z, dtype=self.dtype).reshape(self.M, self.D).contiguous().to(self.device)
         rc = self.lib.cglb_set_hypers(self._ctx, ls.ctypes.data_as(ctypes.POINTER(c_double)), float(variance), float(noise),
                                       float(mean), _ptr(Zd), float(jitter))
@@ -160,7 +180,7 @@ class HipContext:
         return out
 
     def cross_matvec(self, xnew, v_full) -> torch.Tensor:
-        xn = torch.as_tensor(xnew, dtype=self.dtype).reshape(-1, self.D).contiguous().to(self.device)
+        xn = self._xnew(xnew)
         v = self._dev(v_full, self.N)
         out = self.empty(xn.shape[0])
         _lib.check(self.lib.cglb_cross_matvec(self._ctx, _ptr(xn), xn.shape[0], _ptr(v), _ptr(out)), self._ctx)
@@ -219,7 +239,7 @@ class HipContext:
 
     def predict_multi(self, V, xnew) -> Tuple[torch.Tensor, torch.Tensor]:
         """f_mean [n_new, P] for the P target columns and the shared f_var [n_new] (cglb_predict_multi)."""
-        xn = torch.as_tensor(xnew, dtype=self.dtype).reshape(-1, self.D).contiguous().to(self.device)
+        xn = self._xnew(xnew)
         Vt = self._cols(V, self.P)
         mean = torch.empty((self.P, xn.shape[0]), dtype=self.dtype, device=self.device)
         var = self.empty(xn.shape[0])
@@ -241,8 +261,7 @@ class HipContext:
                 raise ValueError("v_inout must be a device tensor of shape [N, P] in the context dtype")
             v, entry = v_inout.t().contiguous(), self.lib.cglb_objective_and_grad_multi  # the library's layout: column b contiguous
         else:
-            if v_inout.numel() != self.N or not v_inout.is_contiguous():
-                raise ValueError("v_inout must be a contiguous device vector of length N in the context dtype")
+            check_v_inout(v_inout, self)
             v, entry = v_inout, self.lib.cglb_objective_and_grad
         out4 = (c_double * 4)()
         g = np.empty(grad_len(self.D, self.M), dtype=np.float64) if with_grad else None
@@ -261,15 +280,13 @@ class HipContext:
         return out
 
     def unpack_grad(self, g: np.ndarray) -> dict:
-        D, M = self.D, self.M
-        return {"lengthscales": g[:D].copy(), "variance": float(g[D]), "noise": float(g[D + 1]), "mean": float(g[D + 2]),
-                "Z": g[D + 3:].reshape(M, D).copy()}
+        return unpack_grad(g, self.D, self.M)
 
     def select_inducing(self, lengthscales, variance, jitter=1e-12, return_Z=False):
         """Greedy conditional-variance choice of the M inducing points under the given (initial) kernel - config.py:55-65.
         Returns (indices int64 [min(M, N)], remaining trace) and, if asked, the device tensor Z = X[indices].
         Must be followed by set_hypers before any other call."""
-        ls = np.ascontiguousarray(np.broadcast_to(np.asarray(lengthscales, dtype=np.float64).reshape(-1), (self.D,)))
+        ls = self._ls(lengthscales)
         msel = min(self.M, self.N)
         idx = np.empty(msel, dtype=np.int64)
         Z = torch.empty((msel, self.D), dtype=self.dtype, device=self.device) if return_Z else None
@@ -280,7 +297,7 @@ class HipContext:
         return (idx, trace.value, Z) if return_Z else (idx, trace.value)
 
     def predict(self, v_full, xnew) -> Tuple[torch.Tensor, torch.Tensor]:
-        xn = torch.as_tensor(xnew, dtype=self.dtype).reshape(-1, self.D).contiguous().to(self.device)
+        xn = self._xnew(xnew)
         v = self._dev(v_full, self.N)
         mean, var = self.empty(xn.shape[0]), self.empty(xn.shape[0])
         _lib.check(self.lib.cglb_predict(self._ctx, _ptr(v), _ptr(xn), xn.shape[0], _ptr(mean), _ptr(var)), self._ctx)
@@ -288,7 +305,7 @@ class HipContext:
 
     # -- exact GPR (cglb_gpr_*): dense Cholesky marginal likelihood, fp64, one rank, one target column; num_inducing is a placeholder ----
     def gpr_set_hypers(self, lengthscales, variance, noise, mean):
-        ls = np.ascontiguousarray(np.broadcast_to(np.asarray(lengthscales, dtype=np.float64).reshape(-1), (self.D,)))
+        ls = self._ls(lengthscales)
         rc = self.lib.cglb_gpr_set_hypers(self._ctx, ls.ctypes.data_as(ctypes.POINTER(c_double)), float(variance), float(noise), float(mean))
         _lib.check(rc, self._ctx)
 
@@ -297,13 +314,11 @@ class HipContext:
         g = np.empty(self.D + 3, dtype=np.float64) if with_grad else None
         rc = self.lib.cglb_gpr_objective_and_grad(self._ctx, out3, g.ctypes.data_as(ctypes.POINTER(c_double)) if with_grad else None)
         _lib.check(rc, self._ctx)
-        D = self.D
-        grad = None if g is None else {"lengthscales": g[:D].copy(), "variance": float(g[D]), "noise": float(g[D + 1]), "mean": float(g[D + 2])}
-        return GPRResult(out3[0], out3[1], out3[2], grad)
+        return GPRResult(out3[0], out3[1], out3[2], None if g is None else unpack_grad(g, self.D))
 
     def gpr_predict(self, xnew) -> Tuple[torch.Tensor, torch.Tensor]:
         """predict_f mean and variance at xnew [n_new, D] from the factor of the last evaluation (factored first if there is none)."""
-        xn = torch.as_tensor(xnew, dtype=self.dtype).reshape(-1, self.D).contiguous().to(self.device)
+        xn = self._xnew(xnew)
         mean, var = self.empty(xn.shape[0]), self.empty(xn.shape[0])
         _lib.check(self.lib.cglb_gpr_predict(self._ctx, _ptr(xn), xn.shape[0], _ptr(mean), _ptr(var)), self._ctx)
         return mean, var
@@ -313,8 +328,7 @@ class HipContext:
     def itergp_objective_and_grad(self, eps, v_inout: torch.Tensor, max_error=1.0, max_cg_iter=1000, lanczos_iter=20, with_grad=True) -> IterGPResult:
         """eps [t, M + N]: the probes' standard-normal draws (the library draws none).  v_inout (device, length N) is the persistent warm start of
         the data column, updated in place."""
-        if v_inout.device != self.device or v_inout.dtype != self.dtype or v_inout.numel() != self.N or not v_inout.is_contiguous():
-            raise ValueError("v_inout must be a contiguous device vector of length N in the context dtype")
+        check_v_inout(v_inout, self)
         e = torch.as_tensor(eps, dtype=torch.float64).reshape(-1, self.M + self.N).contiguous().to(self.device)
         out4 = (c_double * 4)()
         g = np.empty(self.D + 3, dtype=np.float64) if with_grad else None
@@ -324,9 +338,7 @@ class HipContext:
                                                      byref(steps), byref(half))
         _lib.check(rc, self._ctx)
         self._itergp_shape = (steps.value, 1 + int(e.shape[0]))
-        D = self.D
-        grad = None if g is None else {"lengthscales": g[:D].copy(), "variance": float(g[D]), "noise": float(g[D + 1]), "mean": float(g[D + 2])}
-        return IterGPResult(out4[0], out4[1], out4[2], out4[3], steps.value, half.value, grad)
+        return IterGPResult(out4[0], out4[1], out4[2], out4[3], steps.value, half.value, None if g is None else unpack_grad(g, self.D))
 
     def itergp_coefficients(self) -> Tuple[np.ndarray, np.ndarray]:
         """(rz [steps + 1, 1 + t], pAp [steps, 1 + t]) of the last itergp_objective_and_grad."""
@@ -338,7 +350,7 @@ class HipContext:
 
     def itergp_predict(self, xnew, max_error=1e-3, max_cg_iter=1000) -> Tuple[torch.Tensor, torch.Tensor]:
         """predict_f mean and variance at xnew [n_new, D]: one solve for alpha and n_new / 8 batched solves for the variances."""
-        xn = torch.as_tensor(xnew, dtype=self.dtype).reshape(-1, self.D).contiguous().to(self.device)
+        xn = self._xnew(xnew)
         mean, var = self.empty(xn.shape[0]), self.empty(xn.shape[0])
         rc = self.lib.cglb_itergp_predict(self._ctx, _ptr(xn), xn.shape[0], float(max_error), int(max_cg_iter), _ptr(mean), _ptr(var))
         _lib.check(rc, self._ctx)

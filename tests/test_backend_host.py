@@ -74,6 +74,24 @@ def test_constraints_match_gpytorch_conventions():
     assert float(k.outputscale) == pytest.approx(0.3, rel=1e-12)
 
 
+def test_a_saved_value_is_set_back_bit_for_bit():
+    """`load` hands the values `save` wrote to the constrained parameters with `exact`: value = softplus(raw) + lower_bound comes back bit for
+    bit for any raw, where the plain inverse is only good to a unit in the last place; without `exact` the setter is the plain inverse."""
+    from cglb_amd.backend.models import _Constrained, _inv_softplus
+    gen = torch.Generator().manual_seed(3)
+    for lower_bound in (0.0, 1e-6, 1e-4):           # lengthscales and variance; the noise of the sparse and exact classes; of itergp
+        for scale in (1.5, 6.0):
+            trained = _Constrained((500,), lower_bound)
+            with torch.no_grad():
+                trained.raw.copy_(scale * torch.randn(500, dtype=torch.float64, generator=gen))
+            saved = trained.value.detach().numpy().copy()
+            loaded = _Constrained((500,), lower_bound)
+            loaded.set(saved, exact=True)
+            assert np.array_equal(loaded.value.detach().numpy(), saved)
+            loaded.set(saved)
+            assert torch.equal(loaded.raw.detach(), _inv_softplus(torch.as_tensor(saved) - lower_bound))
+
+
 def test_logger_keys_and_stopwatch():
     calls = []
     lg = Logger("/tmp/x", lambda: {"loss": 1.5, "cg/steps": 3, "junk": 0, "train/rmse": 0.1}, lambda: {".kernel.variance": 1.0, ".inducing_point": 2},
@@ -183,23 +201,23 @@ def test_json_artefacts_use_the_json_tricks_ndarray_encoding(tmp_path):
     assert isinstance(back["cg/steps"][0], np.ndarray) and back["cg/steps"][0].shape == ()
 
 
-def test_optimize_schedule_four_rounds_without_inducing_points_in_the_last_two(monkeypatch, tmp_path):
-    """pytorch/interface.py:445-543 on the host, with the solver and SciPy replaced by recorders: a warm-up evaluation outside the
-    recording, then up to four `minimize` rounds, each with maxiter = the steps still left, the third and fourth without the
-    inducing points in the variable list (:527-529), the step callback clearing the cache flag and feeding the logger (:479-481)."""
-    from types import SimpleNamespace
-    from cglb_amd.backend import interface
-    from cglb_amd.backend.callbacks import Logger
-    from cglb_amd.backend.conjugate_gradient import ConjugateGradientStats
+class _ScheduleModel(torch.nn.Module):
+    """Stand-in for a model class in the optimiser tests: three parameters, one of them the inducing points unless `inducing` is False."""
 
-    class Model(torch.nn.Module):
-        def __init__(self):
-            super().__init__()
-            self.noise = torch.nn.Parameter(torch.zeros(1, dtype=torch.float64))
-            self.covar_module = torch.nn.Module()
+    def __init__(self, inducing: bool = True):
+        from cglb_amd.backend.conjugate_gradient import ConjugateGradientStats
+        super().__init__()
+        self.noise = torch.nn.Parameter(torch.zeros(1, dtype=torch.float64))
+        self.covar_module = torch.nn.Module()
+        if inducing:
             self.covar_module.inducing_points = torch.nn.Parameter(torch.zeros(4, 2, dtype=torch.float64))
-            self.ls = torch.nn.Parameter(torch.zeros(2, dtype=torch.float64))
-            self.cg_stats = ConjugateGradientStats(3, 0.5)
+        self.ls = torch.nn.Parameter(torch.zeros(2, dtype=torch.float64))
+        self.cg_stats = ConjugateGradientStats(3, 0.5)
+
+
+def _schedule_recorders():
+    """(FakeBound, FakeScipy, rounds): an objective that counts its calls and a `Scipy` that records every `minimize` round."""
+    from types import SimpleNamespace
 
     class FakeBound:
         instances = []
@@ -225,25 +243,71 @@ def test_optimize_schedule_four_rounds_without_inducing_points_in_the_last_two(m
                 step_callback(k, variables, [v.detach() for v in variables])
             return SimpleNamespace(nit=nit, nfev=nit, fun=0.0, status=0)
 
-    monkeypatch.setattr(interface, "LowerBoundCG", FakeBound)
+    return FakeBound, FakeScipy, rounds
+
+
+@pytest.mark.parametrize("entry, objective, inducing", [("_optimize_cglb", "LowerBoundCG", True), ("_optimize_sgpr", "LowerBoundSGPR", True),
+                                                        ("_optimize_gpr", "LogMarginalLikelihood", False)], ids=["cglb", "sgpr", "gpr"])
+def test_optimize_schedule_four_rounds_without_inducing_points_in_the_last_two(entry, objective, inducing, monkeypatch, tmp_path):
+    """pytorch/interface.py:445-543 on the host, with the solver and SciPy replaced by recorders: a warm-up evaluation outside the
+    recording, then up to four `minimize` rounds, each with maxiter = the steps still left, the third and fourth without the
+    inducing points in the variable list (:527-529), the step callback clearing the cache flag and feeding the logger (:479-481).
+    The three L-BFGS-B entries run the same schedule; only cglb logs per evaluation and touches the cache flag, and gpr has no
+    inducing points to leave out."""
+    from cglb_amd.backend import interface
+    from cglb_amd.backend.callbacks import Logger
+
+    FakeBound, FakeScipy, rounds = _schedule_recorders()
+    monkeypatch.setattr(interface, objective, FakeBound)
     monkeypatch.setattr(interface, "Scipy", FakeScipy)
-    model = Model()
+    monkeypatch.setattr(torch.cuda, "synchronize", lambda *a, **k: None)
+    optimize = getattr(interface, entry)
+    model = _ScheduleModel(inducing)
     logger = Logger(str(tmp_path), lambda: {"loss": 1.0}, lambda: {}, holdout_interval=1, include_feval_log=True, verbose=False)
-    results = interface._optimize_cglb(model, None, 20, logger, "scipy")
-    ips = id(model.covar_module.inducing_points)
+    results = optimize(model, None, 20, logger, "scipy")
     assert [r.nit for r in results] == [3, 2, 4, 11]                      # never more than four rounds; the last takes what is left
     assert [r["maxiter"] for r in rounds] == [20, 17, 15, 11]
     assert all(r["ftol"] == 0.0 and r["gtol"] == 0.0 for r in rounds)
-    assert ips in rounds[0]["ids"] and ips in rounds[1]["ids"] and ips not in rounds[2]["ids"] and ips not in rounds[3]["ids"]
-    assert len(rounds[2]["ids"]) == len(rounds[0]["ids"]) - 1
+    if inducing:
+        ips = id(model.covar_module.inducing_points)
+        assert ips in rounds[0]["ids"] and ips in rounds[1]["ids"] and ips not in rounds[2]["ids"] and ips not in rounds[3]["ids"]
+        assert len(rounds[2]["ids"]) == len(rounds[0]["ids"]) - 1
+    else:
+        assert all(r["ids"] == [id(p) for p in model.parameters()] for r in rounds)
     bound = FakeBound.instances[-1]
-    assert bound.calls == 1 + 20 and bound.cached_v_vec is False            # warm-up + one per closure call; flag reset by the callback
-    assert len(logger.logs["steps-per-feval"]) == 20                        # the warm-up evaluation is not recorded (:494-501)
+    assert bound.calls == 1 + 20                                            # warm-up + one per closure call
+    if entry == "_optimize_cglb":
+        assert bound.cached_v_vec is False                                  # flag reset by the callback
+        assert len(logger.logs["steps-per-feval"]) == 20                    # the warm-up evaluation is not recorded (:494-501)
+    else:
+        assert bound.cached_v_vec is True and not logger.logs.get("steps-per-feval")   # no v bookkeeping, nothing logged per evaluation
     assert len(logger.logs["loss"]) == 20                                   # holdout_interval = 1: metrics at every accepted step
     # the schedule stops as soon as the budget is used up
     FakeScipy.nits = iter([20])
     rounds.clear()
-    assert [r.nit for r in interface._optimize_cglb(Model(), None, 20, logger, "scipy")] == [20] and len(rounds) == 1
+    assert [r.nit for r in optimize(_ScheduleModel(inducing), None, 20, logger, "scipy")] == [20] and len(rounds) == 1
+
+
+def test_optimize_itergp_runs_adam_steps_after_one_warm_up_and_refuses_scipy(monkeypatch, tmp_path):
+    """The iterative class keeps its Adam loop: one warm-up evaluation outside the recording, then one evaluation, one per-evaluation
+    log entry and one logger step per Adam step; the losses come back as floats.  L-BFGS-B is refused with its own message."""
+    from cglb_amd.backend import interface
+    from cglb_amd.backend.callbacks import Logger
+
+    FakeBound, _FakeScipy, _rounds = _schedule_recorders()
+    monkeypatch.setattr(interface, "StochasticLogMarginalLikelihood", FakeBound)
+    monkeypatch.setattr(torch.cuda, "synchronize", lambda *a, **k: None)
+    model = _ScheduleModel(inducing=False)
+    logger = Logger(str(tmp_path), lambda: {"loss": 1.0}, lambda: {}, holdout_interval=1, include_feval_log=True, verbose=False)
+    losses = interface._optimize_itergp(model, None, 4, logger, "adam_0.5")
+    assert len(losses) == 4 and all(type(v) is float for v in losses)
+    assert FakeBound.instances[-1].calls == 1 + 4
+    assert logger.logs["steps-per-feval"] == [3] * 4 and logger.logs["residual_error-per-feval"] == [0.5] * 4
+    assert len(logger.logs["loss"]) == 4
+    with pytest.raises(ValueError) as err:
+        interface._optimize_itergp(model, None, 4, logger, "scipy")
+    assert str(err.value) == ("model class 'itergp' cannot be trained with -o scipy: its gradient is a stochastic estimate and not the derivative of "
+                              "the returned value, which the L-BFGS-B line search assumes; use -o adam_<lr>, e.g. adam_0.1")
 
 
 def test_optimize_narrows_and_restores_the_host_thread_pools(monkeypatch):
