@@ -1700,7 +1700,7 @@ static int predict_rows(cglb_ctx* c, const void* v_full, const void* u, const vo
             hipLaunchKernelGGL((scale2_kernel<T>), dim3(grid1d(M)), dim3(256), 0, c->stream, (const T*)c->w_u, (int64_t)M, inv_sigma, (T*)c->w_u, (T)0, (T*)nullptr);
             // tmp1 = L^-1 Kus (:344), tmp2 = LB^-1 tmp1 (:345); panels stored [M][ld] row-major == (ld x M) column-major
             if (is_wide(c)) {
-                CGLB_TRY(wide_kus(c, xs, xa, n_new, ld, t1));
+                CGLB_TRY(wide_kus(c, xs, n_new, ld, t1));
             } else {
                 dim3 grid((unsigned)((n_new + 255) / 256), (unsigned)((M + 31) / 32));
                 CGLB_DISPATCH_KIND(c->kind, CGLB_DISPATCH_DP(c->Dp, hipLaunchKernelGGL((kus_kernel<T, KIND, DP>), grid, dim3(256), 0, c->stream, (const T*)c->Zs,

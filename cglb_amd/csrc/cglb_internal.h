@@ -310,7 +310,7 @@ int wide_after_hypers(cglb_ctx* c);
 int wide_prep_hot(cglb_ctx* c);   // Xh (N x Dh, zero padded), xah in hot units for the register-resident mat-vec of a mid-width context
 int wide_kuf(cglb_ctx* c);
 int wide_kuu(cglb_ctx* c);
-int wide_kus(cglb_ctx* c, const void* XsNew, const void* xaNew, int64_t n_new, int64_t ld, void* out);
+int wide_kus(cglb_ctx* c, const void* XsNew, int64_t n_new, int64_t ld, void* out);
 int wide_matvec(cglb_ctx* c, const void* XsRow, const void* xaRow, int64_t row0_global, int64_t nrows, const void* p_full, void* out, bool diag_noise,
                 double* pdot_slot, int tile_stride, int tile_offset);
 int wide_grad_kff(cglb_ctx* c, const void* v_full, const void* u_rows, int64_t row0, int64_t nrows, int tile_stride, int tile_offset, double* out_dl);

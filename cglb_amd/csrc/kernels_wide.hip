@@ -441,13 +441,33 @@ int wide_kuu(cglb_ctx* c) {
     return CGLB_OK;
 }
 
+// K_us panel by direct differences, like kus_kernel of the narrow inputs (cglb_api.hip): one wave per new point, lanes along d, 32 inducing
+// points per block row.  The Gram form a_n + a_m - 2 g leaves a few ulp of a_n + a_m where a new point coincides with an inducing point,
+// and f + |tmp2|^2 - |tmp1|^2 cancels there down to the jitter: in fp32 that error alone reached the round-off scale of the variance
+// (tests/test_gpu_predict_geometry.py, D = 40, M = 33).  M n_new D work, off the N^2 and N M paths.
+template <typename T, int KIND>
+__global__ __launch_bounds__(256) void wide_kus_kernel(const T* __restrict__ Zs, const T* __restrict__ XsNew, int64_t n_new, int64_t ld, int M, int D, T var,
+                                                       T* __restrict__ out) {
+    const int64_t n = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    if (n >= n_new) return;
+    const int m0 = blockIdx.y * 32, m1 = min(M, m0 + 32);
+    for (int m = m0; m < m1; ++m) {
+        T s = 0;
+        for (int d = lane; d < D; d += 64) {
+            const T df = Zs[(int64_t)m * D + d] - XsNew[n * D + d];
+            s = tfma<T>(df, df, s);
+        }
+        const double d2 = wave_sum((double)s);
+        if (lane == 0) out[(int64_t)m * ld + n] = var * kappa_from_d2<T, KIND>((T)d2);
+    }
+}
+
 // out[m * ld + n] = var * K(z_m, xnew_n)   (models.py:337)
-int wide_kus(cglb_ctx* c, const void* XsNew, const void* xaNew, int64_t n_new, int64_t ld, void* out) {
-    CGLB_DISPATCH_T(c->dtype, CGLB_DISPATCH_KIND(c->kind, {
-        CGLB_TRY(gram_tile<T>(c, (const T*)XsNew, n_new, (const T*)c->Zs, c->M, (T*)out, ld));
-        hipLaunchKernelGGL((wide_profile_kernel<T, KIND, 0>), dim3((unsigned)((n_new + 255) / 256), (unsigned)c->M), dim3(256), 0, c->stream, (T*)out, ld, n_new,
-                           (int64_t)c->M, (const T*)xaNew, (const T*)c->za, (T)c->var, (T)0);
-    }));
+int wide_kus(cglb_ctx* c, const void* XsNew, int64_t n_new, int64_t ld, void* out) {
+    const dim3 grid((unsigned)((n_new + 3) / 4), (unsigned)((c->M + 31) / 32));
+    CGLB_DISPATCH_T(c->dtype, CGLB_DISPATCH_KIND(c->kind, hipLaunchKernelGGL((wide_kus_kernel<T, KIND>), grid, dim3(256), 0, c->stream, (const T*)c->Zs,
+                                                                             (const T*)XsNew, n_new, ld, c->M, c->D, (T)c->var, (T*)out)));
     CGLB_LAUNCH_CHECK(c);
     return CGLB_OK;
 }
