@@ -18,7 +18,7 @@ COMM_ID_BYTES = 128
 #: collective callbacks of cglb_comm_init_callbacks: (user, buf, count, dtype, stream) -> 0 on success
 ALLREDUCE_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_void_p)
 ALLGATHER_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_void_p)
-RBF, MATERN32 = 0, 1
+RBF, MATERN32, MATERN52 = 0, 1, 2
 F64, F32 = 0, 1
 
 # CGLB_HIP_LIB lets a developer point at an experimental build of the same ABI (tools/ only; there is still no CPU fallback)

@@ -18,9 +18,9 @@ from typing import Callable, Dict, Tuple, Union
 import numpy as np
 
 __all__ = [
-    "Config", "ModelConfig", "KernelConfig", "SquaredExponentialConfig", "Matern32Config", "CGLBConfig", "CGLBN2MConfig",
+    "Config", "ModelConfig", "KernelConfig", "SquaredExponentialConfig", "Matern32Config", "Matern52Config", "CGLBConfig", "CGLBN2MConfig",
     "CGLBNM2Config", "SGPRN2MConfig", "GPRConfig", "ExactGPConfig", "IterGPRConfig", "SGPRConfig", "InducingVariableConfig", "GPR_CONFIGS", "SGPR_CONFIGS",
-    "KERNEL_CONFIGS", "INDUCING_VARIABLE_CONFIGS",
+    "KERNEL_CONFIGS", "EXTRA_KERNEL_CONFIGS", "INDUCING_VARIABLE_CONFIGS",
 ]
 
 Data = Tuple[np.ndarray, np.ndarray]
@@ -56,6 +56,9 @@ def _unit_kernel_params(self, data: Data):
 SquaredExponentialConfig = _record("SquaredExponentialConfig", (KernelConfig,), namespace={"params": _unit_kernel_params},
                                    doc="ARD squared-exponential (RBF) kernel.")
 Matern32Config = _record("Matern32Config", (SquaredExponentialConfig,), doc="ARD Matern-3/2 kernel (same initial values).")
+# based on the SE config directly: a subclass of Matern32Config would be claimed by the isinstance(cfg, Matern32Config) dispatch of interface.py
+Matern52Config = _record("Matern52Config", (SquaredExponentialConfig,),
+                         doc="ARD Matern-5/2 kernel, k = f (1 + s + s^2/3) exp(-s), s = sqrt(5) r (same initial values; not in the reference).")
 
 
 def _inducing_init(self, data: Data, kernel_fn: Callable):
@@ -114,4 +117,6 @@ GPR_CONFIGS = dict(gpr=GPRConfig, exactgp=ExactGPConfig, itergp=IterGPRConfig)
 SGPR_CONFIGS = dict(sgpr=SGPRConfig, cglb=CGLBConfig, sgprn2m=SGPRN2MConfig, cglbn2m=CGLBN2MConfig, cglbnm2=CGLBNM2Config)
 KERNEL_CONFIGS = {"SquaredExponential": SquaredExponentialConfig, "Matern32": Matern32Config, "mat32": Matern32Config,
                   "rbf": SquaredExponentialConfig}
+EXTRA_KERNEL_CONFIGS = {"Matern52": Matern52Config, "mat52": Matern52Config}
+"""Kernel choices beyond the reference's registry (which KERNEL_CONFIGS mirrors key for key); the command line offers both."""
 INDUCING_VARIABLE_CONFIGS = {key: InducingVariableConfig for key in ("InducingVariable", "ConditionalVariance", "iv", "cv")}

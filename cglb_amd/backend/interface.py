@@ -19,7 +19,7 @@ import torch
 
 from . import jsonio, metric
 from .callbacks import Logger
-from .config import (CGLBConfig, CGLBN2MConfig, CGLBNM2Config, ExactGPConfig, GPRConfig, IterGPRConfig, KernelConfig, Matern32Config, ModelConfig, SGPRConfig,
+from .config import (CGLBConfig, CGLBN2MConfig, CGLBNM2Config, ExactGPConfig, GPRConfig, IterGPRConfig, KernelConfig, Matern32Config, Matern52Config, ModelConfig, SGPRConfig,
                      SGPRN2MConfig, SquaredExponentialConfig)
 from .models import (CGLB, CGLBN2M, CGLBNM2, GPR, SGPR, SGPRN2M, BaseKernel, ExactGPR, GaussianLikelihood, InducingPointKernel, IterGPR,
                      LogMarginalLikelihood, LowerBoundCG, LowerBoundSGPR, PredictCG, PredictGPR, PredictIterGPR, PredictSGPR, ScaleKernel,
@@ -129,9 +129,16 @@ def _create_kernel_m32(cfg: Matern32Config, data: Data):  # interface.py:220-230
 
 
 @create_kernel.register
+def _create_kernel_m52(cfg: Matern52Config, data: Data):  # beyond the reference (registered before its base, the SE config)
+    return _make_kernel("matern52", cfg, data)
+
+
+@create_kernel.register
 def _create_kernel_se(cfg: SquaredExponentialConfig, data: Data):  # interface.py:207-217
     if isinstance(cfg, Matern32Config):
         return _make_kernel("matern32", cfg, data)
+    if isinstance(cfg, Matern52Config):
+        return _make_kernel("matern52", cfg, data)
     return _make_kernel("rbf", cfg, data)
 
 
@@ -145,10 +152,16 @@ def _kernel_numpy(kernel: ScaleKernel, x1, x2, full_cov: bool):
     x2 = x1 if x2 is None else np.asarray(x2, dtype=np.float64)
     a, b = x1 / ls, x2 / ls
     d2 = np.maximum((a * a).sum(1)[:, None] + (b * b).sum(1)[None, :] - 2.0 * a @ b.T, 0.0)
-    if kernel.base_kernel.kind == "rbf":
+    kind = kernel.base_kernel.kind
+    if kind == "rbf":
         return var * np.exp(-0.5 * d2)
-    r = np.sqrt(d2)
-    return var * (1.0 + np.sqrt(3.0) * r) * np.exp(-np.sqrt(3.0) * r)
+    if kind == "matern32":
+        s = np.sqrt(3.0 * d2)
+        return var * (1.0 + s) * np.exp(-s)
+    if kind == "matern52":
+        s = np.sqrt(5.0 * d2)
+        return var * (1.0 + s + s * s / 3.0) * np.exp(-s)
+    raise ValueError(f"no closed form for kernel kind {kind!r}")
 
 
 class _InitKernel:

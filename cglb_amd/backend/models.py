@@ -70,7 +70,7 @@ class BaseKernel(nn.Module):
 
     def __init__(self, kind: str, ard_num_dims: int):
         super().__init__()
-        self.kind = kind  # "rbf" | "matern32"
+        self.kind = kind  # "rbf" | "matern32" | "matern52": a key of hip_context.KINDS
         self._lengthscale = _Constrained((1, ard_num_dims))
 
     @property

@@ -7,6 +7,10 @@ that exercise the hot path:
     python -m cglb_amd.cli -b hip -t fp64 -l LOGDIR train -d DATASET -n STEPS gpr -k Matern32 -m gpr
     python -m cglb_amd.cli -b hip -t fp64 -l LOGDIR gpr_metric -d DATASET -k Matern32 -p RUN/model.json
     python -m cglb_amd.cli -b hip -t fp64 -l LOGDIR train -d DATASET -n STEPS -o adam_0.1 gpr -k Matern32 -m itergp
+    python -m cglb_amd.cli -b hip -t fp64 -l LOGDIR train -d DATASET -n STEPS cglb -k Matern52 -m cglb -i cv -M 1024
+    python -m cglb_amd.cli -b hip -t fp64 -l LOGDIR metric -d DATASET cglb -k mat52 -m cglb -i cv -M 1024 -p LOGDIR/model.json
+
+`-k` takes the reference's SquaredExponential | rbf | Matern32 | mat32 and, beyond its registry, Matern52 | mat52 (every model class).
 
 `cglb -m` takes cglb | cglbn2m | cglbnm2, `sgpr -m` takes sgpr | sgprn2m (cli.py:203-209, :304-310; these four run on one rank).
 `gpr -m gpr` is the exact GP (cli.py:196-200, :293-311: dense Cholesky on the GPU, fp64, one rank); `gpr_metric` (cli.py:166-181) evaluates
@@ -37,11 +41,12 @@ from typing import Callable, Tuple
 import click
 import numpy as np
 
-from .backend import BACKENDS, GPR_CONFIGS, INDUCING_VARIABLE_CONFIGS, KERNEL_CONFIGS, SGPR_CONFIGS, jsonio
+from .backend import BACKENDS, EXTRA_KERNEL_CONFIGS, GPR_CONFIGS, INDUCING_VARIABLE_CONFIGS, KERNEL_CONFIGS, SGPR_CONFIGS, jsonio
 from .backend.callbacks import Logger
 from .data import synthetic_problem
 
 _default_logdir = "./logs"
+_ALL_KERNEL_CONFIGS = {**KERNEL_CONFIGS, **EXTRA_KERNEL_CONFIGS}  # the reference's -k choices and the ones beyond them (Matern52 | mat52)
 
 
 @dataclass
@@ -203,7 +208,7 @@ def metric(ctx, dataset):
 def _cglb_command(group):
     @group.command("cglb")
     @click.option("-m", "--model-class", type=click.Choice(sorted(SGPR_CONFIGS)), required=True)
-    @click.option("-k", "--kernel", type=click.Choice(sorted(KERNEL_CONFIGS)), required=True)
+    @click.option("-k", "--kernel", type=click.Choice(sorted(_ALL_KERNEL_CONFIGS)), required=True)
     @click.option("-i", "--inducing-variable", type=click.Choice(sorted(INDUCING_VARIABLE_CONFIGS)), required=True)
     @click.option("-M", "--num-inducing-variables", default=100, type=int)
     @click.option("-p", "--param_file", type=click.Path(readable=True))
@@ -216,7 +221,7 @@ def _cglb_command(group):
         if model_class not in CGLB_CLASSES:
             raise click.UsageError(f"model class {model_class!r} takes no -e/--vjoint/--vzero: use the `sgpr` command "
                                    f"(... {ctx.parent.info_name} sgpr -m {model_class} -k KERNEL -i IV -M M)", ctx=ctx)
-        cfg = SGPR_CONFIGS[model_class](KERNEL_CONFIGS[kernel](), INDUCING_VARIABLE_CONFIGS[inducing_variable](num_inducing_variables),
+        cfg = SGPR_CONFIGS[model_class](_ALL_KERNEL_CONFIGS[kernel](), INDUCING_VARIABLE_CONFIGS[inducing_variable](num_inducing_variables),
                                         max_error, vjoint, vzero)
         _run_model(ctx, cfg, param_file)
 
@@ -240,14 +245,14 @@ SGPR_CLASSES = ("sgpr", "sgprn2m")
 def _sgpr_command(group):
     @group.command("sgpr")
     @click.option("-m", "--model-class", type=click.Choice(sorted(SGPR_CLASSES)), required=True)
-    @click.option("-k", "--kernel", type=click.Choice(sorted(KERNEL_CONFIGS)), required=True)
+    @click.option("-k", "--kernel", type=click.Choice(sorted(_ALL_KERNEL_CONFIGS)), required=True)
     @click.option("-i", "--inducing-variable", type=click.Choice(sorted(INDUCING_VARIABLE_CONFIGS)), required=True)
     @click.option("-M", "--num-inducing-variables", default=100, type=int)
     @click.option("-p", "--param_file", type=click.Path(readable=True))
     @click.pass_context
     def sgpr(ctx, model_class, kernel, inducing_variable, num_inducing_variables, param_file):
         """cli.py:203-209, :304-310 (_execute_cb_sgpr): SGPR / SGPRN2M on the same inducing-point initialisation as cglb"""
-        cfg = SGPR_CONFIGS[model_class](KERNEL_CONFIGS[kernel](), INDUCING_VARIABLE_CONFIGS[inducing_variable](num_inducing_variables))
+        cfg = SGPR_CONFIGS[model_class](_ALL_KERNEL_CONFIGS[kernel](), INDUCING_VARIABLE_CONFIGS[inducing_variable](num_inducing_variables))
         _run_model(ctx, cfg, param_file)
 
     return sgpr
@@ -256,20 +261,20 @@ def _sgpr_command(group):
 def _gpr_command(group):
     @group.command("gpr")
     @click.option("-m", "--model-class", type=click.Choice(sorted(GPR_CONFIGS)), required=True)
-    @click.option("-k", "--kernel", type=click.Choice(sorted(KERNEL_CONFIGS)), required=True)
+    @click.option("-k", "--kernel", type=click.Choice(sorted(_ALL_KERNEL_CONFIGS)), required=True)
     @click.option("-p", "--param_file", type=click.Path(readable=True))
     @click.pass_context
     def gpr(ctx, model_class, kernel, param_file):
         """cli.py:196-200, :293-301 (_execute_cb_gpr): the exact GP; `exactgp` is listed like in the reference and raises NotImplementedError;
         `itergp` is the iterative exact GP in the library's own estimator (train with -o adam_<lr>)"""
-        _run_model(ctx, GPR_CONFIGS[model_class](KERNEL_CONFIGS[kernel]()), param_file)
+        _run_model(ctx, GPR_CONFIGS[model_class](_ALL_KERNEL_CONFIGS[kernel]()), param_file)
 
     return gpr
 
 
 @main.command("gpr_metric")
 @click.option("-d", "--dataset", type=str, required=True)
-@click.option("-k", "--kernel", type=click.Choice(sorted(KERNEL_CONFIGS)), required=True)
+@click.option("-k", "--kernel", type=click.Choice(sorted(_ALL_KERNEL_CONFIGS)), required=True)
 @click.option("-p", "--param_file", type=click.Path(readable=True), required=True)
 @click.pass_context
 def gpr_metric(ctx, dataset, kernel, param_file):
@@ -278,7 +283,7 @@ def gpr_metric(ctx, dataset, kernel, param_file):
     o = ctx.obj
     bundle = get_dataset(dataset, o["seed"])
     o.update(dataset=bundle, callback=create_metric_fn(o["backend"], bundle, Path(Path(param_file).parent, "gpr_metric.npy")))
-    _run_model(ctx, GPR_CONFIGS["gpr"](KERNEL_CONFIGS[kernel]()), param_file)
+    _run_model(ctx, GPR_CONFIGS["gpr"](_ALL_KERNEL_CONFIGS[kernel]()), param_file)
 
 
 _cglb_command(train)

@@ -1102,7 +1102,7 @@ int cglb_ctx_create(cglb_ctx** out, int64_t n_total, int64_t row_begin, int64_t 
         return CGLB_ERR_BAD_ARG;
     }
     if (n_total <= 0 || row_begin < 0 || row_end < row_begin || row_end > n_total || d <= 0 || m <= 0 ||
-        (dtype != CGLB_F64 && dtype != CGLB_F32) || (kernel_kind != CGLB_RBF && kernel_kind != CGLB_MATERN32)) {
+        (dtype != CGLB_F64 && dtype != CGLB_F32) || (kernel_kind != CGLB_RBF && kernel_kind != CGLB_MATERN32 && kernel_kind != CGLB_MATERN52)) {
         g_create_error = "bad argument to cglb_ctx_create";
         return CGLB_ERR_BAD_ARG;
     }
@@ -1306,7 +1306,7 @@ int cglb_set_hypers(cglb_ctx* c, const double* lengthscales, double variance, do
     c->pwh_src = nullptr;  // the column weights change with the hypers
     {   // |a_i + a_j + xs_i.xs_j| <= 2 max|xs|^2 (scaled units: octaves for RBF, octaves^2 for Matern).  The unclamped 2^x of
         // the hot loops needs the exponent inside [-1000, 0] octaves (exp2_tab_scale) and its hot-unit integer below 2^30.
-        const double ks = (c->kind == CGLB_RBF) ? std::sqrt(CGLB_LOG2E) : CGLB_SQRT3 * CGLB_LOG2E;
+        const double ks = cglb_kscale(c);
         double s2 = 0.0;
         for (int d = 0; d < c->D; ++d) { const double v = c->xrange[d] * ks / c->ls[d]; s2 += v * v; }
         const double oct = (c->kind == CGLB_RBF) ? 2.0 * s2 : 2.0 * std::sqrt(s2);
@@ -1314,10 +1314,10 @@ int cglb_set_hypers(cglb_ctx* c, const double* lengthscales, double variance, do
         // (RBF: the symmetric kernel's unweighted factor 2^(a_i + x_i.x_j) spans [-1.5 s2, 0.5 s2] octaves; fp32 exp2 range is +-126)
         const double oct_max = (c->dtype == CGLB_F32 && c->kind == CGLB_RBF) ? 200.0 : 0.95 * CGLB_EXP_FLOOR_OCT;
         c->exp_clamp = !(int_ok && oct < oct_max);
-        // Matern-3/2: the unclamped fast-level kernels keep d2 = a_i + a_j - 2 x_i.x_j positive by a bias in the row seeds instead of a
+        // Matern-3/2 and -5/2 (same root, same Gram chain): the unclamped fast-level kernels keep d2 = a_i + a_j - 2 x_i.x_j positive by a bias in the row seeds instead of a
         // clamp per pair (devmath.h).  amax = max_i a_i in hot units^2 <= hot_scale^2 s2; beyond the admissible bias the clamped variant runs.
         c->m32_bias = 0.0;
-        if (c->kind == CGLB_MATERN32) {
+        if (c->kind == CGLB_MATERN32 || c->kind == CGLB_MATERN52) {
             const double hs = cglb_hot_scale(c);
             double lmin = c->ls[0];
             for (int d = 1; d < c->D; ++d) lmin = std::fmin(lmin, c->ls[d]);

@@ -177,7 +177,7 @@ struct cglb_ctx {
     int precision = 1;  // CGLB_PREC_FAST (devmath.h): kernel values to <= 1e-13; 0 = CGLB_PREC_EXACT (~3e-16); 2 = CGLB_PREC_LOW (~1e-10, opt-in)
     int kff_variant = 2, kff_jsplit = 0, kff_rows = 4;  // 0 plain, 1 matrix-pipe Gram (fp64), 2 symmetric (default)
     bool exp_clamp = false;         // scaled operands so large that 2^x needs the range clamp (set by set_hypers)
-    double m32_bias = 0.0;          // Matern-3/2: positivity bias of the squared distance in hot units^2 (devmath.h CGLB_M32_BIAS_*; set by set_hypers)
+    double m32_bias = 0.0;          // Matern-3/2 and -5/2: positivity bias of the squared distance in hot units^2 (devmath.h CGLB_M32_BIAS_*; set by set_hypers)
     bool kff_skip_combine = false;  // timing only: launch the pair kernel without the slab combine
     // bound variants (options "logdet_bound", "quad_term"; include/cglb_hip.h).  Both 0: the CGLB bound of models.py:215-286.
     int logdet_bound = 0;  // 0 Jensen (cglb), 1 NM^2 (cglbnm2, sgpr), 2 N^2M (cglbn2m, sgprn2m; fp64, stored panel, one shard)
@@ -328,6 +328,7 @@ int gpr_stat(cglb_ctx* c, const char* name, double* value);  // CGLB_OK if `name
 // kernels_prep.hip
 int launch_prep_scaled(cglb_ctx* c, const void* Xraw, int64_t n, void* Xs_out, void* xa_out, bool hot = false);
 double cglb_hot_scale(const cglb_ctx* c);  // xh = hot_scale * xs
+double cglb_kscale(const cglb_ctx* c);     // xs = (x - centre) / l * kscale: the kind's operand scale
 int launch_select_inducing(cglb_ctx* c, double variance, double jitter, long long* chosen_dev, void* Z_out, double* trace_dev);  // kernels_select.hip
 int launch_kuf(cglb_ctx* c);  // At <- Kuf[:, rows] (unscaled by sigma)
 int launch_kuu(cglb_ctx* c);  // Lc <- Kuu + jitter I (full symmetric)

@@ -7,6 +7,22 @@
 #define CGLB_LOG2E 1.4426950408889634073599246810019
 #define CGLB_LN2 0.69314718055994530941723212145818
 #define CGLB_SQRT3 1.7320508075688772935274463415059
+#define CGLB_SQRT5 2.2360679774997896964091736687313
+
+// The kernel kinds of include/cglb_hip.h as the template parameter KIND.  Every KIND-dependent function names its kinds (if constexpr chain)
+// and ends in cglb_kind_unknown, so that a kind nobody wrote a formula for does not compile instead of evaluating another kind's profile.
+template <int KIND> constexpr bool cglb_kind_known() { return KIND == CGLB_RBF || KIND == CGLB_MATERN32 || KIND == CGLB_MATERN52; }
+template <int KIND> struct cglb_kind_unknown { static_assert(cglb_kind_known<KIND>() && !cglb_kind_known<KIND>(), "no formula for this kernel kind"); };
+// ANY Matern kind: the profile is a function of the root r of the squared distance (row seeds -|x|^2 / 2, norms |x|^2, negated range reduction)
+template <int KIND> constexpr bool cglb_kind_matern() {
+    static_assert(cglb_kind_known<KIND>(), "unknown kernel kind");
+    return KIND == CGLB_MATERN32 || KIND == CGLB_MATERN52;
+}
+// Operand scale: xs = (x - c) / l * kscale makes the exponent of the profile a power of two of the scaled operands
+//   RBF sqrt(log2 e): exp(-d2/2) = 2^(-|xs_i - xs_j|^2 / 2);   Matern-nu: sqrt(2 nu) log2 e: exp(-sqrt(2 nu) r) = 2^(-|xs_i - xs_j|)
+static inline double cglb_kscale_of_kind(int kind) {
+    return kind == CGLB_RBF ? sqrt(CGLB_LOG2E) : (kind == CGLB_MATERN32 ? CGLB_SQRT3 * CGLB_LOG2E : CGLB_SQRT5 * CGLB_LOG2E);
+}
 
 // 2^x for x <= 0 (x may be hugely negative -> 0).  fp64: no hardware transcendental on CDNA, so
 // round-to-nearest split x = n + r, |r| <= 1/2, degree-11 polynomial for 2^r (max rel. error 1.8e-16
@@ -74,6 +90,8 @@ __device__ __forceinline__ float sqrt_pos(float x) { return __builtin_sqrtf(fmax
 // ---- precision levels of the pair kernels (cglb_set_option "precision") ------------------------------------------------------
 //   CGLB_PREC_EXACT (0): degree-4 table polynomial + two-step square root: kernel values to ~3e-16 (1.5 ulp)
 //   CGLB_PREC_FAST  (1): degree-3 polynomial (3.5e-14) + one-step square root (2.1e-14 on r): kernel values to <= ~1e-13 relative.
+//                        Matern-5/2 at FAST: the root's 2.1e-14 through |dkappa/dr| r = s^2 (1 + s) e^-s / 3 <= 0.62 gives 1.3e-14 (of f), plus the
+//                        polynomial's 3.5e-14: <= ~5e-14, inside the same 1e-13.
 // north_star asks for 1e-6 on the bound; FAST is the default (one fma per pair less, two for Matern-3/2).  Every fp64 instruction
 // of the pair stream is ~5 % of the mat-vec (the kernels are bound by vector-fp64 issue).
 #define CGLB_PREC_EXACT 0
@@ -104,13 +122,15 @@ template <int PREC, bool POSITIVE = false> __device__ __forceinline__ double sqr
     return g + g;
 }
 template <int PREC, bool POSITIVE = false> __device__ __forceinline__ float sqrt_hot(float x) { return 2.0f * __builtin_sqrtf(fmaxf(x, 0.0f)); }
-// Bias of the Matern-3/2 squared distance in hot units^2 (added through the row seed -(a_i + bias)/2): d2 = a_i + a_j - 2 x_i.x_j.
+// Bias of the Matern (3/2 and 5/2) squared distance in hot units^2 (added through the row seed -(a_i + bias)/2): d2 = a_i + a_j - 2 x_i.x_j.
 // With u = 2^-53 and amax = max_i a_i: the seed and the D fused multiply-adds of the Gram chain each round a partial sum of size
 // <= 1.5 amax (error of the chain <= (D + 1) 1.5 u amax, doubled by d2 = a_j - 2 gram), and the stored norms a_i, a_j differ from the
 // exact |x|^2 of the stored operands by <= D u amax each: |d2_computed - d2_exact| <= (5 D + 3) u amax.  The bias is 1.5x that bound.
 // A coincident pair then evaluates to kappa = 1 - 2 (ln2/256)^2 bias instead of 1; the bias is only used while that stays below 3e-13
 // (bias <= 2e-8; the headline shape has 1.2e-8), otherwise the clamped variant runs.  Distinct points sit at d2 >~ 1 hot unit^2 and
 // do not see it.
+// Matern-5/2 shares the Gram chain, hence bound, bias and cap (the names keep their M32).  With x = (ln2/256) rT and rT^2 = 4 bias at a coincident
+// pair, kappa = (1 + x + x^2/3) e^-x = 1 - x^2/6 + O(x^3) = 1 - (2/3) (ln2/256)^2 bias: a third of the Matern-3/2 effect, 1e-13 at the cap.
 #define CGLB_M32_BIAS_FACTOR (1.5 * 1.1102230246251565e-16)   // bias = FACTOR * (5 D + 3) * amax
 #define CGLB_M32_BIAS_MAX 2.0e-8
 
@@ -303,20 +323,94 @@ template <> __device__ __forceinline__ float tfma<float>(float a, float b, float
 template <typename T> __device__ __forceinline__ T tmax(T a, T b) { return a > b ? a : b; }
 template <typename T> __device__ __forceinline__ T tmin(T a, T b) { return a < b ? a : b; }
 
+// The Matern profiles as functions of the root r' of the scaled squared distance; `c` is ln 2 per unit of r (ln2 in scaled units, ln2 / 256
+// in hot units), so that s = c r is the argument sqrt(2 nu) |x - x'| of the textbook form and e^(-s) = 2^(-r').
+//   kappa = P(s) e^(-s):            Matern-3/2  P = 1 + s           Matern-5/2  P = 1 + s + s^2 / 3  (Horner: two fma, constants c and c^2 / 3)
+//   h = hscale L(s) e^(-s):         Matern-3/2  3, L = 1            Matern-5/2  5/3, L = 1 + s       (h: dk/dl_d = var h delta_d^2 / l_d)
+// h is finite at r = 0 for both, so coincident points need no special case in the gradient.
+template <typename T, int KIND> __device__ __forceinline__ T matern_kpoly(T r, double c) {
+    if constexpr (KIND == CGLB_MATERN32) return tfma<T>(r, T(c), T(1));
+    else if constexpr (KIND == CGLB_MATERN52) return tfma<T>(r, tfma<T>(r, T(c * c / 3.0), T(c)), T(1));
+    else return (void)cglb_kind_unknown<KIND>{}, T(0);
+}
+// The same factor in the hot pair stream, from the root rT = 2 sqrt(d2) AND the squared distance d2 it came from.  Matern-5/2 takes its
+// quadratic term from d2 (rT^2 = 4 d2): 1 + (4 c^2 / 3) d2 is formed while the root is in flight and ONE fma follows the root, as for
+// Matern-3/2 - the Horner form puts two dependent fma behind the root, which the short Gram chain of the narrow instances does not hide.
+// Where the clamp of the root acted (d2 <= 0 by round-off, |d2| <= the positivity bias) the term is <= (4/3) c^2 2e-8 = 2e-13.
+template <int KIND> __device__ __forceinline__ double matern_kpoly_hot(double rT, double d2) {
+    constexpr double c = CGLB_LN2 / CGLB_HOT_UNITS;
+    if constexpr (KIND == CGLB_MATERN32) return tfma<double>(rT, c, 1.0);
+    else if constexpr (KIND == CGLB_MATERN52) return tfma<double>(rT, c, tfma<double>(d2, 4.0 * c * c / 3.0, 1.0));
+    else return (void)cglb_kind_unknown<KIND>{}, 0.0;
+}
+// the linear factor L of Matern-5/2's gradient profile (every gradient pass calls this one)
+template <typename T> __device__ __forceinline__ T matern52_hlin(T r, double c) { return tfma<T>(r, T(c), T(1)); }
+// the constant of the gradient profile (the Gram-form passes carry it in the row weights)
+template <typename T, int KIND> __device__ __forceinline__ constexpr T hfac_scale() {
+    if constexpr (KIND == CGLB_RBF) return T(1);
+    else if constexpr (KIND == CGLB_MATERN32) return T(3);
+    else if constexpr (KIND == CGLB_MATERN52) return T(5.0 / 3.0);
+    else return (void)cglb_kind_unknown<KIND>{}, T(0);
+}
+// h / e^(-s) of a Matern kind from the root
+template <typename T, int KIND> __device__ __forceinline__ T matern_hpoly(T r, double c) {
+    if constexpr (KIND == CGLB_MATERN32) return T(3);
+    else if constexpr (KIND == CGLB_MATERN52) return T(5.0 / 3.0) * matern52_hlin<T>(r, c);
+    else return (void)cglb_kind_unknown<KIND>{}, T(0);
+}
+
+// Gradient profile of the Gram-form passes without its constant (hfac_scale rides in the row weights): out[r] = L(x[r]) 2^(-x[r]/T) for a
+// Matern kind's root x in hot units, 2^(x[r]/T) for the RBF exponent.  RBF and Matern-3/2 (L = 1) are exp2_tab_batch itself.  Matern-5/2
+// multiplies the scaled table value by L = 1 + c x (matern52_hlin), formed where x is still live for the range reduction - as the mat-vec's
+// lin - so the caller keeps no root across the table reads: one fma and one multiply per pair more than Matern-3/2.  CLAMP: L takes the clamped root;
+// the product is then <= (1 + 1000 ln2) 2^-1000, the zero the clamped table stands for.
+template <int KIND, bool CLAMP, int PREC, int R>
+__device__ __forceinline__ void hfac_tab_batch(const double (&xin)[R], const double* __restrict__ tab_lds, double (&out)[R]) {
+    if constexpr (KIND == CGLB_RBF || KIND == CGLB_MATERN32) {
+        exp2_tab_batch<CLAMP, cglb_kind_matern<KIND>(), PREC, R>(xin, tab_lds, out);
+    } else if constexpr (KIND == CGLB_MATERN52) {
+        double x[R], t[R];
+#pragma unroll
+        for (int r = 0; r < R; ++r) x[r] = CLAMP ? fmin(xin[r], CGLB_EXP_FLOOR_OCT * CGLB_TAB_SIZE) : xin[r];
+        floor_magic<true, R>(x, t);
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            const double s = __builtin_amdgcn_fract(-x[r]);
+            const double lin = matern52_hlin<double>(x[r], CGLB_LN2 / CGLB_HOT_UNITS);
+            const int ni = __double2loint(t[r]);
+            // L goes to the table value, not to the polynomial: with (P * L) the width-8 instance of grad_kff_gram_kernel needs 130 VGPRs (3 waves
+            // per SIMD) instead of its Matern-3/2 twin's 126 (4 waves)
+            out[r] = (exp2_tab_scale(tab_lds[ni & (CGLB_TAB_SIZE - 1)], ni) * lin) * exp2_tab_poly<PREC>(s);
+        }
+    } else {
+        (void)cglb_kind_unknown<KIND>{};
+    }
+}
+template <int KIND, bool CLAMP, int PREC, int R>
+__device__ __forceinline__ void hfac_tab_batch(const float (&xin)[R], const double* __restrict__ tab_lds, float (&out)[R]) {
+    exp2_tab_batch<CLAMP, cglb_kind_matern<KIND>(), PREC, R>(xin, tab_lds, out);
+    if constexpr (KIND == CGLB_MATERN52) {
+#pragma unroll
+        for (int r = 0; r < R; ++r) out[r] *= matern52_hlin<float>(xin[r], CGLB_LN2 / CGLB_HOT_UNITS);
+    }
+}
+
 // Kernel profile from the scaled operands.
 //   RBF:      xs = (x-c)/l*sqrt(log2 e), a = -|xs|^2/2      kappa = 2^(a_i + a_j + xs_i.xs_j)
 //   Matern32: xs = (x-c)/l*sqrt3*log2 e, a = |xs|^2          r' = sqrt(max(a_i+a_j-2 xs_i.xs_j,0)),
 //             kappa = (1 + r' ln2) 2^(-r')
+//   Matern52: xs = (x-c)/l*sqrt5*log2 e, a = |xs|^2          r' as Matern32,  kappa = (1 + r' ln2 + (r' ln2)^2 / 3) 2^(-r')
 // `gram` = a_i + xs_i.xs_j (the fma chain is seeded with a_i).  RBF: arg = gram + a_j may come out a few ulp
 // above 0 for coincident points; 2^arg is then 1 + O(1e-16), harmless, so no clamp is spent on it.
 template <typename T, int KIND, bool CLAMP> __device__ __forceinline__ T kappa_from_gram(T gram, T aj) {
-    if (KIND == CGLB_RBF) {
+    if constexpr (KIND == CGLB_RBF) {
         return exp2_hot<CLAMP>(gram + aj);
     } else {
-        // Matern: the chain is seeded with -a_i/2, so gram = -a_i/2 + xs_i.xs_j and d2 = a_j - 2 gram
+        // any Matern kind: the chain is seeded with -a_i/2, so gram = -a_i/2 + xs_i.xs_j and d2 = a_j - 2 gram
+        static_assert(cglb_kind_matern<KIND>(), "unknown kernel kind");
         T d2 = tfma<T>(T(-2), gram, aj);
         T r = sqrt_pos(tmax<T>(d2, T(0)));
-        return tfma<T>(r, T(CGLB_LN2), T(1)) * exp2_hot<CLAMP>(-r);
+        return matern_kpoly<T, KIND>(r, CGLB_LN2) * exp2_hot<CLAMP>(-r);
     }
 }
 
@@ -324,29 +418,31 @@ template <typename T, int KIND, bool CLAMP> __device__ __forceinline__ T kappa_f
 //   RBF:      xh = 16 xs, ah = 256 a          kappa = 2^((ah_i + ah_j + xh_i.xh_j)/256)
 //   Matern32: xh = 128 xs, ah = 16384 a       rT = 2 sqrt(max(ah_i + ah_j - 2 xh_i.xh_j, 0)),  kappa = (1 + rT ln2/256) 2^(-rT/256)
 //             (half the nominal scale: sqrt_hot returns twice the root)
+//   Matern52: the hot operands and rT of Matern32 (with its own kscale),  kappa = (1 + c rT + (c rT)^2 / 3) 2^(-rT/256), c = ln2/256:
+//             one fma per pair more than Matern32 (matern_kpoly), everything else in the pair stream the same
 // Two-phase evaluation for software-pipelined loops: `begin` does the range reductions of the R rows a lane owns and issues the R
 // table reads, `poly` is independent of the reads, `end` consumes them - so a loop can keep R lookups in flight.
 template <typename T> struct KappaPend { T s; T lin; int ni; T tabv; };
 // FOLDED, RBF: the column norm a_j is not added here - the caller has folded 2^(a_j/T) into the column operand.
-// FOLDED, Matern-3/2: the caller's row seeds carry the positivity bias (sqrt_hot<PREC, true>: no clamp).
+// FOLDED, any Matern kind: the caller's row seeds carry the positivity bias (sqrt_hot<PREC, true>: no clamp).
 template <typename T, int KIND, bool CLAMP, bool FOLDED, int PREC, int R>
 __device__ __forceinline__ void kappa_hot_begin_batch(const T (&gram)[R], T aj, const double* __restrict__ tab, KappaPend<T> (&kp)[R]) {
     if constexpr (sizeof(T) == 8) {
         double x[R], t[R];  // RBF: x = exponent; Matern: x = r (the exponent is -r)
 #pragma unroll
         for (int r = 0; r < R; ++r) {
-            if (KIND == CGLB_RBF) {
+            if constexpr (KIND == CGLB_RBF) {
                 x[r] = FOLDED ? gram[r] : gram[r] + aj;
                 kp[r].lin = T(1);
                 if (CLAMP) x[r] = tmax<double>(x[r], -CGLB_EXP_FLOOR_OCT * CGLB_TAB_SIZE);
-            } else {
+            } else {  // any Matern kind; the polynomial factor is the kind's own
                 const double d2 = tfma<double>(-2.0, gram[r], aj);
                 x[r] = sqrt_hot<PREC, FOLDED>(d2);
-                kp[r].lin = tfma<double>(x[r], CGLB_LN2 / CGLB_HOT_UNITS, 1.0);
+                kp[r].lin = matern_kpoly_hot<KIND>(x[r], d2);
                 if (CLAMP) x[r] = tmin<double>(x[r], CGLB_EXP_FLOOR_OCT * CGLB_TAB_SIZE);
             }
         }
-        constexpr bool NEG = KIND != CGLB_RBF;
+        constexpr bool NEG = cglb_kind_matern<KIND>();  // any Matern kind: the exponent is -x
         floor_magic<NEG, R>(x, t);
 #pragma unroll
         for (int r = 0; r < R; ++r) {
@@ -357,12 +453,12 @@ __device__ __forceinline__ void kappa_hot_begin_batch(const T (&gram)[R], T aj, 
     } else {  // fp32 has a hardware exp2: no table
 #pragma unroll
         for (int r = 0; r < R; ++r) {
-            if (KIND == CGLB_RBF) {
+            if constexpr (KIND == CGLB_RBF) {
                 kp[r].s = FOLDED ? gram[r] : gram[r] + aj;
                 kp[r].lin = T(1);
-            } else {
+            } else {  // any Matern kind
                 const T rr = sqrt_hot<PREC>(tfma<T>(T(-2), gram[r], aj));
-                kp[r].lin = tfma<T>(rr, T(CGLB_LN2 / CGLB_HOT_UNITS), T(1));
+                kp[r].lin = matern_kpoly<T, KIND>(rr, CGLB_LN2 / CGLB_HOT_UNITS);
                 kp[r].s = -rr;
             }
             kp[r].ni = 0;
@@ -375,7 +471,7 @@ template <typename T, int KIND, int PREC> __device__ __forceinline__ void kappa_
     T p;
     if constexpr (sizeof(T) == 4) p = (T)__builtin_amdgcn_exp2f((float)k.s * (1.0f / (float)CGLB_TAB_SIZE));
     else p = exp2_tab_poly<PREC>(k.s);
-    if (KIND != CGLB_RBF) p *= k.lin;
+    if (cglb_kind_matern<KIND>()) p *= k.lin;  // any Matern kind
     k.s = p;
 }
 template <typename T, int KIND> __device__ __forceinline__ T kappa_hot_end(const KappaPend<T>& k) {
@@ -392,12 +488,17 @@ __device__ __forceinline__ T kappa_hot_single(T gram, T aj, const double* __rest
     return kappa_hot_end<T, KIND>(kp[0]);
 }
 
-// gradient factor from an exact squared distance in hot units (RBF: d2h = 256 d2s; Matern32: d2h = 16384 d2s, r = 2 sqrt(d2h))
+// gradient factor from an exact squared distance in hot units (RBF: d2h = 256 d2s; Matern: d2h = 16384 d2s, rT = 2 sqrt(d2h))
 template <typename T, int KIND, bool CLAMP, int PREC> __device__ __forceinline__ T hfac_hot_from_d2(T d2h, const double* __restrict__ tab) {
-    if (KIND == CGLB_RBF) {
+    if constexpr (KIND == CGLB_RBF) {
         return exp2_tab<CLAMP, PREC>(T(-0.5) * d2h, tab);
-    } else {
+    } else if constexpr (KIND == CGLB_MATERN32) {
         return T(3) * exp2_tab<CLAMP, PREC>(T(-2) * sqrt_pos(d2h), tab);
+    } else if constexpr (KIND == CGLB_MATERN52) {
+        const T rT = T(2) * sqrt_pos(d2h);
+        return matern_hpoly<T, KIND>(rT, CGLB_LN2 / CGLB_HOT_UNITS) * exp2_tab<CLAMP, PREC>(-rT, tab);
+    } else {
+        return (void)cglb_kind_unknown<KIND>{}, T(0);
     }
 }
 // cooperative load of the exp2 table into LDS (call from every thread of the block, before any early exit)
@@ -409,19 +510,24 @@ __device__ __forceinline__ void load_exp_table(double* tab_lds, const double* __
 // Kernel profile from an exact scaled squared distance (direct differences; used off the N^2 path).
 //   d2s is in the scaled units above.
 template <typename T, int KIND> __device__ __forceinline__ T kappa_from_d2(T d2s) {
-    if (KIND == CGLB_RBF) {
+    if constexpr (KIND == CGLB_RBF) {
         return exp2_neg(T(-0.5) * d2s);
-    } else {
+    } else {  // any Matern kind
         T r = sqrt_pos(d2s);
-        return tfma<T>(r, T(CGLB_LN2), T(1)) * exp2_neg(-r);
+        return matern_kpoly<T, KIND>(r, CGLB_LN2) * exp2_neg(-r);
     }
 }
 // gradient factor: dk/dl_d = var * hfac * delta_d^2 / l_d with delta in UNscaled-by-kscale units.
 template <typename T, int KIND> __device__ __forceinline__ T hfac_from_d2(T d2s) {
-    if (KIND == CGLB_RBF) {
+    if constexpr (KIND == CGLB_RBF) {
         return exp2_neg(T(-0.5) * d2s);
-    } else {
+    } else if constexpr (KIND == CGLB_MATERN32) {
         return T(3) * exp2_neg(-sqrt_pos(d2s));
+    } else if constexpr (KIND == CGLB_MATERN52) {
+        const T r = sqrt_pos(d2s);
+        return matern_hpoly<T, KIND>(r, CGLB_LN2) * exp2_neg(-r);
+    } else {
+        return (void)cglb_kind_unknown<KIND>{}, T(0);
     }
 }
 

@@ -22,9 +22,12 @@
         default: return cglb_fail(c, CGLB_ERR_BAD_ARG, "unsupported padded dimension"); \
     }
 
-#define CGLB_DISPATCH_KIND(kind, ...)                                       \
-    if ((kind) == CGLB_RBF) { constexpr int KIND = CGLB_RBF; __VA_ARGS__; } \
-    else { constexpr int KIND = CGLB_MATERN32; __VA_ARGS__; }
+// every kind by name: a kind without a branch of its own is an error, never another kind's instance (`c` as in CGLB_DISPATCH_DP)
+#define CGLB_DISPATCH_KIND(kind, ...)                                                           \
+    if ((kind) == CGLB_RBF) { constexpr int KIND = CGLB_RBF; __VA_ARGS__; }                     \
+    else if ((kind) == CGLB_MATERN32) { constexpr int KIND = CGLB_MATERN32; __VA_ARGS__; }      \
+    else if ((kind) == CGLB_MATERN52) { constexpr int KIND = CGLB_MATERN52; __VA_ARGS__; }      \
+    else return cglb_fail(c, CGLB_ERR_BAD_ARG, "unsupported kernel kind");
 
 #define CGLB_DISPATCH_T(dtype, ...)                                         \
     if ((dtype) == CGLB_F64) { using T = double; __VA_ARGS__; }             \

@@ -5,7 +5,7 @@
 // Direct differences are used here (the per-dimension delta^2 is needed anyway), so coincident points
 // contribute exactly 0 and the Matern-3/2 derivative needs no sqrt guard:
 //   dk/dl_d = var * h * delta_d^2 / l_d,  dk/dx1_d = -var * h * delta_d / l_d,
-//   delta_d = (x1_d - x2_d)/l_d,  h = kappa (RBF) | 3 exp(-sqrt3 r) (Matern-3/2).
+//   delta_d = (x1_d - x2_d)/l_d,  h = kappa (RBF) | 3 exp(-sqrt3 r) (Matern-3/2) | 5/3 (1 + sqrt5 r) exp(-sqrt5 r) (Matern-5/2).
 // Operands are the scaled ones of K1 (xs = (x-c)/l*kscale); the 1/(l_d kscale^2) factors are applied
 // in the finalize kernels.
 #include "pair_common.h"
@@ -182,8 +182,8 @@ __global__ __launch_bounds__(256, (DP == CGLB_GRAM_W3_DP ? 3 : 1)) void grad_kff
         }
         S0[k] = 0;
         aseed[k] = pair_row_seed<T, KIND, BIASED>(ah[row0 + rr], bias);
-        // padded rows carry zero weight; Matern-3/2: h = 3 * 2^(-r), the factor 3 rides in the row weights
-        const T hscale = (KIND == CGLB_RBF) ? T(1) : T(3);
+        // padded rows carry zero weight; Matern: h = hscale * L(r) 2^(-r), the constant (3 | 5/3) rides in the row weights
+        const T hscale = hfac_scale<T, KIND>();
         ui[k] = row < n ? hscale * u[row0 + rr] : T(0);
         vi[k] = row < n ? hscale * v[row0 + rr] : T(0);
     }
@@ -213,7 +213,7 @@ __global__ __launch_bounds__(256, (DP == CGLB_GRAM_W3_DP ? 3 : 1)) void grad_kff
                     for (int d = 0; d < DP; ++d) g = tfma<T>(xi[k][d], xj[d], g);
                     earg[k] = (KIND == CGLB_RBF) ? (FOLD ? g : g + aj) : sqrt_hot<PREC, BIASED>(tfma<T>(T(-2), g, aj));  // RBF: exponent; Matern: r (exponent -r)
                 }
-                exp2_tab_batch<CLAMP, KIND != CGLB_RBF, PREC, R>(earg, tab, h);  // CLAMP: exponents beyond the table's range (set_hypers decides)
+                hfac_tab_batch<KIND, CLAMP, PREC, R>(earg, tab, h);  // CLAMP: exponents beyond the table's range (set_hypers decides)
                 T cj = 0;
 #pragma unroll
                 for (int k = 0; k < R; ++k) {
@@ -312,7 +312,7 @@ __global__ __launch_bounds__(256) void grad_dl_finalize_kernel(const double* __r
 #define CGLB_GRAM_ROWS 2
 #endif
 
-static inline double kscale_of(const cglb_ctx* c) { return (c->kind == CGLB_RBF) ? sqrt(CGLB_LOG2E) : CGLB_SQRT3 * CGLB_LOG2E; }
+static inline double kscale_of(const cglb_ctx* c) { return cglb_kscale(c); }
 
 // column-side copies of the two vectors of the bilinear form for the folded column norm (RBF, unclamped range): vw = v o wh over all
 // n_v entries, uw[off + i] = u[i] wh[off + i] over the n_u entries the caller holds.  vw lives in the mat-vec's pwh buffer.
@@ -489,7 +489,7 @@ __global__ __launch_bounds__(256) void grad_panel_kernel(const T* __restrict__ G
             d2 = tfma<T>(df[d], df[d], d2);
         }
         const T kap = kappa_from_d2<T, KIND>(d2);
-        const T h = (KIND == CGLB_RBF) ? kap : hfac_from_d2<T, KIND>(d2);
+        const T h = (KIND == CGLB_RBF) ? kap : hfac_from_d2<T, KIND>(d2);  // every kind by name in hfac_from_d2
         const T W = g * h;
         adf += (double)g * (double)kap;
 #pragma unroll

@@ -50,7 +50,7 @@ __global__ __launch_bounds__(256, 2) void grad_kff_mid_kernel(const double* __re
     const T a = ah[rr];
     // pair_row_seed of pair_common.h, written out (calling it here reschedules every instance); the seed enters the sum of the parts once
     const T aseed = prt ? T(0) : ((KIND == CGLB_RBF) ? a : (BIASED ? T(-0.5) * (a + bias) : T(-0.5) * a));
-    const T hscale = (KIND == CGLB_RBF) ? T(1) : T(3);
+    const T hscale = hfac_scale<T, KIND>();
     const T ui = row < n ? hscale * u[rr] : T(0);
     const T vi = row < n ? hscale * v[rr] : T(0);
     int64_t j0 = (int64_t)blockIdx.y * jchunk;
@@ -82,7 +82,7 @@ __global__ __launch_bounds__(256, 2) void grad_kff_mid_kernel(const double* __re
                 g = sum_halves(g);
                 const T earg[1] = {(KIND == CGLB_RBF) ? (FOLD ? g : g + aj) : sqrt_hot<PREC, BIASED>(tfma<T>(T(-2), g, aj))};
                 T h[1];
-                exp2_tab_batch<CLAMP, KIND != CGLB_RBF, PREC, 1>(earg, tab, h);
+                hfac_tab_batch<KIND, CLAMP, PREC, 1>(earg, tab, h);
                 T w = ui * vj;
                 w = tfma<T>(vi, wu, w);
                 const T hv = h[0] * w;
@@ -134,7 +134,8 @@ __global__ __launch_bounds__(256) void grad_dl_finalize_mid_kernel(const double*
 
 
 // Lanes sharing a matrix row at padded width 96: 2 with the second moments in LDS (16.8 ms at N = 50k; 24.7 with 4).  The Matern-3/2
-// instance of the exact level (two-step square root) does not fit 256 registers that way (101 spilled: 41 ms) and keeps 4 (25.5 ms).
+// instance of the exact level (two-step square root) does not fit 256 registers that way (101 spilled: 41 ms) and keeps 4 (25.5 ms); the
+// Matern-5/2 instance has the same root and one more live constant, so the rule is "any Matern kind".
 static inline int grad_mid_split(const cglb_ctx* c) {
     if (c->Dh != 96) return 2;
     return (c->kind != CGLB_RBF && c->precision == CGLB_PREC_EXACT) ? 4 : 2;

@@ -65,14 +65,21 @@ __device__ __forceinline__ void grad_multi_cols(const double* __restrict__ Xh, c
                 for (int b = 0; b < SP; ++b) w = __builtin_fma(vi[k][b], uj[b], w);
             }
             double hv;
-            if (KIND == CGLB_RBF) {  // h = kappa
+            if constexpr (KIND == CGLB_RBF) {  // h = kappa
                 hv = exp2_tab<true, PREC>(-0.5 * d2, tab) * w;
                 acck[k] += hv;
-            } else {                 // h = 3 e, kappa = (1 + sqrt3 r) e, e = 2^(-rr / T), sqrt3 r = rr ln 2 / T
+            } else if constexpr (KIND == CGLB_MATERN32) {  // h = 3 e, kappa = (1 + sqrt3 r) e, e = 2^(-rr / T), sqrt3 r = rr ln 2 / T
                 const double rr = 2.0 * sqrt_pos(d2);
                 const double ew = exp2_tab<true, PREC>(-rr, tab) * w;
                 hv = 3.0 * ew;
                 acck[k] = __builtin_fma(ew, __builtin_fma(rr, CGLB_LN2 / CGLB_HOT_UNITS, 1.0), acck[k]);
+            } else if constexpr (KIND == CGLB_MATERN52) {  // h = 5/3 (1 + s) e, kappa = (1 + s + s^2 / 3) e, s = sqrt5 r = rr ln 2 / T
+                const double rr = 2.0 * sqrt_pos(d2);
+                const double ew = exp2_tab<true, PREC>(-rr, tab) * w;
+                hv = matern_hpoly<double, KIND>(rr, CGLB_LN2 / CGLB_HOT_UNITS) * ew;
+                acck[k] = __builtin_fma(ew, matern_kpoly<double, KIND>(rr, CGLB_LN2 / CGLB_HOT_UNITS), acck[k]);
+            } else {
+                (void)cglb_kind_unknown<KIND>{};
             }
 #pragma unroll
             for (int d = 0; d < DP; ++d) acc[k][d] = __builtin_fma(hv, sq[d], acc[k][d]);
@@ -147,7 +154,7 @@ static int grad_multi_group(cglb_ctx* c, const double* U, const double* V, int s
     constexpr int R = grad_multi_rows_per_lane(DP);
     const int64_t n = c->N;
     ScaleParams sp;
-    const double ks = ((c->kind == CGLB_RBF) ? sqrt(CGLB_LOG2E) : CGLB_SQRT3 * CGLB_LOG2E) * cglb_hot_scale(c);  // the pass runs on the hot operand set
+    const double ks = cglb_kscale(c) * cglb_hot_scale(c);  // the pass runs on the hot operand set
     for (int d = 0; d < CGLB_MAX_D_NARROW; ++d) {
         sp.center[d] = 0;
         sp.scale[d] = d < c->D ? 1.0 / (c->ls[d] * ks * ks) : 0.0;

@@ -30,7 +30,7 @@ __global__ __launch_bounds__(256) void kff_matvec_kernel(const T* __restrict__ X
         row = row < nrows ? row : nrows - 1;
 #pragma unroll
         for (int d = 0; d < DP; ++d) xi[k][d] = XsRow[row * DP + d];
-        ai[k] = (KIND == CGLB_RBF) ? xaRow[row] : T(-0.5) * xaRow[row];  // seed of the Gram chain
+        ai[k] = cglb_kind_matern<KIND>() ? T(-0.5) * xaRow[row] : xaRow[row];  // seed of the Gram chain (any Matern kind: -|x|^2 / 2)
         acc[k] = 0;
     }
     const int64_t j0 = col0 + (int64_t)blockIdx.y * jchunk;
@@ -121,7 +121,7 @@ __global__ __launch_bounds__(256, (sizeof(T) == 4 ? 4 : 1)) void kff_rect_kernel
         row = row < nrows ? row : nrows - 1;
 #pragma unroll
         for (int d = 0; d < DP; ++d) xi[r][d] = XsRow[row * DP + d];
-        ai[r] = (KIND == CGLB_RBF) ? xaRow[row] : T(-0.5) * xaRow[row];  // seed of the Gram chain
+        ai[r] = cglb_kind_matern<KIND>() ? T(-0.5) * xaRow[row] : xaRow[row];  // seed of the Gram chain (any Matern kind: -|x|^2 / 2)
         acc[r] = 0;
     }
     const int64_t j0 = col0 + k * chunk;

@@ -179,6 +179,8 @@ static int mfma_launch(cglb_ctx* c, const double* FA, int64_t nrows, const doubl
 // Requires r0 % 16 == 0 (row fragments are addressed by 16-row blocks).
 int launch_kff_mfma_pairs(cglb_ctx* c, const double* p_full, int64_t* jsplit_out) {
     if (c->dtype != CGLB_F64 || (c->r0 & 15)) return cglb_fail(c, CGLB_ERR_STATE, "mfma path needs fp64 and a 16-aligned row shard");
+    if (c->kind != CGLB_RBF && c->kind != CGLB_MATERN32)
+        return cglb_fail(c, CGLB_ERR_BAD_ARG, "kff_variant 1 (experimental matrix-pipe mat-vec) has RBF and Matern-3/2 instances only: use kff_variant 0 or 2");
     const int KA = (c->D + 2 + 3) / 4;
     const int64_t nrows = c->nloc;
     const int64_t njt = (c->N + 15) / 16;

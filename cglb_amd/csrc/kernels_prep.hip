@@ -3,7 +3,7 @@
 #include "devmath.h"
 #include "dispatch.h"
 
-// xs[i][d] = (x[i][d] - c_d) * scale_d (zero padded to DP), xa[i] = RBF: -|xs|^2/2, Matern32: |xs|^2
+// xs[i][d] = (x[i][d] - c_d) * scale_d (zero padded to DP), xa[i] = RBF: -|xs|^2/2, any Matern kind: |xs|^2
 template <typename T, int KIND, int DP>
 __global__ __launch_bounds__(256) void prep_scaled_kernel(const T* __restrict__ X, int64_t n, int D, ScaleParams sp,
                                                           T* __restrict__ Xs, T* __restrict__ xa) {
@@ -17,17 +17,19 @@ __global__ __launch_bounds__(256) void prep_scaled_kernel(const T* __restrict__ 
         Xs[i * DP + d] = v;
         s2 = tfma<T>(v, v, s2);
     }
-    xa[i] = (KIND == CGLB_RBF) ? T(-0.5) * s2 : s2;
+    xa[i] = cglb_kind_matern<KIND>() ? s2 : T(-0.5) * s2;
 }
 
 // hot operand set: RBF exponent -|xh_i-xh_j|^2/2 and Matern exponent -2|xh_i-xh_j| are in 1/T octave (T = 2^CGLB_TAB_BITS);
-// Matern-3/2 carries HALF the nominal scale because the hot-loop square root returns 2 sqrt (devmath.h: sqrt_hot)
+// both Matern kinds carry HALF the nominal scale because the hot-loop square root returns 2 sqrt (devmath.h: sqrt_hot)
 double cglb_hot_scale(const cglb_ctx* c) { return (c->kind == CGLB_RBF) ? sqrt(CGLB_HOT_UNITS) : 0.5 * CGLB_HOT_UNITS; }
+// xs = (x - centre) / l * kscale (devmath.h: cglb_kscale_of_kind); every host site that needs the operand scale calls this
+double cglb_kscale(const cglb_ctx* c) { return cglb_kscale_of_kind(c->kind); }
 
 int launch_prep_scaled(cglb_ctx* c, const void* Xraw, int64_t n, void* Xs_out, void* xa_out, bool hot) {
     if (is_wide(c)) return wide_prep_scaled(c, Xraw, n, Xs_out, xa_out, nullptr);  // one operand set: the wide path has no "hot" units
     ScaleParams sp;
-    double kscale = (c->kind == CGLB_RBF) ? sqrt(CGLB_LOG2E) : CGLB_SQRT3 * CGLB_LOG2E;
+    double kscale = cglb_kscale(c);
     if (hot) kscale *= cglb_hot_scale(c);
     for (int d = 0; d < CGLB_MAX_D_NARROW; ++d) {
         sp.center[d] = d < c->D ? c->xmean[d] : 0.0;

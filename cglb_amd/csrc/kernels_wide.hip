@@ -65,7 +65,7 @@ __global__ __launch_bounds__(256) void wide_prep_kernel(const T* __restrict__ X,
         s2 += (double)v * (double)v;
     }
     s2 = wave_sum(s2);
-    if (lane == 0) xa[i] = (KIND == CGLB_RBF) ? (T)(-0.5 * s2) : (T)s2;
+    if (lane == 0) xa[i] = cglb_kind_matern<KIND>() ? (T)s2 : (T)(-0.5 * s2);  // any Matern kind: |xs|^2
 }
 
 // Hot operand set of a mid-width context (32 < D <= 96, fp64): xh = (x - centre) * scale * hot, zero padded to Dh, a = |xh|^2 term -
@@ -84,16 +84,20 @@ __global__ __launch_bounds__(256) void wide_prep_hot_kernel(const T* __restrict_
         s2 += (double)v * (double)v;
     }
     s2 = wave_sum(s2);
-    if (lane == 0) xah[i] = (KIND == CGLB_RBF) ? (T)(-0.5 * s2) : (T)s2;
+    if (lane == 0) xah[i] = cglb_kind_matern<KIND>() ? (T)s2 : (T)(-0.5 * s2);  // any Matern kind: |xh|^2
 }
 
-// kernel value / derivative factor from a Gram entry.  MODE 0: kappa; 1: h with dk/dl_d = var h delta_d^2 / l_d (RBF: kappa; Matern-3/2: 3 2^(-r))
+// kernel value / derivative factor from a Gram entry.  MODE 0: kappa; 1: h with dk/dl_d = var h delta_d^2 / l_d (RBF: kappa; Matern-3/2: 3 2^(-r);
+// Matern-5/2: 5/3 (1 + r ln2) 2^(-r))
 template <typename T, int KIND, int MODE> __device__ __forceinline__ T wide_profile(T g, T ai, T aj) {
-    if (KIND == CGLB_RBF) return exp2_neg(tmin<T>(ai + aj + g, T(0)));   // the exact exponent is <= 0; round-off may leave it a few ulp above
-    const T d2 = tmax<T>(tfma<T>(T(-2), g, ai + aj), T(0));
-    const T r = sqrt_pos(d2);
-    const T e = exp2_neg(-r);
-    return MODE == 0 ? tfma<T>(r, T(CGLB_LN2), T(1)) * e : T(3) * e;
+    if constexpr (KIND == CGLB_RBF) {
+        return exp2_neg(tmin<T>(ai + aj + g, T(0)));   // the exact exponent is <= 0; round-off may leave it a few ulp above
+    } else {  // any Matern kind; the two polynomial factors are the kind's own (devmath.h)
+        const T d2 = tmax<T>(tfma<T>(T(-2), g, ai + aj), T(0));
+        const T r = sqrt_pos(d2);
+        const T e = exp2_neg(-r);
+        return MODE == 0 ? matern_kpoly<T, KIND>(r, CGLB_LN2) * e : matern_hpoly<T, KIND>(r, CGLB_LN2) * e;
+    }
 }
 
 // in place: G[i + j ld] <- scale * profile(G, a_row[i], a_col[j]) (+ diag on i == j); one thread per element, coalesced along i
@@ -295,7 +299,7 @@ __global__ void wide_dl_finish_kernel(const double* __restrict__ a, const double
     if (d < D) out[d] = var * sl[d] * (a[d] - 2.0 * b[d] + cc[d]);
 }
 
-inline double kscale_of(const cglb_ctx* c) { return (c->kind == CGLB_RBF) ? sqrt(CGLB_LOG2E) : CGLB_SQRT3 * CGLB_LOG2E; }
+inline double kscale_of(const cglb_ctx* c) { return cglb_kscale(c); }
 
 // device copies of centre / scale and the per-dimension gradient factors: wsmall = [sl (D): 1/(l ks^2) | sz (D): 1/(l ks) | 3 x D scratch]
 int upload_scales(cglb_ctx* c) {

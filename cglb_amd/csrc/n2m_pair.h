@@ -11,15 +11,31 @@ constexpr int DC = 16;  // input dimensions staged in LDS per step
 
 template <int KIND>
 __device__ __forceinline__ double n2m_kval(double d2, double f) {
-    if (KIND == CGLB_RBF) return f * exp(-0.5 * d2);
-    const double r = sqrt(d2);
-    return f * (1.0 + CGLB_SQRT3 * r) * exp(-CGLB_SQRT3 * r);
+    if constexpr (KIND == CGLB_RBF) {
+        return f * exp(-0.5 * d2);
+    } else if constexpr (KIND == CGLB_MATERN32) {
+        const double r = sqrt(d2);
+        return f * (1.0 + CGLB_SQRT3 * r) * exp(-CGLB_SQRT3 * r);
+    } else if constexpr (KIND == CGLB_MATERN52) {
+        const double s = CGLB_SQRT5 * sqrt(d2);
+        return f * matern_kpoly<double, KIND>(s, 1.0) * exp(-s);
+    } else {
+        return (void)cglb_kind_unknown<KIND>{}, 0.0;
+    }
 }
 // h with dk/dl_d = h delta_d^2 / l_d, delta_d = (x_id - x_jd) / l_d (oracle kernel_grad_factor)
 template <int KIND>
 __device__ __forceinline__ double n2m_hval(double d2, double f) {
-    if (KIND == CGLB_RBF) return f * exp(-0.5 * d2);
-    return 3.0 * f * exp(-CGLB_SQRT3 * sqrt(d2));
+    if constexpr (KIND == CGLB_RBF) {
+        return f * exp(-0.5 * d2);
+    } else if constexpr (KIND == CGLB_MATERN32) {
+        return 3.0 * f * exp(-CGLB_SQRT3 * sqrt(d2));
+    } else if constexpr (KIND == CGLB_MATERN52) {
+        const double s = CGLB_SQRT5 * sqrt(d2);
+        return f * matern_hpoly<double, KIND>(s, 1.0) * exp(-s);
+    } else {
+        return (void)cglb_kind_unknown<KIND>{}, 0.0;
+    }
 }
 
 // stage dimensions [d0, d0 + DC) of the block's 64 rows of I and of J in LDS (zeros outside the tile and beyond D)

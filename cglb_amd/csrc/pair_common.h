@@ -14,13 +14,14 @@ static_assert(sizeof(pair_unit) == sizeof(int2) && offsetof(pair_unit, y) == off
 // kernels fold for every T; the gradient kernels narrow this to fp64 at the use site.
 template <int KIND, bool CLAMP>
 constexpr bool pair_fold() { return KIND == CGLB_RBF && !CLAMP; }
-// Matern-3/2, fast levels, unclamped range, fp64: squared distances kept positive by a bias in the row seeds instead of a clamp per pair
+// Any Matern kind (3/2 and 5/2 share the root and its bias), fast levels, unclamped range, fp64: squared distances kept positive by a bias in the row seeds instead of a clamp per pair
 // (devmath.h CGLB_M32_BIAS_*)
 template <typename T, int KIND, bool CLAMP, int PREC>
-constexpr bool pair_biased() { return KIND != CGLB_RBF && !CLAMP && PREC != CGLB_PREC_EXACT && sizeof(T) == 8; }
-// seed of a row's Gram chain from its norm term a: RBF the exponent's a_i, Matern-3/2 the -|x_i|^2 / 2 of -2 (x_i.x_j - |x_i|^2 / 2) + a_j
+constexpr bool pair_biased() { return cglb_kind_matern<KIND>() && !CLAMP && PREC != CGLB_PREC_EXACT && sizeof(T) == 8; }
+// seed of a row's Gram chain from its norm term a: RBF the exponent's a_i, any Matern kind the -|x_i|^2 / 2 of -2 (x_i.x_j - |x_i|^2 / 2) + a_j
 template <typename T, int KIND, bool BIASED>
 __device__ __forceinline__ T pair_row_seed(T a, T bias) {
+    static_assert(cglb_kind_known<KIND>(), "unknown kernel kind");
     return (KIND == CGLB_RBF) ? a : (BIASED ? T(-0.5) * (a + bias) : T(-0.5) * a);
 }
 

@@ -15,7 +15,8 @@ import torch
 from . import _lib
 
 KINDS = {"rbf": _lib.RBF, "SquaredExponential": _lib.RBF, "matern32": _lib.MATERN32, "Matern32": _lib.MATERN32,
-         "mat32": _lib.MATERN32, 0: _lib.RBF, 1: _lib.MATERN32}
+         "mat32": _lib.MATERN32, "matern52": _lib.MATERN52, "Matern52": _lib.MATERN52, "mat52": _lib.MATERN52,
+         0: _lib.RBF, 1: _lib.MATERN32, 2: _lib.MATERN52}
 
 
 def grad_len(D: int, M: int) -> int:

@@ -35,7 +35,10 @@ extern "C" {
 typedef struct cglb_ctx cglb_ctx;
 
 enum { CGLB_OK = 0, CGLB_ERR_BAD_ARG = 1, CGLB_ERR_NOT_PD = 2, CGLB_ERR_HIP = 3, CGLB_ERR_BLAS = 4, CGLB_ERR_STATE = 5, CGLB_ERR_COMM = 6 };
-enum { CGLB_RBF = 0, CGLB_MATERN32 = 1 };      /* config.py:72-81 SquaredExponentialConfig / Matern32Config */
+enum { CGLB_RBF = 0, CGLB_MATERN32 = 1,        /* config.py:72-81 SquaredExponentialConfig / Matern32Config */
+       CGLB_MATERN52 = 2 };                     /* beyond the reference's registry: k = f (1 + s + s^2/3) e^-s, s = sqrt5 r; gradient factor
+                                                  * h = 5/3 f (1 + s) e^-s (dk/dl_d = h delta_d^2 / l_d).  Every entry point takes it except the
+                                                  * experimental kff_variant 1, which returns CGLB_ERR_BAD_ARG.  cglb_ctx_create refuses any other value. */
 enum { CGLB_F64 = 0, CGLB_F32 = 1 };           /* pytorch/interface.py:94-104 set_default_float */
 
 /* Number of entries of the packed gradient: [dl_1..dl_D, d variance, d noise, d mean, dZ (M*D row-major)] */
