@@ -103,6 +103,11 @@ SIGNATURES = {
                                                POINTER(c_int), POINTER(c_double)]),
     "cglb_itergp_get_coefficients": (c_int, [c_void_p, POINTER(c_double), POINTER(c_double)]),
     "cglb_itergp_predict": (c_int, [c_void_p, c_void_p, c_int64, c_double, c_int, c_void_p, c_void_p]),
+    # Lanczos variance cache of the iterative class: the reference's gpytorch.settings.fast_pred_var() (pytorch/interface.py:582)
+    "cglb_itergp_var_cache": (c_int, [c_void_p, c_int, POINTER(c_int)]),
+    "cglb_itergp_predict_cached": (c_int, [c_void_p, c_void_p, c_int64, c_double, c_int, c_void_p, c_void_p]),
+    "cglb_cross_matmat": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int, c_void_p]),
+    "cglb_time_cross_matmat": (c_int, [c_void_p, c_int64, c_int, c_int, POINTER(c_double)]),
     "cglb_grad_kff_multi": (c_int, [c_void_p, c_void_p, c_void_p, c_int, POINTER(c_double)]),
     "cglb_time_grad_kff_multi": (c_int, [c_void_p, c_int, c_int, POINTER(c_double)]),
 }

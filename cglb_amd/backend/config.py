@@ -85,9 +85,12 @@ ExactGPConfig = _record("ExactGPConfig", (GPRConfig,), doc="Exact GP (gpytorch's
 IterGPRConfig = _record("IterGPRConfig", (GPRConfig,),
                         [("num_probes", int, dataclasses.field(default=10)), ("prec_size", int, dataclasses.field(default=100)),
                          ("max_error", float, dataclasses.field(default=1.0)), ("max_cg_iter", int, dataclasses.field(default=1000)),
-                         ("lanczos_iter", int, dataclasses.field(default=20)), ("seed", int, dataclasses.field(default=0))],
+                         ("lanczos_iter", int, dataclasses.field(default=20)), ("seed", int, dataclasses.field(default=0)),
+                         ("pred_var_rank", int, dataclasses.field(default=0))],
                         doc="Iterative exact GP: batched CG with a pivoted-Cholesky preconditioner of rank prec_size (the reference's _prec_size() = 100) "
-                            "and stochastic Lanczos quadrature on num_probes probe vectors.")
+                            "and stochastic Lanczos quadrature on num_probes probe vectors.  pred_var_rank > 0: predictive variances from a Lanczos "
+                            "variance cache of that rank (the reference's fast_pred_var, pytorch/interface.py:582) - an upper bound of the exact "
+                            "variance that tightens with the rank; 0 (default): exact solves.")
 
 
 def _sgpr_params(self, data: Data):

@@ -249,7 +249,7 @@ def _create_model_itergp(model_cfg: IterGPRConfig, data: Data):
     likelihood, kernel = _likelihood_and_kernel(model_cfg, data, noise_lower_bound=1e-4)
     return IterGPR((np.asarray(data[0]), _targets(data[1])), likelihood, kernel, dtype=_STATE["dtype"], num_probes=model_cfg.num_probes,
                    prec_size=model_cfg.prec_size, max_error=model_cfg.max_error, max_cg_iter=model_cfg.max_cg_iter,
-                   lanczos_iter=model_cfg.lanczos_iter, seed=model_cfg.seed)
+                   lanczos_iter=model_cfg.lanczos_iter, seed=model_cfg.seed, pred_var_rank=model_cfg.pred_var_rank)
 
 
 def _targets(y) -> np.ndarray:
@@ -552,7 +552,8 @@ def _compute_metrics_gpr(model: ExactGPR, dataset_bundle):
 @metrics_fn.register
 def _compute_metrics_itergp(model: IterGPR, dataset_bundle):
     """The metrics of the exact class from the iterative estimator: lml (one draw of the probes), loss = -lml, and rmse / nlpd of the predictive
-    on the train and test sets; the variances cost (n_train + n_test) / 8 batched solves."""
+    on the train and test sets; the variances cost (n_train + n_test) / 8 batched solves, or with the model's `pred_var_rank` > 0 that many
+    Lanczos steps once per call and one multi-column product over all points (pytorch/interface.py:582 runs under fast_pred_var())."""
 
     def itergp_metrics():
         with torch.no_grad():

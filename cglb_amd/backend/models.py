@@ -358,9 +358,10 @@ class IterGPR(_NoInducingGPR):
 
     def __init__(self, data: Data, likelihood: GaussianLikelihood, kernel: ScaleKernel, dtype: torch.dtype = torch.float64,
                  device: Optional[torch.device] = None, context=None, num_probes: int = 10, prec_size: int = 100, max_error: float = 1.0,
-                 max_cg_iter: int = 1000, lanczos_iter: int = 20, seed: int = 0, deterministic_probes: bool = False):
+                 max_cg_iter: int = 1000, lanczos_iter: int = 20, seed: int = 0, deterministic_probes: bool = False, pred_var_rank: int = 0):
         super().__init__(data, likelihood, kernel)
         self.dtype = dtype
+        self.pred_var_rank = int(pred_var_rank)   # > 0: PredictIterGPR takes its variances from a Lanczos variance cache of this rank
         if self.num_outputs > 1:
             raise NotImplementedError("IterGPR is not available for more than one target column (only CGLB takes [N, P] targets)")
         if dtype != torch.float64:
@@ -686,16 +687,22 @@ class PredictGPR(_Predict):
 
 class PredictIterGPR(_Predict):
     """predict_f of the iterative model: mean c + K_*f alpha from one solve at `max_error` (1e-3 like PredictCG), warm-started at the alpha of
-    the last evaluation, and the variances f - k_*^T K^-1 k_* by batched solves, 8 new points at a time: n_new / 8 solves per call."""
+    the last evaluation, and the variances f - k_*^T K^-1 k_* by batched solves, 8 new points at a time: n_new / 8 solves per call.
+    `var_rank` > 0 (None: the model's `pred_var_rank`): the variances from the library's Lanczos variance cache of that rank instead, built once
+    per set of hyper-parameters and applied to every new point by one multi-column product (the reference's metrics run under
+    gpytorch.settings.fast_pred_var(), pytorch/interface.py:582) - an upper bound of the exact variance that tightens with the rank."""
 
     MODEL = IterGPR
 
-    def __init__(self, model: IterGPR, max_error: float = 1e-3):
+    def __init__(self, model: IterGPR, max_error: float = 1e-3, var_rank: Optional[int] = None):
         super().__init__(model)
         self.max_error = float(max_error)
+        self.var_rank = int(model.pred_var_rank if var_rank is None else var_rank)
 
     def mean_and_variance(self, xnew):
         self.model.push_hypers(get_cholesky_jitter())
+        if self.var_rank > 0:
+            return self.model.hip.itergp_predict(xnew, self.max_error, self.model.max_cg_iter, var_rank=min(self.var_rank, self.model.hip.N, 1024))
         return self.model.hip.itergp_predict(xnew, self.max_error, self.model.max_cg_iter)
 
 

@@ -263,11 +263,17 @@ def _gpr_command(group):
     @click.option("-m", "--model-class", type=click.Choice(sorted(GPR_CONFIGS)), required=True)
     @click.option("-k", "--kernel", type=click.Choice(sorted(_ALL_KERNEL_CONFIGS)), required=True)
     @click.option("-p", "--param_file", type=click.Path(readable=True))
+    @click.option("--pred-var-rank", default=0, type=click.IntRange(0, 1024),
+                  help="itergp: predictive variances of the metrics from a Lanczos variance cache of this rank - an upper bound of the exact "
+                       "variance that tightens with the rank (the reference's fast_pred_var uses 100); 0 (default): exact solves, 8 points each")
     @click.pass_context
-    def gpr(ctx, model_class, kernel, param_file):
+    def gpr(ctx, model_class, kernel, param_file, pred_var_rank):
         """cli.py:196-200, :293-301 (_execute_cb_gpr): the exact GP; `exactgp` is listed like in the reference and raises NotImplementedError;
         `itergp` is the iterative exact GP in the library's own estimator (train with -o adam_<lr>)"""
-        _run_model(ctx, GPR_CONFIGS[model_class](_ALL_KERNEL_CONFIGS[kernel]()), param_file)
+        if pred_var_rank and model_class != "itergp":
+            raise click.UsageError("--pred-var-rank belongs to model class itergp")
+        extra = dict(pred_var_rank=pred_var_rank) if pred_var_rank else {}
+        _run_model(ctx, GPR_CONFIGS[model_class](_ALL_KERNEL_CONFIGS[kernel](), **extra), param_file)
 
     return gpr
 

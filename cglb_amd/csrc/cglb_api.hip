@@ -9,6 +9,7 @@
 
 #include "devmath.h"
 #include "dispatch.h"
+#include "lanczos_host.h"
 #include "slq_host.h"
 
 namespace {
@@ -1030,7 +1031,8 @@ int itergp_mark(cglb_ctx* c, int k) {
     return CGLB_OK;
 }
 
-// "itergp_select_ms" | "itergp_solve_ms" | "itergp_grad_ms" of the last evaluation (0 for a phase it did not run); -1: not one of these names
+// "itergp_select_ms" | "itergp_solve_ms" | "itergp_grad_ms" of the last evaluation (0 for a phase it did not run), the statistics of the variance
+// cache; -1: not one of these names
 int itergp_stat(cglb_ctx* c, const char* name, double* value) {
     static const char* names[] = {"itergp_select_ms", "itergp_solve_ms", "itergp_grad_ms"};
     for (int k = 0; k < 3; ++k) {
@@ -1044,6 +1046,20 @@ int itergp_stat(cglb_ctx* c, const char* name, double* value) {
         }
         return CGLB_OK;
     }
+    // "itergp_cache_ms" | "itergp_var_ms": device time of the last cache build / of the variance part of the last cached predictive
+    static const char* cnames[] = {"itergp_cache_ms", "itergp_var_ms"};
+    for (int k = 0; k < 2; ++k) {
+        if (strcmp(name, cnames[k])) continue;
+        *value = 0.0;
+        if (c->it_cev_set[k]) {
+            float ms = 0.f;
+            HIP_CHECK(c, hipEventSynchronize(c->it_cev[2 * k + 1]));
+            HIP_CHECK(c, hipEventElapsedTime(&ms, c->it_cev[2 * k], c->it_cev[2 * k + 1]));
+            *value = ms;
+        }
+        return CGLB_OK;
+    }
+    if (!strcmp(name, "itergp_cache_request")) { *value = (double)c->it_cache_request; return CGLB_OK; }  // 0: no valid cache
     return -1;
 }
 
@@ -1080,6 +1096,120 @@ int itergp_reserve(cglb_ctx* c, int s, size_t eps_doubles) {
         HIP_CHECK(c, hipHostMalloc((void**)&c->it_log.host_pap, (size_t)s * sizeof(double), hipHostMallocDefault));
         c->it_log.host_cap = s;
     }
+    return CGLB_OK;
+}
+
+// alpha = K^-1 e at the tolerance of a predictive call, warm-started at the alpha of the last evaluation (both predictives)
+int itergp_predict_alpha(cglb_ctx* c, double max_error, int max_cg_iter, multi_work* w) {
+    const size_t col = (size_t)c->N * sizeof(double);
+    CGLB_TRY(multi_reserve(c, 8, w));
+    CGLB_TRY(itergp_reserve(c, 8, 0));
+    if (!(c->it_valid && c->have_terms)) {  // no evaluation at the current data and hyper-parameters: the preconditioner first, alpha from zero
+        CGLB_TRY(itergp_common_terms(c));
+        HIP_CHECK(c, hipMemsetAsync(c->it_alpha, 0, col, c->stream));
+    }
+    CGLB_TRY(launch_sub_scalar(c, c->w_e, c->y, c->mean, c->N));
+    CGLB_TRY(pcg_solve(c, fused_ops(c), c->w_e, c->it_alpha, max_error, max_cg_iter, 40, nullptr, nullptr));
+    c->it_valid = true;
+    return CGLB_OK;
+}
+
+// f_mean = mean + K_*f alpha; leaves the hot-scaled new points in (xs, xa)
+int itergp_predict_mean(cglb_ctx* c, const void* xnew, int64_t n_new, void* xr, void* xs, void* xa, void* f_mean) {
+    HIP_CHECK(c, hipMemcpyAsync(xr, xnew, (size_t)n_new * c->D * sizeof(double), hipMemcpyDefault, c->stream));
+    CGLB_TRY(launch_prep_scaled(c, xr, n_new, xs, xa, true));                  // hot units for the pair kernel
+    CGLB_TRY(launch_cross_matvec(c, xs, xa, n_new, c->it_alpha, f_mean));      // K_*f alpha
+    hipLaunchKernelGGL(add_scalar_kernel, dim3(grid1d_full(n_new)), dim3(256), 0, c->stream, (double*)f_mean, n_new, c->mean);
+    CGLB_LAUNCH_CHECK(c);
+    return CGLB_OK;
+}
+
+// ---- Lanczos variance cache (cglb_itergp_var_cache): fixed-order Gram-Schmidt kernels over the row-major [N][ld] basis ----
+#define LANCZOS_QTW_ROWS 512
+// part[blk][k] = sum over the rows of block blk of Q[i][k] w[i]: lane = column (coalesced along a row), the 4 waves interleave the rows and are
+// added in fixed order
+__global__ __launch_bounds__(256) void lanczos_qtw_kernel(const double* __restrict__ Q, int64_t ld, const double* __restrict__ w, int64_t n, int ncols,
+                                                          double* __restrict__ part) {
+    __shared__ double sm[4][64];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int k = blockIdx.y * 64 + lane;
+    const int64_t i0 = (int64_t)blockIdx.x * LANCZOS_QTW_ROWS;
+    const int64_t i1 = i0 + LANCZOS_QTW_ROWS < n ? i0 + LANCZOS_QTW_ROWS : n;
+    double s = 0.0;
+    if (k < ncols)
+        for (int64_t i = i0 + wv; i < i1; i += 4) s = __builtin_fma(Q[i * ld + k], w[i], s);
+    sm[wv][lane] = s;
+    __syncthreads();
+    if (wv == 0 && k < ncols) part[(int64_t)blockIdx.x * ld + k] = (sm[0][lane] + sm[1][lane]) + (sm[2][lane] + sm[3][lane]);
+}
+// coef[k] = sum_blk part[blk][k] in block order
+__global__ __launch_bounds__(256) void lanczos_qtw_sum_kernel(const double* __restrict__ part, int64_t nblk, int64_t ld, int ncols, double* __restrict__ coef) {
+    const int k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= ncols) return;
+    double s = 0.0;
+    for (int64_t b = 0; b < nblk; ++b) s += part[b * ld + k];
+    coef[k] = s;
+}
+// w[i] -= sum_k Q[i][k] coef[k]: a wave takes 16 rows in turn, lane = column, one wave sum per row
+__global__ __launch_bounds__(256) void lanczos_sub_kernel(const double* __restrict__ Q, int64_t ld, const double* __restrict__ coef, int64_t n, int ncols,
+                                                          double* __restrict__ w) {
+    const int lane = threadIdx.x & 63;
+    const int64_t r0 = ((int64_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * 16;
+    for (int64_t i = r0; i < r0 + 16 && i < n; ++i) {
+        double s = 0.0;
+        for (int k = lane; k < ncols; k += 64) s = __builtin_fma(Q[i * ld + k], coef[k], s);
+        s = wave_sum(s);
+        if (lane == 0) w[i] -= s;
+    }
+}
+// q = w / beta, also stored as column j of Q
+__global__ __launch_bounds__(256) void lanczos_next_kernel(const double* __restrict__ w, double beta, int64_t n, double* __restrict__ q, double* __restrict__ Q,
+                                                           int64_t ld, int j) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const double v = w[i] / beta;
+    q[i] = v;
+    Q[i * ld + j] = v;
+}
+// R = Q L^-T in place, row by row: R_j = (Q_j - l_{j-1} R_{j-1}) / d_j
+__global__ __launch_bounds__(256) void lanczos_factor_apply_kernel(double* __restrict__ Q, int64_t ld, int64_t n, int J, const double* __restrict__ d,
+                                                                   const double* __restrict__ l) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    double* __restrict__ row = Q + i * ld;
+    double prev = 0.0;
+    for (int j = 0; j < J; ++j) {
+        const double r = (j > 0 ? row[j] - l[j - 1] * prev : row[j]) / d[j];
+        row[j] = r;
+        prev = r;
+    }
+}
+
+// coef = Q[:, :ncols]^T w, then w -= Q[:, :ncols] coef
+int lanczos_orthogonalise(cglb_ctx* c, int ncols, double* coef) {
+    const int64_t N = c->N, ld = c->it_cache_ld;
+    const int64_t nblk = (N + LANCZOS_QTW_ROWS - 1) / LANCZOS_QTW_ROWS;
+    hipLaunchKernelGGL(lanczos_qtw_kernel, dim3((unsigned)nblk, (unsigned)((ncols + 63) / 64)), dim3(256), 0, c->stream, (const double*)c->it_cache, ld,
+                       (const double*)c->it_lw, N, ncols, c->it_lpart);
+    CGLB_LAUNCH_CHECK(c);
+    hipLaunchKernelGGL(lanczos_qtw_sum_kernel, dim3((unsigned)((ncols + 255) / 256)), dim3(256), 0, c->stream, (const double*)c->it_lpart, nblk, ld, ncols, coef);
+    CGLB_LAUNCH_CHECK(c);
+    hipLaunchKernelGGL(lanczos_sub_kernel, dim3((unsigned)((N + 63) / 64)), dim3(256), 0, c->stream, (const double*)c->it_cache, ld, (const double*)coef, N, ncols,
+                       c->it_lw);
+    CGLB_LAUNCH_CHECK(c);
+    return CGLB_OK;
+}
+
+int itergp_cache_mark(cglb_ctx* c, int k) {
+    if (!c->it_cev[k]) HIP_CHECK(c, hipEventCreate(&c->it_cev[k]));
+    HIP_CHECK(c, hipEventRecord(c->it_cev[k], c->stream));
+    return CGLB_OK;
+}
+
+// the scope of the cache and of the product that applies it: the class's own, and the register-resident width
+int require_var_cache_ok(cglb_ctx* c) {
+    CGLB_TRY(require_itergp_ok(c));
+    if (is_wide(c)) return cglb_fail(c, CGLB_ERR_BAD_ARG, "the variance cache of the iterative exact GP class is available up to 32 input dimensions");
     return CGLB_OK;
 }
 
@@ -1172,6 +1302,7 @@ int cglb_ctx_destroy(cglb_ctx* c) {
     c->mem.release();
     for (hipEvent_t ev : c->gpr_ev) if (ev) (void)hipEventDestroy(ev);
     for (hipEvent_t ev : c->it_ev) if (ev) (void)hipEventDestroy(ev);
+    for (hipEvent_t ev : c->it_cev) if (ev) (void)hipEventDestroy(ev);
     if (c->it_log.host_pap) (void)hipHostFree(c->it_log.host_pap);
     for (hipEvent_t ev : c->k1_events) (void)hipEventDestroy(ev);
     for (hipEvent_t ev : c->eval_events) (void)hipEventDestroy(ev);
@@ -1285,6 +1416,7 @@ int cglb_set_data(cglb_ctx* c, const void* X, const void* y) {
     c->have_data = true;
     c->gpr_factored = false;
     c->it_valid = false;
+    c->it_cache_rank = c->it_cache_request = 0;
     c->p = 1;  // one target column again (cglb_set_targets)
     c->have_local = c->have_terms = false;
     return CGLB_OK;
@@ -1303,6 +1435,7 @@ int cglb_set_hypers(cglb_ctx* c, const double* lengthscales, double variance, do
     HIP_CHECK(c, hipMemcpyAsync(c->Z, Z, (size_t)c->M * c->D * c->esz, hipMemcpyDefault, c->stream));
     c->have_hypers = true;
     c->it_valid = false;
+    c->it_cache_rank = c->it_cache_request = 0;  // the variance cache belongs to the old hyper-parameters
     c->pwh_src = nullptr;  // the column weights change with the hypers
     {   // |a_i + a_j + xs_i.xs_j| <= 2 max|xs|^2 (scaled units: octaves for RBF, octaves^2 for Matern).  The unclamped 2^x of
         // the hot loops needs the exponent inside [-1000, 0] octaves (exp2_tab_scale) and its hot-unit integer below 2^30.
@@ -1645,6 +1778,7 @@ int cglb_select_inducing(cglb_ctx* c, const double* lengthscales, double varianc
     const int rc_prep = launch_prep_scaled(c, c->X, c->N, c->Xs, c->xa);
     for (int d = 0; d < c->D; ++d) c->ls[d] = saved[d];
     c->have_hypers = c->have_local = c->have_terms = false;
+    c->it_cache_rank = c->it_cache_request = 0;
     if (rc_prep != CGLB_OK) return rc_prep;
     const int M = (int)(c->M < c->N ? c->M : c->N);
     long long* chosen_dev = nullptr;
@@ -1934,7 +2068,7 @@ int cglb_get_stat(cglb_ctx* c, const char* name, double* value) {
         if (rc != -1) return rc;
     }
     {
-        const int rc = itergp_stat(c, name, value);  // "itergp_select_ms" | "itergp_solve_ms" | "itergp_grad_ms"
+        const int rc = itergp_stat(c, name, value);  // "itergp_select_ms" | "itergp_solve_ms" | "itergp_grad_ms" | "itergp_cache_ms" | "itergp_var_ms" | "itergp_cache_request"
         if (rc != -1) return rc;
     }
     if (!strcmp(name, "k1_pairs_per_launch")) { *value = c->sym_pairs; return CGLB_OK; }  // of the most recent symmetric launch geometry
@@ -1997,6 +2131,7 @@ int cglb_set_targets(cglb_ctx* c, const void* Y, int p) {
     c->p = p;
     c->gpr_factored = false;  // alpha = K^-1 (y - c) of the exact GPR class belongs to the old targets
     c->it_valid = false;      // ... and so does the one of the iterative class
+    c->it_cache_rank = c->it_cache_request = 0;  // ... and its variance cache (the Lanczos run starts at y - c)
     return CGLB_OK;
 }
 
@@ -2215,27 +2350,14 @@ int cglb_itergp_predict(cglb_ctx* c, const void* xnew, int64_t n_new, double max
     const int64_t N = c->N;
     const size_t col = (size_t)N * sizeof(double);
     multi_work w;
-    CGLB_TRY(multi_reserve(c, 8, &w));
-    CGLB_TRY(itergp_reserve(c, 8, 0));
-    if (!(c->it_valid && c->have_terms)) {  // no evaluation at the current data and hyper-parameters: the preconditioner first, alpha from zero
-        CGLB_TRY(itergp_common_terms(c));
-        HIP_CHECK(c, hipMemsetAsync(c->it_alpha, 0, col, c->stream));
-    }
-    // alpha = K^-1 e at the tolerance of this call, warm-started at the alpha of the last evaluation
-    CGLB_TRY(launch_sub_scalar(c, c->w_e, c->y, c->mean, N));
-    CGLB_TRY(pcg_solve(c, fused_ops(c), c->w_e, c->it_alpha, max_error, max_cg_iter, 40, nullptr, nullptr));
-    c->it_valid = true;
+    CGLB_TRY(itergp_predict_alpha(c, max_error, max_cg_iter, &w));
     void *xr = nullptr, *xs = nullptr, *xa = nullptr;
     DevTemps tmp;  // freed on every path below
     CGLB_TRY(tmp.alloc(c, &xr, (size_t)n_new * c->D * sizeof(double)));
     CGLB_TRY(tmp.alloc(c, &xs, (size_t)n_new * c->Dp * sizeof(double)));
     CGLB_TRY(tmp.alloc(c, &xa, (size_t)n_new * sizeof(double)));
     auto body = [&]() -> int {
-        HIP_CHECK(c, hipMemcpyAsync(xr, xnew, (size_t)n_new * c->D * sizeof(double), hipMemcpyDefault, c->stream));
-        CGLB_TRY(launch_prep_scaled(c, xr, n_new, xs, xa, true));                  // hot units for the pair kernel
-        CGLB_TRY(launch_cross_matvec(c, xs, xa, n_new, c->it_alpha, f_mean));      // K_*f alpha
-        hipLaunchKernelGGL(add_scalar_kernel, dim3(grid1d_full(n_new)), dim3(256), 0, c->stream, (double*)f_mean, n_new, c->mean);
-        CGLB_LAUNCH_CHECK(c);
+        CGLB_TRY(itergp_predict_mean(c, xnew, n_new, xr, xs, xa, f_mean));
         CGLB_TRY(launch_prep_scaled(c, xr, n_new, xs, xa, false));                 // plain scaled units for the panel fill
         // f_var = f - k_*^T K^-1 k_*: batched solves on the columns of K_f*, 8 new points at a time (n_new / 8 solves)
         for (int64_t g0 = 0; g0 < n_new; g0 += 8) {
@@ -2256,6 +2378,154 @@ int cglb_itergp_predict(cglb_ctx* c, const void* xnew, int64_t n_new, double max
     };
     const int rc = body();
     (void)hipStreamSynchronize(c->stream);  // before `tmp` releases the buffers the kernels use
+    return rc;
+}
+
+int cglb_itergp_var_cache(cglb_ctx* c, int rank, int* rank_out) {
+    if (c) c->obj_valid = false;
+    if (!c || !rank_out) return c ? cglb_fail(c, CGLB_ERR_BAD_ARG, "bad argument") : CGLB_ERR_BAD_ARG;
+    *rank_out = 0;
+    CGLB_TRY(require_var_cache_ok(c));
+    if (rank < 1 || rank > 1024 || rank > c->N) return cglb_fail(c, CGLB_ERR_BAD_ARG, "the rank of the variance cache must lie in 1 .. min(n_total, 1024)");
+    HIP_CHECK(c, hipSetDevice(c->device));
+    c->it_cache_rank = c->it_cache_request = 0;
+    const int64_t N = c->N;
+    const int gw = cross_multi_width(), ld = (rank + gw - 1) / gw * gw;
+    const int64_t nblk = (N + LANCZOS_QTW_ROWS - 1) / LANCZOS_QTW_ROWS;
+    CGLB_TRY(c->mem.reserve(c, &c->it_cache, &c->it_cache_cap, (size_t)N * ld * sizeof(double)));
+    CGLB_TRY(c->mem.reserve(c, &c->it_lq, &c->it_lq_cap, (size_t)N * sizeof(double)));
+    CGLB_TRY(c->mem.reserve(c, &c->it_lw, &c->it_lw_cap, (size_t)N * sizeof(double)));
+    CGLB_TRY(c->mem.reserve(c, &c->it_lc, &c->it_lc_cap, (size_t)(2 * ld + 2) * sizeof(double)));
+    CGLB_TRY(c->mem.reserve(c, &c->it_lpart, &c->it_lpart_cap, (size_t)nblk * ld * sizeof(double)));
+    c->it_cache_ld = ld;
+    c->it_cev_set[0] = false;
+    CGLB_TRY(itergp_cache_mark(c, 0));
+    HIP_CHECK(c, hipMemsetAsync(c->it_cache, 0, (size_t)N * ld * sizeof(double), c->stream));  // the padding columns stay zero
+    double* coef = c->it_lc;          // [ld] first pass, [ld] second pass, then |w|^2
+    double* norm2 = c->it_lc + 2 * ld;
+    const unsigned gridn = (unsigned)((N + 255) / 256);
+    // q_0 = e / |e|
+    CGLB_TRY(launch_sub_scalar(c, c->it_lw, c->y, c->mean, N));
+    CGLB_TRY(launch_dot(c, c->it_lw, c->it_lw, N, norm2));
+    double e2 = 0.0;
+    CGLB_TRY(read_scalars(c, norm2, &e2, 1));
+    if (!(e2 > 0.0) || !std::isfinite(e2)) return cglb_fail(c, CGLB_ERR_STATE, "the variance cache starts its Lanczos run at y - mean, which is zero (or not finite)");
+    hipLaunchKernelGGL(lanczos_next_kernel, dim3(gridn), dim3(256), 0, c->stream, (const double*)c->it_lw, std::sqrt(e2), N, c->it_lq, c->it_cache, (int64_t)ld, 0);
+    CGLB_LAUNCH_CHECK(c);
+    std::vector<double> alpha, beta;
+    int J = 0;
+    for (int j = 0; j < rank; ++j) {
+        CGLB_TRY(launch_kff_matvec(c, c->it_lq, c->it_lw, nullptr));   // w = K q_j: the context's own mat-vec, noise included
+        CGLB_TRY(lanczos_orthogonalise(c, j + 1, coef));               // two passes over all columns so far; coef[j] of the first is alpha_j
+        CGLB_TRY(lanczos_orthogonalise(c, j + 1, coef + ld));
+        CGLB_TRY(launch_dot(c, c->it_lw, c->it_lw, N, norm2));
+        double aj = 0.0, b2 = 0.0;
+        HIP_CHECK(c, hipMemcpyAsync(&aj, coef + j, sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        CGLB_TRY(read_scalars(c, norm2, &b2, 1));
+        const double bj = std::sqrt(b2);
+        alpha.push_back(aj);
+        beta.push_back(bj);
+        J = j + 1;
+        if (lanczos_stop(j, rank, bj, alpha[0])) break;
+        hipLaunchKernelGGL(lanczos_next_kernel, dim3(gridn), dim3(256), 0, c->stream, (const double*)c->it_lw, bj, N, c->it_lq, c->it_cache, (int64_t)ld, j + 1);
+        CGLB_LAUNCH_CHECK(c);
+    }
+    std::vector<double> diag, sub;
+    if (lanczos_bidiag_factor(alpha.data(), beta.data(), J, diag, sub) != 0)
+        return cglb_fail(c, CGLB_ERR_NOT_PD, "variance cache: the Lanczos tridiagonal is not positive definite");
+    HIP_CHECK(c, hipMemcpyAsync(c->it_lc, diag.data(), (size_t)J * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    HIP_CHECK(c, hipMemcpyAsync(c->it_lc + ld, sub.data(), (size_t)J * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(lanczos_factor_apply_kernel, dim3(gridn), dim3(256), 0, c->stream, c->it_cache, (int64_t)ld, N, J, (const double*)c->it_lc,
+                       (const double*)(c->it_lc + ld));
+    CGLB_LAUNCH_CHECK(c);
+    CGLB_TRY(itergp_cache_mark(c, 1));
+    HIP_CHECK(c, hipStreamSynchronize(c->stream));  // diag / sub are read until here
+    c->it_cev_set[0] = true;
+    c->it_cache_rank = J;
+    c->it_cache_request = rank;
+    *rank_out = J;
+    return CGLB_OK;
+}
+
+int cglb_itergp_predict_cached(cglb_ctx* c, const void* xnew, int64_t n_new, double max_error, int max_cg_iter, void* f_mean, void* f_var) {
+    if (c) c->obj_valid = false;
+    if (!c || !xnew || !f_mean || !f_var || n_new < 0 || max_cg_iter < 0) return c ? cglb_fail(c, CGLB_ERR_BAD_ARG, "bad argument") : CGLB_ERR_BAD_ARG;
+    CGLB_TRY(require_var_cache_ok(c));
+    if (c->it_cache_rank < 1) return cglb_fail(c, CGLB_ERR_STATE, "cglb_itergp_var_cache must precede cglb_itergp_predict_cached at the current data and hyper-parameters");
+    if (n_new == 0) return CGLB_OK;
+    HIP_CHECK(c, hipSetDevice(c->device));
+    multi_work w;
+    CGLB_TRY(itergp_predict_alpha(c, max_error, max_cg_iter, &w));
+    const int gw = cross_multi_width(), r_pad = (c->it_cache_rank + gw - 1) / gw * gw;
+    CGLB_TRY(c->mem.reserve(c, &c->it_blk, &c->it_blk_cap, (size_t)n_new * r_pad * sizeof(double)));
+    void *xr = nullptr, *xs = nullptr, *xa = nullptr;
+    DevTemps tmp;  // freed on every path below
+    CGLB_TRY(tmp.alloc(c, &xr, (size_t)n_new * c->D * sizeof(double)));
+    CGLB_TRY(tmp.alloc(c, &xs, (size_t)n_new * c->Dp * sizeof(double)));
+    CGLB_TRY(tmp.alloc(c, &xa, (size_t)n_new * sizeof(double)));
+    auto body = [&]() -> int {
+        CGLB_TRY(itergp_predict_mean(c, xnew, n_new, xr, xs, xa, f_mean));
+        // f_var = f - |R^T k_*|^2: one multi-column product K_*f R over the padded columns of the cache, then the row norms of the summed block
+        c->it_cev_set[1] = false;
+        CGLB_TRY(itergp_cache_mark(c, 2));
+        CGLB_TRY(launch_cross_multi(c, xs, xa, n_new, c->it_cache, c->it_cache_ld, r_pad, c->it_blk, r_pad));
+        CGLB_TRY(launch_cross_multi_var(c, c->it_blk, n_new, r_pad, r_pad, (double*)f_var));
+        CGLB_TRY(itergp_cache_mark(c, 3));
+        c->it_cev_set[1] = true;
+        return CGLB_OK;
+    };
+    const int rc = body();
+    (void)hipStreamSynchronize(c->stream);  // before `tmp` releases the buffers the kernels use
+    return rc;
+}
+
+int cglb_cross_matmat(cglb_ctx* c, const void* xnew, int64_t n_new, const void* V, int S, void* out) {
+    if (c) c->obj_valid = false;
+    if (!c || !xnew || !V || !out || n_new < 0 || S < 1) return c ? cglb_fail(c, CGLB_ERR_BAD_ARG, "bad argument") : CGLB_ERR_BAD_ARG;
+    CGLB_TRY(require_var_cache_ok(c));
+    if (n_new == 0) return CGLB_OK;
+    HIP_CHECK(c, hipSetDevice(c->device));
+    void *xr = nullptr, *xs = nullptr, *xa = nullptr;
+    DevTemps tmp;  // freed on every path below
+    CGLB_TRY(tmp.alloc(c, &xr, (size_t)n_new * c->D * sizeof(double)));
+    CGLB_TRY(tmp.alloc(c, &xs, (size_t)n_new * c->Dp * sizeof(double)));
+    CGLB_TRY(tmp.alloc(c, &xa, (size_t)n_new * sizeof(double)));
+    auto body = [&]() -> int {
+        HIP_CHECK(c, hipMemcpyAsync(xr, xnew, (size_t)n_new * c->D * sizeof(double), hipMemcpyDefault, c->stream));
+        CGLB_TRY(launch_prep_scaled(c, xr, n_new, xs, xa, true));  // rows of the pair kernel: hot units
+        int64_t ldv = 0;
+        CGLB_TRY(launch_cross_multi_operand(c, V, S, &ldv));
+        return launch_cross_multi(c, xs, xa, n_new, (const double*)c->cm_vi, ldv, S, (double*)out, S);
+    };
+    const int rc = body();
+    (void)hipStreamSynchronize(c->stream);  // before `tmp` releases the buffers the kernels use
+    return rc;
+}
+
+int cglb_time_cross_matmat(cglb_ctx* c, int64_t n_new, int S, int reps, double* ms_avg) {
+    if (c) c->obj_valid = false;
+    if (!c || !ms_avg || reps <= 0 || S == 0 || n_new < 1) return c ? cglb_fail(c, CGLB_ERR_BAD_ARG, "bad argument") : CGLB_ERR_BAD_ARG;
+    CGLB_TRY(require_var_cache_ok(c));
+    if (n_new > c->N) return cglb_fail(c, CGLB_ERR_BAD_ARG, "the timed product takes its new points from the training rows: n_new <= n_total");
+    HIP_CHECK(c, hipSetDevice(c->device));
+    const int s = S < 0 ? -S : S;
+    multi_work w;
+    CGLB_TRY(multi_reserve(c, s, &w));
+    void* out = nullptr;
+    DevTemps tmp;
+    CGLB_TRY(tmp.alloc(c, &out, (size_t)n_new * s * sizeof(double)));
+    // operands: the first n_new training rows as new points, s copies of y as columns (values do not change the instruction stream)
+    for (int b = 0; b < s; ++b) HIP_CHECK(c, hipMemcpyAsync(w.p + (size_t)b * c->N * c->esz, c->y, (size_t)c->N * c->esz, hipMemcpyDeviceToDevice, c->stream));
+    const int rc = time_repeated(c, reps, [&]() -> int {
+        if (S < 0) {  // the comparison side: s single products
+            for (int b = 0; b < s; ++b) CGLB_TRY(launch_cross_matvec(c, c->Xh, c->xah, n_new, w.p + (size_t)b * c->N * c->esz, (double*)out + (size_t)b * n_new));
+            return CGLB_OK;
+        }
+        int64_t ldv = 0;
+        CGLB_TRY(launch_cross_multi_operand(c, w.p, s, &ldv));
+        return launch_cross_multi(c, c->Xh, c->xah, n_new, (const double*)c->cm_vi, ldv, s, (double*)out, s);
+    }, ms_avg);
+    (void)hipStreamSynchronize(c->stream);
     return rc;
 }
 

@@ -234,6 +234,21 @@ struct cglb_ctx {
     bool it_valid = false;                              // it_alpha and the common terms belong to the current data, targets and hyper-parameters
     hipEvent_t it_ev[4] = {nullptr, nullptr, nullptr, nullptr};  // start | pivots and common terms | solve | gradient of the last evaluation
     int it_ev_last = 0;                                 // index of the last event that evaluation recorded (0: none, 2: value only, 3: with gradient)
+    // Lanczos variance cache of the class (cglb_itergp_var_cache) and the multi-column cross product that applies it (kernels_cross_multi.hip)
+    double* it_cache = nullptr;                         // [N][it_cache_ld]: Q during the build, then R = Q L^-T with K^-1 ~ R R^T; zero beyond column J
+    size_t it_cache_cap = 0;
+    int it_cache_rank = 0, it_cache_ld = 0;             // J columns in use (0: no valid cache); row stride = the requested rank rounded up to 8
+    int it_cache_request = 0;                           // the rank the valid cache was asked for
+    double *it_lq = nullptr, *it_lw = nullptr, *it_lc = nullptr, *it_lpart = nullptr;  // [N] q_j, [N] w, [2 ld + 2] coefficients, block partials of Q^T w
+    size_t it_lq_cap = 0, it_lw_cap = 0, it_lc_cap = 0, it_lpart_cap = 0;
+    double* it_blk = nullptr;                           // [rows][r_pad] summed block K_*f R of the cached predictive
+    size_t it_blk_cap = 0;
+    hipEvent_t it_cev[4] = {nullptr, nullptr, nullptr, nullptr};  // cache build start | end, cached variance start | end
+    bool it_cev_set[2] = {false, false};
+    void* cm_part = nullptr;                            // partial-sum slabs [jsplit][rows][8] of the multi-column cross product
+    size_t cm_part_cap = 0;
+    void* cm_vi = nullptr;                              // [N][S rounded up to 8] interleaved column operand of cglb_cross_matmat
+    size_t cm_vi_cap = 0;
     std::string err;
 };
 
@@ -362,6 +377,13 @@ int launch_cross_matvec(cglb_ctx* c, const void* Xs_new, const void* xa_new, int
 // One evaluation of every kernel value for up to 8 pairs where grad_multi_native(c), S single passes elsewhere.
 bool grad_multi_native(const cglb_ctx* c);
 int launch_grad_kff_multi(cglb_ctx* c, const void* U, const void* V, int S, double* out);
+// kernels_cross_multi.hip: out[i * ldo + s] = var * sum_j kappa(row_i, x_j) Vi[j * ldv + s], s < S; Vi dev [N][ldv] row-major (ldv a multiple of 8, zero
+// padded), rows hot-scaled; every kernel value evaluated once per group of 8 columns.  fp64, Dp <= 32.  Bitwise repeatable.
+int launch_cross_multi(cglb_ctx* c, const void* XsRow, const void* xaRow, int64_t nrows, const double* Vi, int64_t ldv, int S, double* out, int64_t ldo);
+int launch_cross_multi_operand(cglb_ctx* c, const void* V, int S, int64_t* ldv_out);  // c->cm_vi <- V [S][N] interleaved
+int launch_cross_multi_var(cglb_ctx* c, const double* blk, int64_t nrows, int sp, int64_t ld, double* f_var);  // f_var[i] = var - |blk[i][:sp]|^2
+int cross_multi_rows_per_block(const cglb_ctx* c);  // new points per workgroup of the pair kernel at the context's width
+int cross_multi_width();                            // columns per group (8): the leading dimensions are multiples of it
 // kernels_vec.hip
 // dot, update_v_r, update_p: s columns of length n ([s][n], one launch each; per-column device scalars [s]); s = 1 is the one-column form.
 // A zero denominator gives a zero factor.

@@ -349,13 +349,53 @@ class HipContext:
         _lib.check(rc, self._ctx)
         return rz, pap
 
-    def itergp_predict(self, xnew, max_error=1e-3, max_cg_iter=1000) -> Tuple[torch.Tensor, torch.Tensor]:
-        """predict_f mean and variance at xnew [n_new, D]: one solve for alpha and n_new / 8 batched solves for the variances."""
+    def itergp_predict(self, xnew, max_error=1e-3, max_cg_iter=1000, var_rank=0) -> Tuple[torch.Tensor, torch.Tensor]:
+        """predict_f mean and variance at xnew [n_new, D]: one solve for alpha and n_new / 8 batched solves for the variances.  var_rank > 0:
+        the variances from the Lanczos variance cache of that rank instead (built first when there is no valid one of that rank) - an upper
+        bound of the exact variance that tightens with the rank."""
         xn = self._xnew(xnew)
         mean, var = self.empty(xn.shape[0]), self.empty(xn.shape[0])
-        rc = self.lib.cglb_itergp_predict(self._ctx, _ptr(xn), xn.shape[0], float(max_error), int(max_cg_iter), _ptr(mean), _ptr(var))
+        if var_rank and int(var_rank) > 0:
+            if int(self.get_stat("itergp_cache_request")) != int(var_rank):
+                self.itergp_var_cache(int(var_rank))
+            rc = self.lib.cglb_itergp_predict_cached(self._ctx, _ptr(xn), xn.shape[0], float(max_error), int(max_cg_iter), _ptr(mean), _ptr(var))
+        else:
+            rc = self.lib.cglb_itergp_predict(self._ctx, _ptr(xn), xn.shape[0], float(max_error), int(max_cg_iter), _ptr(mean), _ptr(var))
         _lib.check(rc, self._ctx)
         return mean, var
+
+    def itergp_var_cache(self, rank: int) -> int:
+        """Builds the Lanczos variance cache (K^-1 ~ R R^T, `rank` Lanczos steps started at y - mean) at the current data and hyper-parameters;
+        returns the number of columns J <= rank (smaller when the Krylov space closed early)."""
+        out = c_int()
+        _lib.check(self.lib.cglb_itergp_var_cache(self._ctx, int(rank), byref(out)), self._ctx)
+        return out.value
+
+    def itergp_predict_cached(self, xnew, max_error=1e-3, max_cg_iter=1000) -> Tuple[torch.Tensor, torch.Tensor]:
+        """cglb_itergp_predict_cached as it is: RuntimeError without a valid cache."""
+        xn = self._xnew(xnew)
+        mean, var = self.empty(xn.shape[0]), self.empty(xn.shape[0])
+        rc = self.lib.cglb_itergp_predict_cached(self._ctx, _ptr(xn), xn.shape[0], float(max_error), int(max_cg_iter), _ptr(mean), _ptr(var))
+        _lib.check(rc, self._ctx)
+        return mean, var
+
+    def cross_matmat(self, xnew, V, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """variance kappa(xnew, X) V for V [N, S]: [n_new, S], one evaluation of every kernel value per group of 8 columns (cglb_cross_matmat).
+        `out`: a contiguous device tensor [n_new, S] to write into."""
+        xn = self._xnew(xnew)
+        Vt = self._cols(V)
+        if out is None:
+            out = torch.empty((xn.shape[0], Vt.shape[0]), dtype=self.dtype, device=self.device)
+        elif out.device != self.device or out.dtype != self.dtype or tuple(out.shape) != (xn.shape[0], Vt.shape[0]) or not out.is_contiguous():
+            raise ValueError("out must be a contiguous device tensor [n_new, S] in the context dtype")
+        _lib.check(self.lib.cglb_cross_matmat(self._ctx, _ptr(xn), xn.shape[0], _ptr(Vt), int(Vt.shape[0]), _ptr(out)), self._ctx)
+        return out
+
+    def time_cross_matmat(self, n_new: int, s: int, reps: int) -> float:
+        """ms per product with s > 0 columns at the first n_new training rows; s < 0: |s| single cross mat-vecs on the same operands."""
+        ms = c_double()
+        _lib.check(self.lib.cglb_time_cross_matmat(self._ctx, int(n_new), int(s), int(reps), byref(ms)), self._ctx)
+        return ms.value
 
     def grad_kff_multi(self, U, V) -> np.ndarray:
         """[sum_b u_b^T (dK_ff / dl_d) v_b for d < D, sum_b u_b^T kappa v_b] for U, V [N, S]: one evaluation of every kernel value for up to 8 pairs."""

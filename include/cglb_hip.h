@@ -296,9 +296,38 @@ int cglb_itergp_objective_and_grad(cglb_ctx* ctx, const void* eps, int t, void* 
 int cglb_itergp_get_coefficients(cglb_ctx* ctx, double* rz_log, double* pap_log);
 /* predict_f: f_mean = mean + K_*f alpha with alpha = K^-1 e solved to max_error (warm-started at the alpha of the last evaluation at the current
  * data and hyper-parameters; without one the preconditioner is built first), f_var = variance - k_*^T K^-1 k_* by batched solves on the columns
- * of K_f*, 8 new points at a time (each to 1/2 sum_b r_b^T P^-1 r_b <= max_error): n_new / 8 solves - a Lanczos variance cache is not part
- * of this.  xnew: any [n_new, d], d <= 32; f_mean, f_var: dev [n_new]. */
+ * of K_f*, 8 new points at a time (each to 1/2 sum_b r_b^T P^-1 r_b <= max_error): n_new / 8 solves.  The Lanczos variance cache below
+ * (cglb_itergp_var_cache, cglb_itergp_predict_cached) is the opt-in that replaces these solves.  xnew: any [n_new, d], d <= 32; f_mean, f_var:
+ * dev [n_new]. */
 int cglb_itergp_predict(cglb_ctx* ctx, const void* xnew, int64_t n_new, double max_error, int max_cg_iter, void* f_mean, void* f_var);
+/* Lanczos variance cache: what the reference's exact-GP metrics get from gpytorch.settings.fast_pred_var() (pytorch/interface.py:582) - a low-rank
+ * approximation of K^-1 built once and applied to every new point.  gpytorch's start vector is not reproduced; the estimator is defined here and
+ * pinned to tests/love_ref.py.  Scope of cglb_itergp_predict (fp64, one rank, one target column, d <= 32; else CGLB_ERR_BAD_ARG).
+ *   Lanczos  on K = variance kappa(X, X) + noise I with full reorthogonalisation, started at q_0 = e / |e|, e = y - mean (CGLB_ERR_STATE if e = 0):
+ *            w = K q_j (the context's own mat-vec), alpha_j = q_j^T w, two passes w <- w - Q (Q^T w) over all columns so far, beta_j = |w|;
+ *            stop with J = j + 1 columns when j + 1 = rank or beta_j <= 1e-10 alpha_0 (the Krylov space has closed: with an RBF kernel K has
+ *            about a hundred numerically distinct eigenvalues - this is a normal end, not an error), else q_{j+1} = w / beta_j
+ *   factor   T = tridiag(alpha, beta) = L L^T on the host, L lower bidiagonal (csrc/lanczos_host.h); CGLB_ERR_NOT_PD at a pivot that is not positive
+ *   cache    R = Q L^-T (R_j = (Q_j - l_{j-1} R_{j-1}) / d_j), so that K^-1 ~ R R^T; dev [n_total][rank rounded up to 8] row-major in a grow-only
+ *            buffer of the context, zero beyond column J: the cache row of a training point is one contiguous scalar load
+ *   variance f_var(x*) = variance - sum_s (sum_j variance kappa(x*, x_j) R[j, s])^2
+ * A Galerkin projection of K^-1: f_var is never below the exact variance, does not increase with the rank and is exact at J = n_total.  It is an
+ * APPROXIMATION - an upper bound that tightens with the rank (DESIGN.md section 4f has measured overestimates).  1 <= rank <= min(n_total, 1024);
+ * rank_out = J.  Two builds on the same inputs give bitwise equal caches.  cglb_set_data, cglb_set_hypers, cglb_set_targets and
+ * cglb_select_inducing invalidate the cache. */
+int cglb_itergp_var_cache(cglb_ctx* ctx, int rank, int* rank_out);
+/* cglb_itergp_predict with the variance from the cache: f_mean as there (the same solve for alpha, the same product), f_var from one
+ * multi-column product K_*f R (cglb_cross_matmat's kernel) and the row norms of the result.  CGLB_ERR_STATE without a valid cache. */
+int cglb_itergp_predict_cached(cglb_ctx* ctx, const void* xnew, int64_t n_new, double max_error, int max_cg_iter, void* f_mean, void* f_var);
+/* The product of the cached predictive on its own (tests, timing): out[i, s] = variance sum_j kappa(xnew_i, x_j) V[s, j].  xnew: any [n_new, d];
+ * V: dev [S, n_total], column s contiguous (the convention of cglb_grad_kff_multi); out: dev [n_new, S] row-major.  Every kernel value is
+ * evaluated once per group of 8 columns (csrc/kernels_cross_multi.hip); always the range-clamped 2^x; bitwise reproducible.  Scope of
+ * cglb_itergp_predict_cached. */
+int cglb_cross_matmat(cglb_ctx* ctx, const void* xnew, int64_t n_new, const void* V, int S, void* out);
+/* average duration (ms) of `reps` back-to-back products with S > 0 columns (operand interleave, pair kernel and fixed-order sum of every group, on
+ * the context stream) at the first n_new training rows as new points (n_new <= n_total), beside cglb_time_grad_kff_multi; S < 0 times the
+ * comparison side instead: |S| single products of cglb_cross_matvec's kernel on the same operands */
+int cglb_time_cross_matmat(cglb_ctx* ctx, int64_t n_new, int S, int reps, double* ms_avg);
 /* The gradient pass of the class on its own (tests, timing): out host double[d + 1], out[k] = sum_b u_b^T (dK_ff / dl_k) v_b for k < d and
  * out[d] = sum_b u_b^T kappa v_b (kappa = K_ff / variance), b < S.  U, V: dev [S, n_total], pair b contiguous.  Every kernel value is evaluated
  * once per unordered pair for up to 8 pairs of vectors (fp64, d <= 32: csrc/kernels_grad_multi.hip; wider inputs run S single passes); S > 8
@@ -342,7 +371,9 @@ int cglb_time_kernel(cglb_ctx* ctx, int which, int reps, double* ms_avg);
  * time (HIP events on the context stream) of the phases of the last cglb_gpr_objective_and_grad - tiles of K | factorisation | alpha and the
  * scalars | K^-1 | gradient pass; 0 for a phase that evaluation did not run;
  * "itergp_select_ms" | "itergp_solve_ms" | "itergp_grad_ms": device time of the phases of the last cglb_itergp_objective_and_grad - pivots and
- * common terms | right-hand sides and the batched solve | gradient; 0 for a phase that evaluation did not run. */
+ * common terms | right-hand sides and the batched solve | gradient; 0 for a phase that evaluation did not run;
+ * "itergp_cache_ms" | "itergp_var_ms": device time of the last cglb_itergp_var_cache | of the variance part (product and row norms) of the last
+ * cglb_itergp_predict_cached; "itergp_cache_request": the rank the valid variance cache was asked for, 0 without a valid cache. */
 int cglb_get_stat(cglb_ctx* ctx, const char* name, double* value);
 /* Tunables: name = "kff_variant" | "kff_jsplit" | "kff_rows" | "sym_chunk" | "precond_mode" | "chol_mode" | "pcg_lookahead" | "sym_order" | "aat_block" | "grad_gram" | "k1_profile" |
  * "grad_trsm" (gradient algebra against L = chol(K_uu): 0 products with the explicit inverse, 1 backward-stable triangular solves, 2 = default:
