@@ -141,7 +141,8 @@ __global__ __launch_bounds__(256) void update_p_seg_kernel(T* __restrict__ p, co
                                                            const T* __restrict__ wh, T* __restrict__ pw) {
     double nrz = 0.0;
     for (int g = 0; g < world; ++g) nrz += (double)zseg[(int64_t)g * (per + 1) + per];
-    const T beta = restart ? T(0) : (T)(nrz / rz[0]);
+    const double den = rz[0];
+    const T beta = (restart || den == 0.0) ? T(0) : (T)(nrz / den);  // the zero-denominator rule of update_p_kernel
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
         const T zi = zseg[i + i / per];  // slice g = i / per starts at g * (per + 1)
         const T pi = restart ? zi : tfma<T>(beta, p[i], zi);

@@ -163,11 +163,17 @@ int cglb_vec_update_p(cglb_ctx* ctx, int64_t n, void* p, const void* z, const vo
 /* p = z + p * (new_rz / rz) (or p = z) with z all-gathered in `world` slices of per + 1 elements (cglb_shard_precond_z_seg) and
  * new_rz = the sum, in rank order, of the slices' extra elements: the stop-test scalar is then identical on every rank by
  * construction.  new_rz: dev double[1], written; rz: dev double[1], the previous value (conjugate_gradient.py:75-76).
+ * As in cglb_vec_update_p, rz == 0 gives a zero factor (p = z, finite); a NaN in either scalar still propagates into p.
+ * With restart = 1 the value of rz is not used, so new_rz and rz may be the same slot (the first call of a solve).
  * The kernel also prepares the operand of the NEXT cglb_matvec_cyclic(p): p must not be modified in between (the PCG loop does not). */
 int cglb_vec_update_p_seg(cglb_ctx* ctx, int64_t n, int64_t per, int world, void* p, const void* zseg, void* new_rz, const void* rz, int restart);
 int cglb_vec_axpy(cglb_ctx* ctx, int64_t n, double alpha, const void* x, void* y); /* y += alpha x */
 /* objective phase 1 with (K_ff + noise I) v already computed for the local rows; phase 2 unchanged; the local slice of
- * w = P r for the all-gather of u = w + v/2; phase 3 with the cyclic share of the N^2 gradient form (u_full gathered). */
+ * w = P r for the all-gather of u = w + v/2; phase 3 with the cyclic share of the N^2 gradient form (u_full gathered).
+ * Placement of that share: the global upper triangle of the symmetric form is dealt by row blocks, block b to rank b mod world, like the
+ * mat-vec's, but the block size is that of the gradient kernel's instance (256 threads x 1, 2 or 4 rows, chosen from the padded input width,
+ * the dtype and the option grad_gram; tiles on the wide path) and not the mat-vec's 256 rows.  Only the sum over the ranks of the lengthscale
+ * entries is defined by this interface; every other entry of grad_partial is placed as in cglb_shard_obj_phase3. */
 int cglb_shard_obj_phase1_kv(cglb_ctx* ctx, const void* Kv_local, void* u_partial);
 int cglb_shard_obj_w(cglb_ctx* ctx, void* w_local_out);
 int cglb_shard_obj_phase3_cyclic(cglb_ctx* ctx, const void* v_full, const void* u_full, const void* sc, const void* aw, void* grad_partial);

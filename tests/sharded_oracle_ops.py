@@ -17,15 +17,25 @@ class OracleLocalOps(LocalOps):
         self.N, self.D = X.shape
         self.M = hyp.Z.shape[0]
         self.r0, self.r1 = r0, r1
-        self.Kloc = orc.kernel_matrix(kind, X[r0:r1], X, hyp.lengthscales, hyp.variance)  # K_ff[I_g, :]
+        self._Kloc = self._Kfull = None   # built on first use by an op that needs K_ff (the vector and preconditioner ops do not)
         self._aat = torch.zeros(self.M * self.M, dtype=torch.float64)
 
     def set_hypers(self, lengthscales, variance, noise, mean, Z, jitter):
         Z = np.asarray(Z.detach().cpu().numpy() if isinstance(Z, torch.Tensor) else Z, dtype=np.float64).reshape(self.M, self.D)
         self.hyp = orc.Hypers(np.asarray(lengthscales, dtype=np.float64).reshape(-1).copy(), float(variance), float(noise), float(mean), Z.copy(), float(jitter))
-        self.Kloc = orc.kernel_matrix(self.kind, self.X[self.r0:self.r1], self.X, self.hyp.lengthscales, self.hyp.variance)
-        if hasattr(self, "Kfull"):
-            self.Kfull = orc.kernel_matrix(self.kind, self.X, self.X, self.hyp.lengthscales, self.hyp.variance)
+        self._Kloc = self._Kfull = None
+
+    @property
+    def Kloc(self):                                          # K_ff[I_g, :]
+        if self._Kloc is None:
+            self._Kloc = orc.kernel_matrix(self.kind, self.X[self.r0:self.r1], self.X, self.hyp.lengthscales, self.hyp.variance)
+        return self._Kloc
+
+    @property
+    def Kfull(self):
+        if self._Kfull is None:
+            self._Kfull = orc.kernel_matrix(self.kind, self.X, self.X, self.hyp.lengthscales, self.hyp.variance)
+        return self._Kfull
 
     def y_full(self):
         return torch.from_numpy(np.asarray(self.y, dtype=np.float64).copy())
@@ -64,7 +74,7 @@ class OracleLocalOps(LocalOps):
         if rz is not None:
             rz[0] = float(rp @ r.numpy()) / self.hyp.noise
     def update_v_r(self, v, r, p, Ap, rz, pAp, update_r):
-        gamma = float(rz[0]) / float(pAp[0])
+        gamma = 0.0 if float(pAp[0]) == 0.0 else float(rz[0]) / float(pAp[0])   # a zero denominator gives a zero factor; NaN propagates
         v += gamma * p
         if update_r:
             r -= gamma * Ap
@@ -73,7 +83,7 @@ class OracleLocalOps(LocalOps):
         if restart:
             p.copy_(z)
         else:
-            p.copy_(z + p * (float(new_rz[0]) / float(rz[0])))
+            p.copy_(z + p * (0.0 if float(rz[0]) == 0.0 else float(new_rz[0]) / float(rz[0])))   # same rule
 
     # objective phases (mirror of cglb_api.hip obj_phase1..3)
     def obj_phase1(self, v_full, u):
@@ -157,7 +167,6 @@ class OracleSymLocalOps(OracleLocalOps, SymLocalOps):
     def __init__(self, kind, X, y, hyp, r0, r1):
         super().__init__(kind, X, y, hyp, r0, r1)
         self.world, self.rank = 1, 0
-        self.Kfull = orc.kernel_matrix(kind, X, X, hyp.lengthscales, hyp.variance)
 
     @property
     def noise(self):
@@ -202,7 +211,7 @@ class OracleSymLocalOps(OracleLocalOps, SymLocalOps):
         if restart:
             p[:n].copy_(z)
         else:
-            p[:n].copy_(z + p[:n] * (nrz / float(rz[0])))
+            p[:n].copy_(z + p[:n] * (0.0 if float(rz[0]) == 0.0 else nrz / float(rz[0])))   # same rule
         new_rz[0] = nrz
 
     def obj_phase1_kv(self, Kv_local, u):
@@ -215,7 +224,6 @@ class OracleSymLocalOps(OracleLocalOps, SymLocalOps):
 
     def obj_phase3_cyclic(self, v_full, u_full, sc, aw, grad):
         # everything except the N^2 form exactly as the row-sharded phase 3 ...
-        saved = self.Kloc
         super().obj_phase3(v_full, sc, aw, grad)
         g = grad.numpy().copy()
         D, ls, f = self.D, np.asarray(self.hyp.lengthscales, dtype=np.float64), self.hyp.variance
