@@ -347,8 +347,9 @@ int cglb_time_grad_kff_multi(cglb_ctx* ctx, int S, int reps, double* ms_avg);
  * The reference calls robustgp.ConditionalVariance(sample=False) (third-party): greedy maximisation of the conditional
  * variance under the INITIAL kernel (pivoted Cholesky of K_ff, lowest index on ties).  Needs set_data only; works on all n rows
  * whatever the row range of the context, so every rank of a sharded run obtains the same answer.  `lengthscales` host [d];
- * indices_out: host [min(m, n)] row indices in selection order; Z_out: dev [m, d] = X[indices] or NULL; trace_out: host,
- * sum of the remaining conditional variances, tr(K_ff - Q_ff) (+ n * jitter), or NULL.  Invalidates set_hypers (the scaled
+ * indices_out: host [min(m, n)] row indices in selection order; Z_out: dev [m, d] or NULL: rows 0 .. min(m, n) - 1 receive X[indices], with
+ * m > n the rows from n on are left as they were; trace_out: host, sum of the remaining conditional variances,
+ * tr(K_ff - Q_ff) (+ n * jitter), or NULL.  Invalidates set_hypers (the scaled
  * operand buffers are used as scratch).  Blocking. */
 int cglb_select_inducing(cglb_ctx* ctx, const double* lengthscales, double variance, double jitter, int64_t* indices_out, void* Z_out,
                          double* trace_out);
