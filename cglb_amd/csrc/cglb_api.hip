@@ -1206,10 +1206,12 @@ int itergp_cache_mark(cglb_ctx* c, int k) {
     return CGLB_OK;
 }
 
-// the scope of the cache and of the product that applies it: the class's own, and the register-resident width
-int require_var_cache_ok(cglb_ctx* c) {
+// the scope of the cache: the class's own, at any width (wide inputs apply it through the Gram tiles of kernels_wide.hip)
+int require_var_cache_ok(cglb_ctx* c) { return require_itergp_ok(c); }
+// the scope of the register-resident multi-column cross product behind cglb_cross_matmat (kernels_cross_multi.hip)
+int require_cross_multi_ok(cglb_ctx* c) {
     CGLB_TRY(require_itergp_ok(c));
-    if (is_wide(c)) return cglb_fail(c, CGLB_ERR_BAD_ARG, "the variance cache of the iterative exact GP class is available up to 32 input dimensions");
+    if (is_wide(c)) return cglb_fail(c, CGLB_ERR_BAD_ARG, "the register-resident multi-column cross product is available up to 32 input dimensions");
     return CGLB_OK;
 }
 
@@ -2071,6 +2073,7 @@ int cglb_get_stat(cglb_ctx* c, const char* name, double* value) {
         const int rc = itergp_stat(c, name, value);  // "itergp_select_ms" | "itergp_solve_ms" | "itergp_grad_ms" | "itergp_cache_ms" | "itergp_var_ms" | "itergp_cache_request"
         if (rc != -1) return rc;
     }
+    if (!strcmp(name, "matmat_native")) { *value = (c->have_data && kff_multi_native(c)) ? 1.0 : 0.0; return CGLB_OK; }  // shared-kernel instance or single mat-vecs
     if (!strcmp(name, "k1_pairs_per_launch")) { *value = c->sym_pairs; return CGLB_OK; }  // of the most recent symmetric launch geometry
     if (!strcmp(name, "kpart_bytes")) { *value = (double)c->kpart_cap; return CGLB_OK; }     // partial-sum slabs of the mat-vec
     if (!strcmp(name, "comm_allreduce_calls")) { *value = c->comm ? (double)c->comm->n_allreduce : 0.0; return CGLB_OK; }
@@ -2344,7 +2347,6 @@ int cglb_itergp_predict(cglb_ctx* c, const void* xnew, int64_t n_new, double max
     if (c) c->obj_valid = false;
     if (!c || !xnew || !f_mean || !f_var || n_new < 0 || max_cg_iter < 0) return c ? cglb_fail(c, CGLB_ERR_BAD_ARG, "bad argument") : CGLB_ERR_BAD_ARG;
     CGLB_TRY(require_itergp_ok(c));
-    if (is_wide(c)) return cglb_fail(c, CGLB_ERR_BAD_ARG, "the predictive of the iterative exact GP class is available up to 32 input dimensions");
     if (n_new == 0) return CGLB_OK;
     HIP_CHECK(c, hipSetDevice(c->device));
     const int64_t N = c->N;
@@ -2363,10 +2365,14 @@ int cglb_itergp_predict(cglb_ctx* c, const void* xnew, int64_t n_new, double max
         for (int64_t g0 = 0; g0 < n_new; g0 += 8) {
             const int sg = (int)std::min<int64_t>(8, n_new - g0);
             using T = double;
-            dim3 grid((unsigned)((N + 255) / 256), 1);
-            CGLB_DISPATCH_KIND(c->kind, CGLB_DISPATCH_DP(c->Dp, hipLaunchKernelGGL((kus_kernel<T, KIND, DP>), grid, dim3(256), 0, c->stream,
-                                                                                    (const T*)xs + g0 * DP, (const T*)c->Xs, N, N, sg, (T)c->var, (T*)w.b)));
-            CGLB_LAUNCH_CHECK(c);
+            if (is_wide(c)) {  // the panel of the wide operand set, the training rows as its column side
+                CGLB_TRY(wide_kpanel(c, (const T*)xs + g0 * c->D, sg, c->Xs, N, N, w.b));
+            } else {
+                dim3 grid((unsigned)((N + 255) / 256), 1);
+                CGLB_DISPATCH_KIND(c->kind, CGLB_DISPATCH_DP(c->Dp, hipLaunchKernelGGL((kus_kernel<T, KIND, DP>), grid, dim3(256), 0, c->stream,
+                                                                                        (const T*)xs + g0 * DP, (const T*)c->Xs, N, N, sg, (T)c->var, (T*)w.b)));
+                CGLB_LAUNCH_CHECK(c);
+            }
             HIP_CHECK(c, hipMemsetAsync(c->it_V, 0, (size_t)sg * col, c->stream));
             if (sg == 1) CGLB_TRY(pcg_solve(c, fused_ops(c), w.b, c->it_V, max_error, max_cg_iter, 40, nullptr, nullptr));
             else CGLB_TRY(pcg_solve(c, multi_ops(c, w, sg), w.b, c->it_V, max_error, max_cg_iter, 40, nullptr, nullptr));
@@ -2468,7 +2474,8 @@ int cglb_itergp_predict_cached(cglb_ctx* c, const void* xnew, int64_t n_new, dou
         // f_var = f - |R^T k_*|^2: one multi-column product K_*f R over the padded columns of the cache, then the row norms of the summed block
         c->it_cev_set[1] = false;
         CGLB_TRY(itergp_cache_mark(c, 2));
-        CGLB_TRY(launch_cross_multi(c, xs, xa, n_new, c->it_cache, c->it_cache_ld, r_pad, c->it_blk, r_pad));
+        if (is_wide(c)) CGLB_TRY(wide_cross_multi(c, xs, xa, n_new, c->it_cache, c->it_cache_ld, r_pad, c->it_blk, r_pad));  // Gram tiles + one GEMM each
+        else CGLB_TRY(launch_cross_multi(c, xs, xa, n_new, c->it_cache, c->it_cache_ld, r_pad, c->it_blk, r_pad));
         CGLB_TRY(launch_cross_multi_var(c, c->it_blk, n_new, r_pad, r_pad, (double*)f_var));
         CGLB_TRY(itergp_cache_mark(c, 3));
         c->it_cev_set[1] = true;
@@ -2482,7 +2489,7 @@ int cglb_itergp_predict_cached(cglb_ctx* c, const void* xnew, int64_t n_new, dou
 int cglb_cross_matmat(cglb_ctx* c, const void* xnew, int64_t n_new, const void* V, int S, void* out) {
     if (c) c->obj_valid = false;
     if (!c || !xnew || !V || !out || n_new < 0 || S < 1) return c ? cglb_fail(c, CGLB_ERR_BAD_ARG, "bad argument") : CGLB_ERR_BAD_ARG;
-    CGLB_TRY(require_var_cache_ok(c));
+    CGLB_TRY(require_cross_multi_ok(c));
     if (n_new == 0) return CGLB_OK;
     HIP_CHECK(c, hipSetDevice(c->device));
     void *xr = nullptr, *xs = nullptr, *xa = nullptr;
@@ -2505,7 +2512,7 @@ int cglb_cross_matmat(cglb_ctx* c, const void* xnew, int64_t n_new, const void* 
 int cglb_time_cross_matmat(cglb_ctx* c, int64_t n_new, int S, int reps, double* ms_avg) {
     if (c) c->obj_valid = false;
     if (!c || !ms_avg || reps <= 0 || S == 0 || n_new < 1) return c ? cglb_fail(c, CGLB_ERR_BAD_ARG, "bad argument") : CGLB_ERR_BAD_ARG;
-    CGLB_TRY(require_var_cache_ok(c));
+    CGLB_TRY(require_cross_multi_ok(c));
     if (n_new > c->N) return cglb_fail(c, CGLB_ERR_BAD_ARG, "the timed product takes its new points from the training rows: n_new <= n_total");
     HIP_CHECK(c, hipSetDevice(c->device));
     const int s = S < 0 ? -S : S;

@@ -326,6 +326,9 @@ int wide_prep_hot(cglb_ctx* c);   // Xh (N x Dh, zero padded), xah in hot units 
 int wide_kuf(cglb_ctx* c);
 int wide_kuu(cglb_ctx* c);
 int wide_kus(cglb_ctx* c, const void* XsNew, int64_t n_new, int64_t ld, void* out);
+int wide_kpanel(cglb_ctx* c, const void* Zs, int M, const void* XsNew, int64_t n_new, int64_t ld, void* out);  // out[m * ld + n] = var K(z_m, xnew_n), any two scaled sets
+// out[i * ldo + s] = var * sum_j kappa(row_i, x_j) Vi[j * ldv + s], s < S (fp64): what launch_cross_multi is to narrow inputs, through the Gram tiles
+int wide_cross_multi(cglb_ctx* c, const void* XsRow, const void* xaRow, int64_t nrows, const double* Vi, int64_t ldv, int S, double* out, int64_t ldo);
 int wide_matvec(cglb_ctx* c, const void* XsRow, const void* xaRow, int64_t row0_global, int64_t nrows, const void* p_full, void* out, bool diag_noise,
                 double* pdot_slot, int tile_stride, int tile_offset);
 int wide_grad_kff(cglb_ctx* c, const void* v_full, const void* u_rows, int64_t row0, int64_t nrows, int tile_stride, int tile_offset, double* out_dl);
@@ -365,6 +368,17 @@ int launch_grad_kff_cyclic(cglb_ctx* c, const void* v_full, const void* u_full, 
 // columns where kff_multi_native(c), s single mat-vecs elsewhere.
 bool kff_multi_native(const cglb_ctx* c);
 int launch_kff_matmat(cglb_ctx* c, const void* V, int s, void* Out);
+// what the two pair kernels of the product share (kernels_kff_multi.hip): the span / LDS-chunk geometry with its work list and slabs, the
+// interleaved column operand c->mm_vi (pre-weighted where `fold`), and the combine of the slabs into Out
+struct multi_geometry {
+    int64_t span = 0, chunk = 0, prow_ld = 0;
+    int Q = 0, nwg = 0, nrb = 0, nspan = 0;
+    double *Prow = nullptr, *Pcol = nullptr;
+};
+int multi_prepare(cglb_ctx* c, const double* V, int s, int sp, int rbrows, bool fold, multi_geometry* geo);
+int multi_combine(cglb_ctx* c, const multi_geometry& geo, int rbrows, int sp, const double* V, int s, double* Out);
+// kernels_kff_multi_mid.hip: one group of 2 .. multi_mid_group(Dh) columns of a context with mid_reg(c) (32 < D <= 96, fp64), both exponent ranges
+int launch_kff_multi_mid(cglb_ctx* c, const double* V, int sg, double* Out);
 int launch_kff_plain_range(cglb_ctx* c, const void* p_full, int64_t col0, int64_t col1, void* part, int64_t* nslots);
 int launch_kff_mfma_pairs(cglb_ctx* c, const double* p_full, int64_t* jsplit_out);
 int launch_pairs_rect(cglb_ctx* c, const void* XsRow, const void* xaRow, int64_t nrows, const void* XsCol, const void* xaCol, const void* pcol,

@@ -19,12 +19,12 @@
 // Slab layout (double), n = N:
 //   Prow[K][b][li], K < nspan : row sums of span K (valid for K >= the span that holds the first row of block rb(i)), ld prow_ld
 //   Pcol[g][b][j], g < ceil(nrb / 4) : column sums produced by the group of row blocks 4g .. 4g+3 (valid where the group starts left of j)
-// Scope: fp64, Dp <= 32, unclamped exponent range, one rank, full square.  Everything else falls back to S single mat-vecs
+// Scope: fp64, Dp <= 32, unclamped exponent range, one rank, full square; the mid widths (32 < D <= 96) have a pair kernel of their own
+// (kernels_kff_multi_mid.hip) behind the same geometry, operand and combine.  Everything else falls back to S single mat-vecs
 // (launch_kff_matmat below).
 #include "pair_common.h"
 
 #define MULTI_PART 16        // partial sums per lane and batch: 16 / S_pad columns x S_pad right-hand sides
-#define MULTI_CS_MAX 1024    // column sums a wave stages in LDS (columns of a chunk x S_pad)
 #define MULTI_LATE_DP 24     // padded width from which the next column's x operand is fetched after the Gram chain (SGPR budget)
 
 // rows per lane: at most 4 (the single kernel's 8 at Dp <= 4 left the Matern instances 10 VGPRs over the 256 of two waves per SIMD),
@@ -286,48 +286,63 @@ static int ensure_multi_items(cglb_ctx* c, int64_t n, int rbrows, int64_t span, 
     return CGLB_OK;
 }
 
-template <int KIND, int DP, int SP>
-static int kff_multi_generic(cglb_ctx* c, const double* V, int s, double* Out, bool skip_combine) {
-    constexpr int R = multi_rows_per_lane(DP, SP);
-    constexpr int RBROWS = 64 * R;
-    constexpr bool FOLD = pair_fold<KIND, false>();
+// Geometry, work list, slabs and the interleaved operand of one group of the product (both pair kernels: this file and kernels_kff_multi_mid.hip)
+int multi_prepare(cglb_ctx* c, const double* V, int s, int sp, int rbrows, bool fold, multi_geometry* geo) {
     const int64_t n = c->N;
-    // span: the column chunk rule of the single kernel (option "sym_chunk"); LDS chunk: at most MULTI_CS_MAX / SP columns of it, Q to the span
-    int64_t span = pair_column_chunk(n, RBROWS, 1, c->sym_chunk_opt);
-    const int64_t chunk = std::min<int64_t>(span, MULTI_CS_MAX / SP);  // 512 / 256 / 128: multiples of 16
+    // span: the column chunk rule of the single kernel (option "sym_chunk"); LDS chunk: at most MULTI_CS_MAX / sp columns of it, Q to the span
+    int64_t span = pair_column_chunk(n, rbrows, 1, c->sym_chunk_opt);
+    const int64_t chunk = std::min<int64_t>(span, MULTI_CS_MAX / sp);  // 512 / 256 / 128: multiples of 16
     const int Q = (int)((span + chunk - 1) / chunk);
     span = (int64_t)Q * chunk;
     int nwg = 0;
-    CGLB_TRY(ensure_multi_items(c, n, RBROWS, span, &nwg));
-    const int nrb = (int)((n + RBROWS - 1) / RBROWS), ngroups = (nrb + 3) / 4, nspan = (int)((n + span - 1) / span);
-    const int64_t prow_ld = (int64_t)nrb * RBROWS;
-    const size_t need = ((size_t)ngroups * n + (size_t)nspan * prow_ld) * SP * sizeof(double);
+    CGLB_TRY(ensure_multi_items(c, n, rbrows, span, &nwg));
+    const int nrb = (int)((n + rbrows - 1) / rbrows), ngroups = (nrb + 3) / 4, nspan = (int)((n + span - 1) / span);
+    const int64_t prow_ld = (int64_t)nrb * rbrows;
+    const size_t need = ((size_t)ngroups * n + (size_t)nspan * prow_ld) * sp * sizeof(double);
     CGLB_TRY(pair_reserve_slabs(c, &c->mm_part, &c->mm_part_cap, need, "K_ff mat-mat", "", "multiply fewer columns at a time"));
     CGLB_TRY(c->mem.reserve(c, &c->mm_vi, &c->mm_vi_cap, (size_t)n * 8 * sizeof(double)));
-    double* Prow = (double*)c->mm_part;
-    double* Pcol = Prow + (size_t)nspan * prow_ld * SP;
-    hipLaunchKernelGGL(multi_operand_kernel, dim3((unsigned)((n * SP + 255) / 256)), dim3(256), 0, c->stream, V, s, SP, n,
-                       FOLD ? (const double*)c->wh : (const double*)nullptr, (double*)c->mm_vi);
+    hipLaunchKernelGGL(multi_operand_kernel, dim3((unsigned)((n * sp + 255) / 256)), dim3(256), 0, c->stream, V, s, sp, n,
+                       fold ? (const double*)c->wh : (const double*)nullptr, (double*)c->mm_vi);
     CGLB_LAUNCH_CHECK(c);
-    using T = double;
-    CGLB_DISPATCH_PREC(c, hipLaunchKernelGGL((kff_multi_kernel<KIND, DP, R, SP, PREC>), dim3(nwg), dim3(256), 0, c->stream, (const double*)c->Xh,
-                                             (const double*)c->xah, V, s, (const double*)c->mm_vi, (const double*)c->wh, n, chunk, Q, nrb,
-                                             (const int2*)c->mm_list.dev, prow_ld, Prow, Pcol, (const double*)c->exp_tab, c->m32_bias));
-    CGLB_LAUNCH_CHECK(c);
-    if (skip_combine) return CGLB_OK;
-    hipLaunchKernelGGL(kff_multi_combine_kernel, dim3((unsigned)((n + 63) / 64), (unsigned)s), dim3(256), 0, c->stream, (const double*)Prow, nspan, prow_ld,
-                       (const double*)Pcol, n, span, RBROWS, SP, c->var, c->noise, V, Out);
+    geo->span = span; geo->chunk = chunk; geo->prow_ld = prow_ld;
+    geo->Q = Q; geo->nwg = nwg; geo->nrb = nrb; geo->nspan = nspan;
+    geo->Prow = (double*)c->mm_part;
+    geo->Pcol = geo->Prow + (size_t)nspan * prow_ld * sp;
+    return CGLB_OK;
+}
+
+int multi_combine(cglb_ctx* c, const multi_geometry& geo, int rbrows, int sp, const double* V, int s, double* Out) {
+    hipLaunchKernelGGL(kff_multi_combine_kernel, dim3((unsigned)((c->N + 63) / 64), (unsigned)s), dim3(256), 0, c->stream, (const double*)geo.Prow, geo.nspan,
+                       geo.prow_ld, (const double*)geo.Pcol, c->N, geo.span, rbrows, sp, c->var, c->noise, V, Out);
     CGLB_LAUNCH_CHECK(c);
     return CGLB_OK;
 }
 
-// the shared-kernel product exists for: fp64, Dp <= 32, unclamped exponent range, the symmetric variant, one rank owning every row
-bool kff_multi_native(const cglb_ctx* c) {
-    return c->dtype == CGLB_F64 && !is_wide(c) && !c->exp_clamp && c->kff_variant == 2 && c->par_world == 1 && !c->comm && c->r0 == 0 && c->r1 == c->N;
+template <int KIND, int DP, int SP>
+static int kff_multi_generic(cglb_ctx* c, const double* V, int s, double* Out, bool skip_combine) {
+    constexpr int R = multi_rows_per_lane(DP, SP);
+    constexpr int RBROWS = 64 * R;
+    multi_geometry geo;
+    CGLB_TRY(multi_prepare(c, V, s, SP, RBROWS, pair_fold<KIND, false>(), &geo));
+    using T = double;
+    CGLB_DISPATCH_PREC(c, hipLaunchKernelGGL((kff_multi_kernel<KIND, DP, R, SP, PREC>), dim3(geo.nwg), dim3(256), 0, c->stream, (const double*)c->Xh,
+                                             (const double*)c->xah, V, s, (const double*)c->mm_vi, (const double*)c->wh, c->N, geo.chunk, geo.Q, geo.nrb,
+                                             (const int2*)c->mm_list.dev, geo.prow_ld, geo.Prow, geo.Pcol, (const double*)c->exp_tab, c->m32_bias));
+    CGLB_LAUNCH_CHECK(c);
+    if (skip_combine) return CGLB_OK;
+    return multi_combine(c, geo, RBROWS, SP, V, s, Out);
 }
 
-// Out[b] = (K_ff + noise I) V[b], b < s; V, Out: [s][N] (column b contiguous).  Groups of up to 8 columns through the shared-kernel product,
-// a single left-over column and every context outside its scope through the single mat-vec.
+// the shared-kernel product exists for fp64, the symmetric variant, one rank owning every row, and: Dp <= 32 with the unclamped exponent
+// range; 32 < D <= 96 with the register-resident operand set (mid_reg), both ranges, at the widths that have an instance (multi_mid_group)
+bool kff_multi_native(const cglb_ctx* c) {
+    if (c->dtype != CGLB_F64 || c->kff_variant != 2 || c->par_world != 1 || c->comm || c->r0 != 0 || c->r1 != c->N) return false;
+    if (!is_wide(c)) return !c->exp_clamp;
+    return mid_reg(c) && multi_mid_group(c->Dh) >= 2;
+}
+
+// Out[b] = (K_ff + noise I) V[b], b < s; V, Out: [s][N] (column b contiguous).  Groups of up to 8 columns (mid widths: multi_mid_group) through
+// the shared-kernel product, a single left-over column and every context outside its scope through the single mat-vec.
 int launch_kff_matmat(cglb_ctx* c, const void* V, int s, void* Out) {
     const size_t stride = (size_t)c->N * c->esz, ostride = (size_t)c->nloc * c->esz;
     if (!kff_multi_native(c)) {
@@ -335,12 +350,15 @@ int launch_kff_matmat(cglb_ctx* c, const void* V, int s, void* Out) {
         return CGLB_OK;
     }
     c->pwh_src = nullptr;  // the weighted copy a PCG update may have left belongs to no operand of this product
-    for (int b0 = 0; b0 < s; b0 += 8) {
-        const int sg = std::min(8, s - b0);
+    const bool mid = is_wide(c);
+    const int group = mid ? multi_mid_group(c->Dh) : MULTI_GROUP_NARROW;
+    for (int b0 = 0, sg = 0; b0 < s; b0 += sg) {
+        sg = multi_next_group(s - b0, group);
         const double* Vg = (const double*)V + (size_t)b0 * c->N;
         double* Og = (double*)Out + (size_t)b0 * c->N;
         if (sg == 1) { CGLB_TRY(launch_kff_matvec(c, Vg, Og, nullptr)); continue; }
-        const int sp = sg <= 2 ? 2 : (sg <= 4 ? 4 : 8);
+        if (mid) { CGLB_TRY(launch_kff_multi_mid(c, Vg, sg, Og)); continue; }
+        const int sp = multi_group_pad(sg);
         const bool skip = c->kff_skip_combine;
         CGLB_DISPATCH_KIND(c->kind, CGLB_DISPATCH_DP(c->Dp, {
             if (sp == 2) CGLB_TRY((kff_multi_generic<KIND, DP, 2>(c, Vg, sg, Og, skip)));

@@ -467,12 +467,44 @@ __global__ __launch_bounds__(256) void wide_kus_kernel(const T* __restrict__ Zs,
     }
 }
 
-// out[m * ld + n] = var * K(z_m, xnew_n)   (models.py:337)
-int wide_kus(cglb_ctx* c, const void* XsNew, int64_t n_new, int64_t ld, void* out) {
-    const dim3 grid((unsigned)((n_new + 3) / 4), (unsigned)((c->M + 31) / 32));
-    CGLB_DISPATCH_T(c->dtype, CGLB_DISPATCH_KIND(c->kind, hipLaunchKernelGGL((wide_kus_kernel<T, KIND>), grid, dim3(256), 0, c->stream, (const T*)c->Zs,
-                                                                             (const T*)XsNew, n_new, ld, c->M, c->D, (T)c->var, (T*)out)));
+// out[m * ld + n] = var * K(z_m, xnew_n) for any two sets in plain scaled units: M rows Zs against n_new rows XsNew
+int wide_kpanel(cglb_ctx* c, const void* Zs, int M, const void* XsNew, int64_t n_new, int64_t ld, void* out) {
+    if (M == 0 || n_new == 0) return CGLB_OK;
+    const dim3 grid((unsigned)((n_new + 3) / 4), (unsigned)((M + 31) / 32));
+    CGLB_DISPATCH_T(c->dtype, CGLB_DISPATCH_KIND(c->kind, hipLaunchKernelGGL((wide_kus_kernel<T, KIND>), grid, dim3(256), 0, c->stream, (const T*)Zs,
+                                                                             (const T*)XsNew, n_new, ld, M, c->D, (T)c->var, (T*)out)));
     CGLB_LAUNCH_CHECK(c);
+    return CGLB_OK;
+}
+
+// out[m * ld + n] = var * K(z_m, xnew_n)   (models.py:337)
+int wide_kus(cglb_ctx* c, const void* XsNew, int64_t n_new, int64_t ld, void* out) { return wide_kpanel(c, c->Zs, c->M, XsNew, n_new, ld, out); }
+
+// Multi-column cross product of wide inputs (the cached predictive variance of the iterative exact GP class): per tile the Gram GEMM, the
+// kernel profile in place, then one GEMM of the tile against the matching rows of Vi, accumulated over the column tiles.  Vi [N][ldv]
+// row-major is column-major ldv x N; out [nrows][ldo] row-major is column-major ldo x nrows: out^T = Vi_J^T K_IJ^T.
+int wide_cross_multi(cglb_ctx* c, const void* XsRow, const void* xaRow, int64_t nrows, const double* Vi, int64_t ldv, int S, double* out, int64_t ldo) {
+    if (c->dtype != CGLB_F64) return cglb_fail(c, CGLB_ERR_BAD_ARG, "the multi-column cross product needs an fp64 context");
+    if (nrows == 0) return CGLB_OK;
+    if (S < 1 || S > ldv || S > ldo) return cglb_fail(c, CGLB_ERR_BAD_ARG, "the multi-column cross product needs 1 <= S <= both leading dimensions");
+    using T = double;
+    const int64_t N = c->N;
+    CGLB_TRY(c->mem.reserve(c, &c->wtile, &c->wtile_cap, (size_t)TILE * TILE * sizeof(T)));
+    T* G = (T*)c->wtile;
+    CGLB_DISPATCH_KIND(c->kind, {
+        for (int64_t i0 = 0; i0 < nrows; i0 += TILE) {
+            const int64_t nr = std::min(TILE, nrows - i0);
+            for (int64_t j0 = 0; j0 < N; j0 += TILE) {
+                const int64_t nc = std::min(TILE, N - j0);
+                CGLB_TRY(gram_tile<T>(c, (const T*)XsRow + i0 * c->D, nr, (const T*)c->Xs + j0 * c->D, nc, G, nr));
+                hipLaunchKernelGGL((wide_profile_kernel<T, KIND, 0>), dim3((unsigned)((nr + 255) / 256), (unsigned)nc), dim3(256), 0, c->stream, G, nr, nr, nc,
+                                   (const T*)xaRow + i0, (const T*)c->xa + j0, (T)c->var, (T)0);
+                CGLB_LAUNCH_CHECK(c);
+                BLAS_CHECK(c, wgemm(c->blas, rocblas_operation_none, rocblas_operation_transpose, S, (int)nr, (int)nc, 1.0, Vi + j0 * ldv, (int)ldv, (const T*)G, (int)nr,
+                                    j0 > 0 ? 1.0 : 0.0, out + i0 * ldo, (int)ldo));
+            }
+        }
+    });
     return CGLB_OK;
 }
 

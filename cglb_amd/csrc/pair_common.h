@@ -25,6 +25,7 @@ __device__ __forceinline__ T pair_row_seed(T a, T bias) {
     return (KIND == CGLB_RBF) ? a : (BIASED ? T(-0.5) * (a + bias) : T(-0.5) * a);
 }
 
+#define MULTI_CS_MAX 1024  // multi-column product (kernels_kff_multi.hip, kernels_kff_multi_mid.hip): column sums a wave stages in LDS (columns of a chunk x S_pad)
 #define PAIR_TR_LD 65  // leading dimension of a wave's 8 x 64 transposition scratch (odd: the column reads spread over the banks)
 // Sums ACROSS the 64 lanes of the 8 per-lane partials t8[0..7] (8 columns of a batch); every lane returns the sum of column lane & 7.
 // Transposed through LDS: every lane writes its 8 partials (row jj of `tr`, stride PAIR_TR_LD: conflict-free), then lane (c = lane & 7,

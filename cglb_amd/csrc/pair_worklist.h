@@ -60,3 +60,21 @@ static std::vector<pair_unit> pair_work_order(int ngroups, int nunits, F first_u
     if (list.empty()) list.push_back({-1, -1});  // keeps the device allocation non-empty
     return list;
 }
+
+// Group width of the multi-column K_ff product (kernels_kff_multi.hip, kernels_kff_multi_mid.hip): a product of s columns is cut into groups
+// of at most `group` columns, each padded to S_pad = 2, 4 or 8 right-hand sides, and a single left-over column goes through the mat-vec.
+//   narrow widths (Dp <= 32): groups of 8.
+//   mid widths (hot width Dh = 48, 64, 80, 96; one row per lane, the row operand alone fills 2 Dh VGPRs): the widest S_pad whose
+//   instances compile without a spill (DESIGN.md section 4b has the registers of every instance); 0 = no instance, the product falls
+//   back to single mat-vecs.  Every width holds 8: up to 80 inside the 256 VGPRs of two waves per SIMD (at 64 with S_pad 8, and at 80,
+//   with 8 instead of 16 per-lane partials), at 96 as one wave per SIMD with 14 - 42 values in the accumulation registers.
+#define MULTI_GROUP_NARROW 8
+static constexpr int multi_mid_group(int dh) { return (dh == 48 || dh == 64 || dh == 80 || dh == 96) ? 8 : 0; }
+// per-lane partial column sums of a batch at a mid width (16 as in the narrow kernel, 8 where 16 do not fit); 0 = not instantiated
+static constexpr int multi_mid_partials(int dh, int sp) {
+    if (sp < 2 || sp > multi_mid_group(dh) || (sp & (sp - 1)) != 0) return 0;
+    return (dh <= 48 || (dh <= 64 && sp <= 4)) ? 16 : 8;
+}
+static constexpr int multi_group_pad(int sg) { return sg <= 2 ? 2 : (sg <= 4 ? 4 : 8); }  // S_pad of a group of sg columns
+// columns of the next group when `left` columns remain and groups hold at most `group` (>= 2): 1 = the single left-over column
+static constexpr int multi_next_group(int left, int group) { return left < group ? left : group; }

@@ -232,7 +232,8 @@ int cglb_dist_predict(cglb_ctx* ctx, const void* v_full, const void* xnew, int64
  * these calls the single-column code (bit-identical results).
  * Batched PCG: the P columns are P independent recurrences (conjugate_gradient.py:41-86 per column) with their own
  * gamma_b = rz_b / pAp_b and beta_b = rz_b' / rz_b, advancing in lockstep over ONE product K_ff P[N, P] per iteration that evaluates every
- * kernel value once for up to 8 columns (fp64, d <= 32, unclamped exponent range, kff_variant 2; otherwise s single mat-vecs).  One
+ * kernel value once for up to 8 columns (fp64, kff_variant 2, and either d <= 32 with the unclamped exponent range or 32 < d <= 96 with
+ * "wide_reg" 1, both ranges; otherwise s single mat-vecs - cglb_get_stat "matmat_native" tells which).  One
  * stop test before every iteration: 1/2 sum_b r_b^T P r_b <= max_error or steps == max_cg_iter (the sum is the gap upper - lower of the
  * summed bound); the restart rule applies to all columns at once; pAp_b == 0 gives gamma_b = 0 and rz_b == 0 gives beta_b = 0 (a column
  * that is exactly converged or all zero stays finite and leaves the others unchanged). */
@@ -303,12 +304,13 @@ int cglb_itergp_get_coefficients(cglb_ctx* ctx, double* rz_log, double* pap_log)
 /* predict_f: f_mean = mean + K_*f alpha with alpha = K^-1 e solved to max_error (warm-started at the alpha of the last evaluation at the current
  * data and hyper-parameters; without one the preconditioner is built first), f_var = variance - k_*^T K^-1 k_* by batched solves on the columns
  * of K_f*, 8 new points at a time (each to 1/2 sum_b r_b^T P^-1 r_b <= max_error): n_new / 8 solves.  The Lanczos variance cache below
- * (cglb_itergp_var_cache, cglb_itergp_predict_cached) is the opt-in that replaces these solves.  xnew: any [n_new, d], d <= 32; f_mean, f_var:
- * dev [n_new]. */
+ * (cglb_itergp_var_cache, cglb_itergp_predict_cached) is the opt-in that replaces these solves.  xnew: any [n_new, d]; f_mean, f_var:
+ * dev [n_new].  Any input width: beyond 32 dimensions the right-hand sides come from the wide operand set, and the batched solves run on the
+ * shared-kernel product up to 96 dimensions and on single mat-vecs beyond. */
 int cglb_itergp_predict(cglb_ctx* ctx, const void* xnew, int64_t n_new, double max_error, int max_cg_iter, void* f_mean, void* f_var);
 /* Lanczos variance cache: what the reference's exact-GP metrics get from gpytorch.settings.fast_pred_var() (pytorch/interface.py:582) - a low-rank
  * approximation of K^-1 built once and applied to every new point.  gpytorch's start vector is not reproduced; the estimator is defined here and
- * pinned to tests/love_ref.py.  Scope of cglb_itergp_predict (fp64, one rank, one target column, d <= 32; else CGLB_ERR_BAD_ARG).
+ * pinned to tests/love_ref.py.  Scope of cglb_itergp_predict (fp64, one rank, one target column, any input width; else CGLB_ERR_BAD_ARG).
  *   Lanczos  on K = variance kappa(X, X) + noise I with full reorthogonalisation, started at q_0 = e / |e|, e = y - mean (CGLB_ERR_STATE if e = 0):
  *            w = K q_j (the context's own mat-vec), alpha_j = q_j^T w, two passes w <- w - Q (Q^T w) over all columns so far, beta_j = |w|;
  *            stop with J = j + 1 columns when j + 1 = rank or beta_j <= 1e-10 alpha_0 (the Krylov space has closed: with an RBF kernel K has
@@ -323,12 +325,13 @@ int cglb_itergp_predict(cglb_ctx* ctx, const void* xnew, int64_t n_new, double m
  * cglb_select_inducing invalidate the cache. */
 int cglb_itergp_var_cache(cglb_ctx* ctx, int rank, int* rank_out);
 /* cglb_itergp_predict with the variance from the cache: f_mean as there (the same solve for alpha, the same product), f_var from one
- * multi-column product K_*f R (cglb_cross_matmat's kernel) and the row norms of the result.  CGLB_ERR_STATE without a valid cache. */
+ * multi-column product K_*f R (cglb_cross_matmat's kernel; beyond 32 input dimensions the Gram tiles of csrc/kernels_wide.hip: Gram GEMM, kernel
+ * profile in place and one GEMM of the tile against the matching cache rows) and the row norms of the result.  CGLB_ERR_STATE without a valid cache. */
 int cglb_itergp_predict_cached(cglb_ctx* ctx, const void* xnew, int64_t n_new, double max_error, int max_cg_iter, void* f_mean, void* f_var);
 /* The product of the cached predictive on its own (tests, timing): out[i, s] = variance sum_j kappa(xnew_i, x_j) V[s, j].  xnew: any [n_new, d];
  * V: dev [S, n_total], column s contiguous (the convention of cglb_grad_kff_multi); out: dev [n_new, S] row-major.  Every kernel value is
  * evaluated once per group of 8 columns (csrc/kernels_cross_multi.hip); always the range-clamped 2^x; bitwise reproducible.  Scope of
- * cglb_itergp_predict_cached. */
+ * cglb_itergp_predict_cached, and d <= 32: this is the entry of the register-resident kernel (CGLB_ERR_BAD_ARG on wider inputs). */
 int cglb_cross_matmat(cglb_ctx* ctx, const void* xnew, int64_t n_new, const void* V, int S, void* out);
 /* average duration (ms) of `reps` back-to-back products with S > 0 columns (operand interleave, pair kernel and fixed-order sum of every group, on
  * the context stream) at the first n_new training rows as new points (n_new <= n_total), beside cglb_time_grad_kff_multi; S < 0 times the
@@ -367,6 +370,8 @@ int cglb_time_kernel(cglb_ctx* ctx, int which, int reps, double* ms_avg);
  * "k1_launches" return the accumulated device time and launch count since then (the call synchronises with the pending launches).
  * "k1_pairs_per_launch": kernel pairs one launch of that kernel evaluates with the current geometry (~N(N+256)/2 on one GPU: the
  * symmetric form visits each unordered pair once) - the unit count of the roofline; "kpart_bytes": size of the partial-sum slabs;
+ * "matmat_native": 1 if a product of two or more columns (cglb_matmat, the batched solves) on this context in its current state - data, dtype,
+ * hyper-parameters, "wide_reg", "kff_variant", ranks - runs through a shared-kernel instance, 0 if it falls back to single mat-vecs;
  * after cglb_set_option(ctx, "eval_profile", 1): "eval_setup_ms" | "eval_pcg_ms" | "eval_final_ms" | "eval_grad_ms" = device time (HIP events on
  * the context stream) accumulated over the phases of every cglb_objective_and_grad / cglb_dist_objective_and_grad /
  * cglb_objective_and_grad_multi since - common terms | PCG | final mat-vec, preconditioner and bound scalars | gradient - and "eval_count" =
