@@ -2074,6 +2074,11 @@ int cglb_get_stat(cglb_ctx* c, const char* name, double* value) {
         if (rc != -1) return rc;
     }
     if (!strcmp(name, "matmat_native")) { *value = (c->have_data && kff_multi_native(c)) ? 1.0 : 0.0; return CGLB_OK; }  // shared-kernel instance or single mat-vecs
+    if (!strcmp(name, "exp_clamp") || !strcmp(name, "m32_bias")) {  // the exponent-range regime of the last cglb_set_hypers
+        if (!c->have_hypers) return cglb_fail(c, CGLB_ERR_STATE, "set_hypers must precede this statistic");
+        *value = !strcmp(name, "exp_clamp") ? (c->exp_clamp ? 1.0 : 0.0) : c->m32_bias;
+        return CGLB_OK;
+    }
     if (!strcmp(name, "k1_pairs_per_launch")) { *value = c->sym_pairs; return CGLB_OK; }  // of the most recent symmetric launch geometry
     if (!strcmp(name, "kpart_bytes")) { *value = (double)c->kpart_cap; return CGLB_OK; }     // partial-sum slabs of the mat-vec
     if (!strcmp(name, "comm_allreduce_calls")) { *value = c->comm ? (double)c->comm->n_allreduce : 0.0; return CGLB_OK; }

@@ -88,10 +88,17 @@ __device__ __forceinline__ double sqrt_pos(double x) {
 __device__ __forceinline__ float sqrt_pos(float x) { return __builtin_sqrtf(fmaxf(x, 0.0f)); }
 
 // ---- precision levels of the pair kernels (cglb_set_option "precision") ------------------------------------------------------
+// The figures below are those of the EVALUATOR (table, polynomial, square root) for the squared distance it is handed.  A kernel value of a
+// Gram-form pass carries, at every level, the cancellation error of that distance on top - (5 D + 3) u max(a_i, a_j), derived at
+// CGLB_M32_BIAS_* below - which is absolute in the exponent: relative to the value it grows with the exponent range of the data, up to
+// (ln2 / 4) (5 D + 3) u oct for RBF (oct as in cglb_set_hypers): 3e-12 at D = 32, oct = 931 (measured on an MI355X: 2.2e-13 at EXACT and FAST
+// alike), 9e-12 at D = 77, oct = 1200 in the mid-width instances, whose two interleaved chains add three roundings (measured 1.4e-12).
+// DESIGN.md section 2 has the per-element measurements (tests/test_gpu_kernel_values.py).
 //   CGLB_PREC_EXACT (0): degree-4 table polynomial + two-step square root: kernel values to ~3e-16 (1.5 ulp)
 //   CGLB_PREC_FAST  (1): degree-3 polynomial (3.5e-14) + one-step square root (2.1e-14 on r): kernel values to <= ~1e-13 relative.
-//                        Matern-5/2 at FAST: the root's 2.1e-14 through |dkappa/dr| r = s^2 (1 + s) e^-s / 3 <= 0.62 gives 1.3e-14 (of f), plus the
-//                        polynomial's 3.5e-14: <= ~5e-14, inside the same 1e-13.
+//                        Matern-5/2 at FAST: matern_kpoly_hot takes the quadratic term from d2, so the root's 2.1e-14 enters through the linear
+//                        term and the exponent only, (s^2 + s^3 / 3) e^-s <= 0.94 (the closed form's s^2 (1 + s) e^-s / 3 <= 0.62 would hold if
+//                        the quadratic term followed the root): 2.0e-14 (of f), plus the polynomial's 3.5e-14: <= ~6e-14, inside the same 1e-13.
 // north_star asks for 1e-6 on the bound; FAST is the default (one fma per pair less, two for Matern-3/2).  Every fp64 instruction
 // of the pair stream is ~5 % of the mat-vec (the kernels are bound by vector-fp64 issue).
 #define CGLB_PREC_EXACT 0

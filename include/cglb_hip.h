@@ -372,6 +372,10 @@ int cglb_time_kernel(cglb_ctx* ctx, int which, int reps, double* ms_avg);
  * symmetric form visits each unordered pair once) - the unit count of the roofline; "kpart_bytes": size of the partial-sum slabs;
  * "matmat_native": 1 if a product of two or more columns (cglb_matmat, the batched solves) on this context in its current state - data, dtype,
  * hyper-parameters, "wide_reg", "kff_variant", ranks - runs through a shared-kernel instance, 0 if it falls back to single mat-vecs;
+ * "exp_clamp" | "m32_bias": the exponent-range regime the last cglb_set_hypers chose from the data's per-column range and the lengthscales
+ * (CGLB_ERR_STATE before one) - 1 if the pair kernels run their range-clamped instances (kernel values below 2^-1000 come out as that floor,
+ * not 0), 0 for the unclamped ones | the positivity bias of the Matern squared distance in hot units^2 (0 for RBF; above 2e-8 the clamped
+ * instances run and the bias is not applied).  Read-only; for tests that must show which instance a configuration ran;
  * after cglb_set_option(ctx, "eval_profile", 1): "eval_setup_ms" | "eval_pcg_ms" | "eval_final_ms" | "eval_grad_ms" = device time (HIP events on
  * the context stream) accumulated over the phases of every cglb_objective_and_grad / cglb_dist_objective_and_grad /
  * cglb_objective_and_grad_multi since - common terms | PCG | final mat-vec, preconditioner and bound scalars | gradient - and "eval_count" =
@@ -390,8 +394,18 @@ int cglb_get_stat(cglb_ctx* ctx, const char* name, double* value);
 /* Tunables: name = "kff_variant" | "kff_jsplit" | "kff_rows" | "sym_chunk" | "precond_mode" | "chol_mode" | "pcg_lookahead" | "sym_order" | "aat_block" | "grad_gram" | "k1_profile" |
  * "grad_trsm" (gradient algebra against L = chol(K_uu): 0 products with the explicit inverse, 1 backward-stable triangular solves, 2 = default:
  *  the products followed by one step of iterative refinement against L - the accuracy of the solves for about two thirds of their time) |
- * "precision" (1, default: kernel values to <= 1e-13 relative - degree-3 table polynomial, one-step square root; 0: ~3e-16; 2: opt-in, degree-2
- *  polynomial, kernel values to ~1e-10 - inside the 1e-6 the bound needs, one instruction per pair cheaper) ...;
+ * "precision" (the EVALUATOR of a kernel value - 2^x, square root, polynomial factor - given the squared distance it is handed: 1, default:
+ *  <= 1e-13 relative - degree-3 table polynomial, one-step square root; 0: ~3e-16; 2: opt-in, degree-2 polynomial, ~1e-10 - inside the 1e-6
+ *  the bound needs, one instruction per pair cheaper.  This is not the whole error of a kernel value: every N^2 product forms the squared
+ *  distance in Gram form, |x_i|^2 + |x_j|^2 - 2 x_i.x_j on the centred, scaled inputs, whose rounding error is ABSOLUTE in the exponent -
+ *  up to (5 d + 3) 2^-53 max(|x_i|^2, |x_j|^2) (csrc/devmath.h).  With R the exponent range of the data in octaves (RBF: 2 sum_k (range_k /
+ *  l_k)^2 log2 e, range_k the largest deviation of column k from its mean) a kernel value moves by up to (ln2 / 4) (5 d + 3) 2^-53 R of
+ *  itself (RBF; the Matern kinds: (ln2)^2 / 2 (5 d + 3) 2^-53 sum_k (sqrt(2 nu) range_k / l_k)^2 log2e^2 of the variance), at every level:
+ *  3e-12 at d = 32 and R = 931, the widest range the unclamped kernels take (measured 2.2e-13), 9e-12 at d = 77 and R = 1200 (measured
+ *  1.4e-12), below 1e-14 where R (5 d + 3) < 500.  Pairs near the centre of the data see their own, smaller norms.  The unclamped Matern
+ *  instances of levels 1 and 2 add the positivity bias, at most 3e-13 of the variance on a coincident pair.  The direct-difference passes
+ *  (cglb_select_inducing, K_uu and K_uf of inputs up to 32 dimensions, cglb_grad_kff_multi up to 32 dimensions) have no such term.
+ *  tests/kernel_value_cases.py derives the bound of one value term by term; tests/test_gpu_kernel_values.py holds every fp64 product to it) ...;
  * "pcg_lookahead" (0: the host waits for the stop statistic before enqueuing anything; 1, default: the next mat-vec is enqueued first while
  *  1/2 r^T P r of the previous iteration exceeds 32 x max_error; k >= 2: that factor - a mis-speculated mat-vec is wasted work, never a wrong result) |
  * "final_matvec" (cglb_objective_and_grad after a solve: 1 recomputes K v with a mat-vec like models.py:280; 0, the default, takes K v = e - r

@@ -22,7 +22,8 @@ Tolerance of an instance (case, kind, dtype), `tol(inst)`:
     tolerance is therefore 6 times the measured round-off, not 4; DESIGN.md lists measured and stored values side by side;
     The margin of 4: the kernel sums the dot product in eight interleaved fma chains and rounds sqrt / division differently from numpy - an
     error of the same order, not the same number;
-  * kernel-value term, fp64: variance * 1e-13, the relative kernel-value error include/cglb_hip.h states for the default "precision" level;
+  * kernel-value term, fp64: variance * 1e-13, the relative error include/cglb_hip.h states for the evaluator at the default "precision" level.
+    The selection kernel takes direct differences (kappa_from_d2), so the Gram-form term that header adds for the N^2 products does not apply;
   * kernel-value term, fp32: the largest difference between the float32 restatement's kernel columns and the fp64 oracle's on the rounded inputs,
     stored per instance in `KV32` the same way (units of eps_32 * variance, same bracket, the same factor 1.5).
 
