@@ -108,6 +108,10 @@ SIGNATURES = {
     "cglb_itergp_predict_cached": (c_int, [c_void_p, c_void_p, c_int64, c_double, c_int, c_void_p, c_void_p]),
     "cglb_cross_matmat": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int, c_void_p]),
     "cglb_time_cross_matmat": (c_int, [c_void_p, c_int64, c_int, c_int, POINTER(c_double)]),
+    "cglb_feature_matmat": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p]),
+    "cglb_time_feature_matmat": (c_int, [c_void_p, c_int64, c_int64, c_int, c_int, POINTER(c_double)]),
+    "cglb_itergp_sample": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_double, c_int, c_void_p, c_void_p,
+                                   POINTER(c_int), POINTER(c_double)]),
     "cglb_grad_kff_multi": (c_int, [c_void_p, c_void_p, c_void_p, c_int, POINTER(c_double)]),
     "cglb_time_grad_kff_multi": (c_int, [c_void_p, c_int, c_int, POINTER(c_double)]),
 }

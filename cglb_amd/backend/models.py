@@ -21,7 +21,8 @@ from torch import nn
 from torch.nn import functional as F
 
 from ..dist_context import make_context
-from ..hip_context import HipContext
+from .. import _lib
+from ..hip_context import KINDS, HipContext
 from .conjugate_gradient import ConjugateGradient, ConjugateGradientStats, KernelOperator, NystromPreconditioner
 
 Tensor = torch.Tensor
@@ -704,6 +705,61 @@ class PredictIterGPR(_Predict):
         if self.var_rank > 0:
             return self.model.hip.itergp_predict(xnew, self.max_error, self.model.max_cg_iter, var_rank=min(self.var_rank, self.model.hip.N, 1024))
         return self.model.hip.itergp_predict(xnew, self.max_error, self.model.max_cg_iter)
+
+
+_FEATURE_NU = {_lib.RBF: None, _lib.MATERN32: 1.5, _lib.MATERN52: 2.5}   # by the library's kind; the names: hip_context.KINDS
+
+
+def feature_draws(kind: str, d: int, F: int, generator: torch.Generator):
+    """The raw draws behind `draw_features`, in its order: z [F, d] standard normal, chi2 [F] (one chi-square draw of 2 nu degrees of freedom
+    per feature as the sum of 2 nu squared normals; None for RBF), u [F] uniform on [0, 1)."""
+    nu = _FEATURE_NU[KINDS[kind]]
+    z = torch.randn(F, d, dtype=torch.float64, generator=generator)
+    chi2 = None if nu is None else torch.randn(F, int(2 * nu), dtype=torch.float64, generator=generator).square().sum(dim=1)
+    u = torch.rand(F, dtype=torch.float64, generator=generator)
+    return z, chi2, u
+
+
+def draw_features(kind: str, d: int, F: int, generator: torch.Generator) -> Tuple[Tensor, Tensor]:
+    """(omega [F, d], b [F]) of F random Fourier features of the unit-lengthscale kernel `kind` ("rbf" | "matern32" | "matern52"), from a
+    torch.Generator on the CPU: omega from the kernel's spectral measure - standard normal rows for RBF; for Matern-nu the multivariate
+    Student-t with 2 nu degrees of freedom, z sqrt(2 nu / chi2_{2 nu}) with one chi-square draw per feature - and b uniform on [0, 2 pi), so that
+    (2 / F) sum_j cos(omega_j . x + b_j) cos(omega_j . x' + b_j) -> kappa(x, x')."""
+    nu = _FEATURE_NU[KINDS[kind]]
+    z, chi2, u = feature_draws(kind, d, F, generator)
+    omega = z if nu is None else z * torch.sqrt(2.0 * nu / chi2).reshape(-1, 1)
+    return omega, 2.0 * math.pi * u
+
+
+class SampleIterGPR(nn.Module):
+    """predict_f_samples of the iterative model: `SampleIterGPR(model)(xnew, num_samples)` -> [num_samples, n_new, 1] joint draws of the
+    posterior of f at xnew by pathwise conditioning (cglb_itergp_sample): a random-Fourier-feature prior draw of `num_features` features,
+    corrected through one batched solve at `max_error` with the class's preconditioner.  O(N) memory.  The draws are exact for the
+    `num_features`-feature approximation of the prior (their mean is the exact predictive mean); the spread carries that approximation's
+    O(1 / sqrt(num_features)) covariance error.  Frequencies, phases, weights and noise draws come from `model.generator`; with
+    `fixed_features` the frequencies and phases are drawn once, here, and successive calls share that prior basis."""
+
+    def __init__(self, model: IterGPR, num_features: int = 1024, max_error: float = 1e-3, fixed_features: bool = False):
+        if not isinstance(model, IterGPR):
+            raise ValueError(f"IterGPR model expected in the constructor of the {self.__class__}")
+        super().__init__()
+        object.__setattr__(self, "model", model)
+        self.num_features, self.max_error = int(num_features), float(max_error)
+        self.features = self._draw() if fixed_features else None
+
+    def _draw(self):
+        model = self.model
+        return draw_features(model.covar_module.base_kernel.kind, model.hip.D, self.num_features, model.generator)
+
+    def forward(self, xnew: Tensor, num_samples: int = 1) -> Tensor:
+        model, S = self.model, int(num_samples)
+        with torch.no_grad():
+            omega, b = self._draw() if self.features is None else self.features
+            W = torch.randn(S, self.num_features, dtype=torch.float64, generator=model.generator)
+            eps = torch.randn(S, model.hip.N, dtype=torch.float64, generator=model.generator)
+            model.push_hypers(get_cholesky_jitter())
+            res = model.hip.itergp_sample(xnew, omega, b, W, eps, self.max_error, model.max_cg_iter)
+        return res.samples.reshape(S, -1, 1)
 
 
 class _PredictLogdensity:

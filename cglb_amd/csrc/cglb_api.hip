@@ -1060,6 +1060,18 @@ int itergp_stat(cglb_ctx* c, const char* name, double* value) {
         return CGLB_OK;
     }
     if (!strcmp(name, "itergp_cache_request")) { *value = (double)c->it_cache_request; return CGLB_OK; }  // 0: no valid cache
+    // "feature_ms": device time of the last feature product (pair kernel and slab sums of every group; not the operand records) of
+    // cglb_feature_matmat or cglb_itergp_sample
+    if (!strcmp(name, "feature_ms")) {
+        *value = 0.0;
+        if (c->ft_ev_set) {
+            float ms = 0.f;
+            HIP_CHECK(c, hipEventSynchronize(c->ft_ev[1]));
+            HIP_CHECK(c, hipEventElapsedTime(&ms, c->ft_ev[0], c->ft_ev[1]));
+            *value = ms;
+        }
+        return CGLB_OK;
+    }
     return -1;
 }
 
@@ -1215,6 +1227,43 @@ int require_cross_multi_ok(cglb_ctx* c) {
     return CGLB_OK;
 }
 
+// ---- pathwise posterior samples (cglb_itergp_sample) and the feature product under them (kernels_feature_multi.hip) ----
+// B[s][i] = (y_i - mean) - G[i][s] - sn eps[s][i]: the right-hand sides of Matheron's rule, G row-major [n][S]
+__global__ __launch_bounds__(256) void sample_rhs_kernel(const double* __restrict__ y, double mean, const double* __restrict__ G, const double* __restrict__ eps,
+                                                         double sn, int64_t n, int S, double* __restrict__ B) {
+    const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= n * S) return;
+    const int64_t s = idx / n, i = idx - s * n;
+    B[idx] = ((y[i] - mean) - G[i * S + s]) - sn * eps[idx];
+}
+// f[s][i] = (mean + G[i][s]) + KU(i, s), KU(i, s) at KU[i * ki + s * ks]
+__global__ __launch_bounds__(256) void sample_combine_kernel(double mean, const double* __restrict__ G, const double* __restrict__ KU, int64_t ki, int64_t ks,
+                                                             int64_t n, int S, double* __restrict__ f) {
+    const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= n * S) return;
+    const int64_t s = idx / n, i = idx - s * n;
+    f[idx] = (mean + G[i * S + s]) + KU[i * ki + s * ks];
+}
+
+// the feature product of one call between the two events of "feature_ms"
+int feature_product(cglb_ctx* c, const double* X, int64_t nrows, int64_t F, int S, double* out) {
+    for (int k = 0; k < 2; ++k)
+        if (!c->ft_ev[k]) HIP_CHECK(c, hipEventCreate(&c->ft_ev[k]));
+    c->ft_ev_set = false;
+    HIP_CHECK(c, hipEventRecord(c->ft_ev[0], c->stream));
+    CGLB_TRY(launch_feature_multi(c, X, nrows, F, S, out, S));
+    HIP_CHECK(c, hipEventRecord(c->ft_ev[1], c->stream));
+    c->ft_ev_set = true;
+    return CGLB_OK;
+}
+
+// dst[0 .. n) = src[0 .. m) repeated (operands of a timed launch: values do not change a branch-free instruction stream)
+int fill_cyclic(cglb_ctx* c, double* dst, int64_t n, const double* src, int64_t m) {
+    for (int64_t o = 0; o < n; o += m)
+        HIP_CHECK(c, hipMemcpyAsync(dst + o, src, (size_t)std::min(m, n - o) * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+    return CGLB_OK;
+}
+
 }  // namespace
 
 // =================================================== C ABI ====================================================
@@ -1305,6 +1354,7 @@ int cglb_ctx_destroy(cglb_ctx* c) {
     for (hipEvent_t ev : c->gpr_ev) if (ev) (void)hipEventDestroy(ev);
     for (hipEvent_t ev : c->it_ev) if (ev) (void)hipEventDestroy(ev);
     for (hipEvent_t ev : c->it_cev) if (ev) (void)hipEventDestroy(ev);
+    for (hipEvent_t ev : c->ft_ev) if (ev) (void)hipEventDestroy(ev);
     if (c->it_log.host_pap) (void)hipHostFree(c->it_log.host_pap);
     for (hipEvent_t ev : c->k1_events) (void)hipEventDestroy(ev);
     for (hipEvent_t ev : c->eval_events) (void)hipEventDestroy(ev);
@@ -2538,6 +2588,119 @@ int cglb_time_cross_matmat(cglb_ctx* c, int64_t n_new, int S, int reps, double* 
         return launch_cross_multi(c, c->Xh, c->xah, n_new, (const double*)c->cm_vi, ldv, s, (double*)out, s);
     }, ms_avg);
     (void)hipStreamSynchronize(c->stream);
+    return rc;
+}
+
+int cglb_feature_matmat(cglb_ctx* c, const void* x, int64_t n_rows, const void* omega, const void* phase, const void* W, int64_t F, int S, void* out) {
+    if (c) c->obj_valid = false;
+    if (!c || !omega || !phase || !W || !out || n_rows < 0 || F < 1 || S < 1) return c ? cglb_fail(c, CGLB_ERR_BAD_ARG, "bad argument") : CGLB_ERR_BAD_ARG;
+    CGLB_TRY(require_itergp_ok(c));
+    if (!x && n_rows != c->N) return cglb_fail(c, CGLB_ERR_BAD_ARG, "the feature product of the training rows (x NULL) has n_rows = n_total");
+    if (n_rows == 0) return CGLB_OK;
+    HIP_CHECK(c, hipSetDevice(c->device));
+    void* xr = nullptr;
+    DevTemps tmp;  // freed on every path below
+    if (x) CGLB_TRY(tmp.alloc(c, &xr, (size_t)n_rows * c->D * sizeof(double)));
+    auto body = [&]() -> int {
+        if (x) HIP_CHECK(c, hipMemcpyAsync(xr, x, (size_t)n_rows * c->D * sizeof(double), hipMemcpyDefault, c->stream));
+        CGLB_TRY(launch_feature_operand(c, omega, phase, W, F, S));
+        return feature_product(c, x ? (const double*)xr : (const double*)c->X, n_rows, F, S, (double*)out);
+    };
+    const int rc = body();
+    (void)hipStreamSynchronize(c->stream);  // before `tmp` releases the buffer the kernels use, and the caller its omega and phase
+    return rc;
+}
+
+int cglb_time_feature_matmat(cglb_ctx* c, int64_t n_rows, int64_t F, int S, int reps, double* ms_avg) {
+    if (c) c->obj_valid = false;
+    if (!c || !ms_avg || reps <= 0 || S < 1 || F < 1 || n_rows < 1) return c ? cglb_fail(c, CGLB_ERR_BAD_ARG, "bad argument") : CGLB_ERR_BAD_ARG;
+    CGLB_TRY(require_itergp_ok(c));
+    if (n_rows > c->N) return cglb_fail(c, CGLB_ERR_BAD_ARG, "the timed product takes its rows from the training rows: n_rows <= n_total");
+    HIP_CHECK(c, hipSetDevice(c->device));
+    void *om = nullptr, *ph = nullptr, *W = nullptr, *out = nullptr;
+    DevTemps tmp;
+    CGLB_TRY(tmp.alloc(c, &om, (size_t)F * c->D * sizeof(double)));
+    CGLB_TRY(tmp.alloc(c, &ph, (size_t)F * sizeof(double)));
+    CGLB_TRY(tmp.alloc(c, &W, (size_t)S * F * sizeof(double)));
+    CGLB_TRY(tmp.alloc(c, &out, (size_t)n_rows * S * sizeof(double)));
+    // operands: the training inputs as frequencies, the targets as phases and weights
+    const auto fill = [&]() -> int {
+        CGLB_TRY(fill_cyclic(c, (double*)om, F * c->D, (const double*)c->X, c->N * c->D));
+        CGLB_TRY(fill_cyclic(c, (double*)ph, F, (const double*)c->y, c->N));
+        return fill_cyclic(c, (double*)W, (int64_t)S * F, (const double*)c->y, c->N);
+    };
+    int rc = fill();
+    if (rc == CGLB_OK)
+        rc = time_repeated(c, reps, [&]() -> int {
+            CGLB_TRY(launch_feature_operand(c, om, ph, W, F, S));
+            return launch_feature_multi(c, (const double*)c->X, n_rows, F, S, (double*)out, S);
+        }, ms_avg);
+    (void)hipStreamSynchronize(c->stream);
+    return rc;
+}
+
+int cglb_itergp_sample(cglb_ctx* c, const void* xnew, int64_t n_new, const void* omega, const void* phase, const void* W, const void* eps, int64_t F, int S,
+                       double max_error, int max_cg_iter, void* f_out, void* U_out, int* steps, double* half_rz) {
+    if (c) c->obj_valid = false;
+    if (!c || !xnew || !omega || !phase || !W || !eps || !f_out || n_new < 0 || F < 1 || S < 1 || max_cg_iter < 0)
+        return c ? cglb_fail(c, CGLB_ERR_BAD_ARG, "bad argument") : CGLB_ERR_BAD_ARG;
+    CGLB_TRY(require_itergp_ok(c));
+    if (n_new == 0) return CGLB_OK;
+    HIP_CHECK(c, hipSetDevice(c->device));
+    const int64_t N = c->N;
+    const size_t col = (size_t)N * sizeof(double);
+    multi_work w;
+    CGLB_TRY(multi_reserve(c, S, &w));
+    CGLB_TRY(itergp_reserve(c, S, (size_t)S * N));
+    CGLB_TRY(c->mem.reserve(c, &c->ft_G, &c->ft_G_cap, (size_t)std::max(N, n_new) * S * sizeof(double)));
+    CGLB_TRY(c->mem.reserve(c, &c->ft_KU, &c->ft_KU_cap, (size_t)n_new * S * sizeof(double)));
+    // the preconditioner of the last evaluation at the current data and hyper-parameters; without one it is built first.  it_alpha and it_valid
+    // stay as they are: the next predictive call finds what it would have found
+    if (!(c->it_valid && c->have_terms)) CGLB_TRY(itergp_common_terms(c));
+    void *xr = nullptr, *xs = nullptr, *xa = nullptr;
+    DevTemps tmp;  // freed on every path below
+    CGLB_TRY(tmp.alloc(c, &xr, (size_t)n_new * c->D * sizeof(double)));
+    CGLB_TRY(tmp.alloc(c, &xs, (size_t)n_new * c->Dp * sizeof(double)));
+    CGLB_TRY(tmp.alloc(c, &xa, (size_t)n_new * sizeof(double)));
+    int st = 0;
+    double half = 0.0;
+    auto body = [&]() -> int {
+        // B_s = e - Phi(X) w_s - sqrt(noise) eps_s
+        CGLB_TRY(launch_feature_operand(c, omega, phase, W, F, S));
+        CGLB_TRY(feature_product(c, (const double*)c->X, N, F, S, c->ft_G));
+        HIP_CHECK(c, hipMemcpyAsync(c->it_eps, eps, (size_t)S * col, hipMemcpyDefault, c->stream));
+        hipLaunchKernelGGL(sample_rhs_kernel, dim3(grid1d_full((int64_t)S * N)), dim3(256), 0, c->stream, (const double*)c->y, c->mean, (const double*)c->ft_G,
+                           (const double*)c->it_eps, std::sqrt(c->noise), N, S, (double*)w.b);
+        CGLB_LAUNCH_CHECK(c);
+        // U = K^-1 B: one batched solve from zero, no restart steps, stopped on 1/2 sum_s r_s^T P^-1 r_s <= max_error
+        HIP_CHECK(c, hipMemsetAsync(c->it_V, 0, (size_t)S * col, c->stream));
+        if (S == 1) CGLB_TRY(pcg_solve(c, fused_ops(c), w.b, c->it_V, max_error, max_cg_iter, 0, &st, &half));
+        else CGLB_TRY(pcg_solve(c, multi_ops(c, w, S), w.b, c->it_V, max_error, max_cg_iter, 0, &st, &half));
+        // f_s = mean + Phi(X*) w_s + K_*f U_s
+        HIP_CHECK(c, hipMemcpyAsync(xr, xnew, (size_t)n_new * c->D * sizeof(double), hipMemcpyDefault, c->stream));
+        CGLB_TRY(launch_prep_scaled(c, xr, n_new, xs, xa, true));  // hot units for the pair kernels
+        CGLB_TRY(feature_product(c, (const double*)xr, n_new, F, S, c->ft_G));
+        int64_t ki = S, ks = 1;
+        if (is_wide(c)) {  // column by column, as the predictive mean of a wide context
+            for (int s = 0; s < S; ++s) CGLB_TRY(launch_cross_matvec(c, xs, xa, n_new, c->it_V + (size_t)s * N, c->ft_KU + (size_t)s * n_new));
+            ki = 1; ks = n_new;
+        } else {
+            int64_t ldv = 0;
+            CGLB_TRY(launch_cross_multi_operand(c, c->it_V, S, &ldv));
+            CGLB_TRY(launch_cross_multi(c, xs, xa, n_new, (const double*)c->cm_vi, ldv, S, c->ft_KU, S));
+        }
+        hipLaunchKernelGGL(sample_combine_kernel, dim3(grid1d_full((int64_t)S * n_new)), dim3(256), 0, c->stream, c->mean, (const double*)c->ft_G,
+                           (const double*)c->ft_KU, ki, ks, n_new, S, (double*)f_out);
+        CGLB_LAUNCH_CHECK(c);
+        if (U_out) HIP_CHECK(c, hipMemcpyAsync(U_out, c->it_V, (size_t)S * col, hipMemcpyDeviceToDevice, c->stream));
+        return CGLB_OK;
+    };
+    const int rc = body();
+    (void)hipStreamSynchronize(c->stream);  // before `tmp` releases the buffers the kernels use, and the caller its host arrays
+    if (rc == CGLB_OK) {
+        if (steps) *steps = st;
+        if (half_rz) *half_rz = half;
+    }
     return rc;
 }
 

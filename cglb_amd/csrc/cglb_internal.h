@@ -249,6 +249,18 @@ struct cglb_ctx {
     size_t cm_part_cap = 0;
     void* cm_vi = nullptr;                              // [N][S rounded up to 8] interleaved column operand of cglb_cross_matmat
     size_t cm_vi_cap = 0;
+    // random-feature product (kernels_feature_multi.hip) and the pathwise posterior samples built on it (cglb_itergp_sample)
+    double* ft_rec = nullptr;                           // [groups][F][FEATURE_REC] operand records {b_j | omega_j | W[8 g .., j]} in turns
+    double* ft_in = nullptr;                            // [F][D] omega and [F] phases as the caller gave them (device copy)
+    double* ft_par = nullptr;                           // [D] 1 / (2 pi l_k), [D] centre c_k
+    double* ft_part = nullptr;                          // partial-sum slabs [jsplit][rows][8]
+    size_t ft_rec_cap = 0, ft_in_cap = 0, ft_par_cap = 0, ft_part_cap = 0;
+    std::vector<double> ft_host;                        // host source of ft_par
+    double* ft_G = nullptr;                             // [rows][S] feature product of a sampling call (training rows, then the new points)
+    double* ft_KU = nullptr;                            // [n_new][S] K_*f U of a sampling call
+    size_t ft_G_cap = 0, ft_KU_cap = 0;
+    hipEvent_t ft_ev[2] = {nullptr, nullptr};           // start | end of the last feature product ("feature_ms")
+    bool ft_ev_set = false;
     std::string err;
 };
 
@@ -398,6 +410,13 @@ int launch_cross_multi_operand(cglb_ctx* c, const void* V, int S, int64_t* ldv_o
 int launch_cross_multi_var(cglb_ctx* c, const double* blk, int64_t nrows, int sp, int64_t ld, double* f_var);  // f_var[i] = var - |blk[i][:sp]|^2
 int cross_multi_rows_per_block(const cglb_ctx* c);  // new points per workgroup of the pair kernel at the context's width
 int cross_multi_width();                            // columns per group (8): the leading dimensions are multiples of it
+// kernels_feature_multi.hip: out[i * ldo + s] = sqrt(2 var / F) sum_j W[s][j] cos(sum_k omega[j][k] (x_ik - c_k) / l_k + b_j), s < S; X dev [nrows][D] raw
+// rows; the operand records of (omega, phase, W) in c->ft_rec first (omega [F][D], phase [F]: host or device; W dev [S][F]).  fp64, any D.  Bitwise
+// repeatable.
+int launch_feature_operand(cglb_ctx* c, const void* omega, const void* phase, const void* W, int64_t F, int S);
+int launch_feature_multi(cglb_ctx* c, const double* X, int64_t nrows, int64_t F, int S, double* out, int64_t ldo);
+int feature_rows_per_block(const cglb_ctx* c);      // rows per workgroup at the context's width
+void feature_split(const cglb_ctx* c, int64_t nrows, int64_t F, int64_t* jsplit_out, int64_t* jchunk_out);  // feature chunks of one launch
 // kernels_vec.hip
 // dot, update_v_r, update_p: s columns of length n ([s][n], one launch each; per-column device scalars [s]); s = 1 is the one-column form.
 // A zero denominator gives a zero factor.

@@ -87,6 +87,35 @@ __device__ __forceinline__ double sqrt_pos(double x) {
 }
 __device__ __forceinline__ float sqrt_pos(float x) { return __builtin_sqrtf(fmaxf(x, 0.0f)); }
 
+// cos(2 pi phi) for a phase phi in TURNS of any magnitude below 2^51 (random-feature product, kernels_feature_multi.hip).  Branch-free:
+//   t = phi - rint(phi), |t| <= 1/2: exact in fp64 at any magnitude (the caller prepares its operands in turns, so no multiple of an
+//       irrational period is ever subtracted: the large-argument path of libm's cos, which branches per lane, has no counterpart here)
+//   d = 1/4 - |t|,  a = 1/4 - |d| in [0, 1/4]: the fold to a quarter period, cos(2 pi t) = sign(d) cos(2 pi a).  Both subtractions are exact
+//       for |t| >= 1/8 (Sterbenz); below, each rounds by <= 2^-55, which moves the value by <= 2 * 2 pi sin(pi/4) 2^-55 = 2.5e-16;
+//       a = 0 at t = 0 and the constant term is 1: cos_turns(integer) = 1 exactly
+//   C(a^2) ~ cos(2 pi a): even polynomial of degree 16 (tools/cos_poly_fit.py: approximation error 5.7e-17), Horner form
+// ABSOLUTE error <= CGLB_COS_TURNS_ERR = 3e-16 for every phase: the maximum over the 1e5 phases of tests/test_sample_ref_host.py (exact eighths of a
+// turn +- 1 ulp, magnitudes up to 2^30) against 50-digit arithmetic is 2.5e-16, read at the upper end of its last digit.  There is one level:
+// the "precision" option does not apply.
+// 14 vector-fp64 instructions: rndne, 3 add, mul, 8 fma, v_bfi_b32 for the sign.
+#define CGLB_COS_TURNS_ERR 3e-16
+__device__ __forceinline__ double cos_turns(double phi) {
+    const double t = phi - __builtin_rint(phi);
+    const double d = 0.25 - __builtin_fabs(t);
+    const double a = 0.25 - __builtin_fabs(d);
+    const double v = a * a;
+    double p = 0x1.179a329ef4140p-2;
+    p = __builtin_fma(p, v, -0x1.b6a6feabe52e9p+0);
+    p = __builtin_fma(p, v, 0x1.f9d2c1f3b2167p+2);
+    p = __builtin_fma(p, v, -0x1.a6d1f12b0bef2p+4);
+    p = __builtin_fma(p, v, 0x1.e1f5068620bcbp+5);
+    p = __builtin_fma(p, v, -0x1.55d3c7e3c9051p+6);
+    p = __builtin_fma(p, v, 0x1.03c1f081b5a9fp+6);
+    p = __builtin_fma(p, v, -0x1.3bd3cc9be45dep+4);
+    p = __builtin_fma(p, v, 1.0);
+    return __builtin_copysign(p, d);
+}
+
 // ---- precision levels of the pair kernels (cglb_set_option "precision") ------------------------------------------------------
 // The figures below are those of the EVALUATOR (table, polynomial, square root) for the squared distance it is handed.  A kernel value of a
 // Gram-form pass carries, at every level, the cancellation error of that distance on top - (5 D + 3) u max(a_i, a_j), derived at

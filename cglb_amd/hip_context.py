@@ -53,6 +53,14 @@ class IterGPResult:
     grad: Optional[dict]  # the unbiased gradient estimate {lengthscales, variance, noise, mean}: not the derivative of `lml`
 
 
+@dataclass
+class IterGPSamples:
+    samples: torch.Tensor           # [S, n_new] posterior function samples, sample s contiguous
+    steps: int                      # iterations of the batched solve
+    residual_error: float           # 1/2 sum_s r_s^T P^-1 r_s at its end
+    solves: Optional[torch.Tensor]  # [S, N] U_s = K^-1 (e - Phi(X) w_s - sqrt(noise) eps_s) when asked for
+
+
 def _ptr(t: Optional[torch.Tensor]):
     return None if t is None else c_void_p(t.data_ptr())
 
@@ -396,6 +404,51 @@ class HipContext:
         ms = c_double()
         _lib.check(self.lib.cglb_time_cross_matmat(self._ctx, int(n_new), int(s), int(reps), byref(ms)), self._ctx)
         return ms.value
+
+    def _features(self, omega, phase, W):
+        om = torch.as_tensor(omega, dtype=self.dtype).reshape(-1, self.D).contiguous().to(self.device)
+        ph = torch.as_tensor(phase, dtype=self.dtype).reshape(-1).contiguous().to(self.device)
+        Wt = torch.as_tensor(W, dtype=self.dtype).to(self.device)
+        Wt = Wt.reshape(-1, om.shape[0]).contiguous()
+        if ph.shape[0] != om.shape[0] or om.shape[0] < 1 or Wt.shape[0] < 1:
+            raise ValueError("omega [F, D], phase [F] and W [S, F] must agree on F >= 1")
+        return om, ph, Wt
+
+    def feature_matmat(self, x, omega, phase, W, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """sqrt(2 variance / F) sum_j W[s, j] cos(omega_j . (x_i - c) / l + phase_j) at the rows x [n_rows, D] (None: the training rows) for
+        omega [F, D], phase [F], W [S, F]: [n_rows, S], every cosine evaluated once per group of 8 columns (cglb_feature_matmat).
+        `out`: a contiguous device tensor [n_rows, S] to write into."""
+        xr = None if x is None else self._xnew(x)
+        n = self.N if xr is None else xr.shape[0]
+        om, ph, Wt = self._features(omega, phase, W)
+        if out is None:
+            out = torch.empty((n, Wt.shape[0]), dtype=self.dtype, device=self.device)
+        elif out.device != self.device or out.dtype != self.dtype or tuple(out.shape) != (n, Wt.shape[0]) or not out.is_contiguous():
+            raise ValueError("out must be a contiguous device tensor [n_rows, S] in the context dtype")
+        rc = self.lib.cglb_feature_matmat(self._ctx, _ptr(xr), n, _ptr(om), _ptr(ph), _ptr(Wt), int(om.shape[0]), int(Wt.shape[0]), _ptr(out))
+        _lib.check(rc, self._ctx)
+        return out
+
+    def time_feature_matmat(self, n_rows: int, f: int, s: int, reps: int) -> float:
+        """ms per feature product of f features and s columns at the first n_rows training rows."""
+        ms = c_double()
+        _lib.check(self.lib.cglb_time_feature_matmat(self._ctx, int(n_rows), int(f), int(s), int(reps), byref(ms)), self._ctx)
+        return ms.value
+
+    def itergp_sample(self, xnew, omega, phase, W, eps, max_error=1e-3, max_cg_iter=1000, return_solves=False) -> IterGPSamples:
+        """Pathwise posterior samples at xnew [n_new, D] (cglb_itergp_sample): omega [F, D], phase [F], W [S, F] and eps [S, N] are the
+        caller's draws (the library draws none).  Sample s is f_s = mean + Phi(xnew) w_s + K_*f K^-1 (y - mean - Phi(X) w_s - sqrt(noise) eps_s)."""
+        xn = self._xnew(xnew)
+        om, ph, Wt = self._features(omega, phase, W)
+        S = int(Wt.shape[0])
+        e = torch.as_tensor(eps, dtype=self.dtype).reshape(S, self.N).contiguous().to(self.device)
+        f = torch.empty((S, xn.shape[0]), dtype=self.dtype, device=self.device)
+        U = torch.empty((S, self.N), dtype=self.dtype, device=self.device) if return_solves else None
+        steps, half = c_int(), c_double()
+        rc = self.lib.cglb_itergp_sample(self._ctx, _ptr(xn), xn.shape[0], _ptr(om), _ptr(ph), _ptr(Wt), _ptr(e), int(om.shape[0]), S, float(max_error),
+                                         int(max_cg_iter), _ptr(f), _ptr(U), byref(steps), byref(half))
+        _lib.check(rc, self._ctx)
+        return IterGPSamples(f, steps.value, half.value, U)
 
     def grad_kff_multi(self, U, V) -> np.ndarray:
         """[sum_b u_b^T (dK_ff / dl_d) v_b for d < D, sum_b u_b^T kappa v_b] for U, V [N, S]: one evaluation of every kernel value for up to 8 pairs."""

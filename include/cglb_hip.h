@@ -337,6 +337,37 @@ int cglb_cross_matmat(cglb_ctx* ctx, const void* xnew, int64_t n_new, const void
  * the context stream) at the first n_new training rows as new points (n_new <= n_total), beside cglb_time_grad_kff_multi; S < 0 times the
  * comparison side instead: |S| single products of cglb_cross_matvec's kernel on the same operands */
 int cglb_time_cross_matmat(cglb_ctx* ctx, int64_t n_new, int S, int reps, double* ms_avg);
+/* Random-Fourier-feature product, the prior term of a pathwise sample (csrc/kernels_feature_multi.hip):
+ *   out[i, s] = sqrt(2 variance / F) sum_{j < F} W[s, j] cos( sum_k omega[j, k] (x_ik - c_k) / l_k + b_j )
+ * with l the current lengthscales and c the training column means the context centres by.  x: any [n_rows, d], or NULL for the training rows
+ * (n_rows = n_total); omega: any (host or device) [F, d]; phase: any [F] (b, radians); W: dev [S, F], column s contiguous (the convention of
+ * cglb_cross_matmat); out: dev [n_rows, S] row-major.  The n_rows x F feature matrix is never formed: every cosine is evaluated once per group of
+ * 8 columns, by the branch-free cos_turns of csrc/devmath.h (absolute error <= 3e-16 at any phase magnitude; the "precision" option does not
+ * apply).  Bitwise reproducible.  Scope of cglb_itergp_predict (fp64, one rank, one target column, any input width; else CGLB_ERR_BAD_ARG).
+ * "feature_ms" (cglb_get_stat): device time of the last product. */
+int cglb_feature_matmat(cglb_ctx* ctx, const void* x, int64_t n_rows, const void* omega, const void* phase, const void* W, int64_t F, int S, void* out);
+/* average duration (ms) of `reps` back-to-back feature products (operand records, kernel and fixed-order sum of every group, on the context
+ * stream) of F features and S columns at the first n_rows training rows (n_rows <= n_total), beside cglb_time_cross_matmat */
+int cglb_time_feature_matmat(cglb_ctx* ctx, int64_t n_rows, int64_t F, int S, int reps, double* ms_avg);
+/* predict_f_samples by pathwise conditioning (Matheron's rule with a random-feature prior; Wilson et al. 2020), S samples at once:
+ *   f_s = mean + Phi(X*) w_s + K_*f U_s,   U_s = K^-1 (e - Phi(X) w_s - sqrt(noise) eps_s),   K = variance kappa(X, X) + noise I,  e = y - mean
+ * with Phi w the product of cglb_feature_matmat.  The library draws no random numbers: omega [F, d], phase [F] (any), W (dev [S, F]) and eps
+ * (any [S, n_total]) are the caller's; with standard normal W and eps, phases uniform on [0, 2 pi) and omega drawn from the spectral measure of the
+ * unit-lengthscale kernel, each f_s is a draw of the posterior of the GP whose PRIOR is the F-feature approximation of the kernel, conditioned
+ * through the exact K: exact for that prior up to the solve's tolerance, and the mean over draws is the exact predictive mean for ANY omega and
+ * phase.  The feature approximation itself (covariance error O(1 / sqrt(F))) is a property of the estimator, not of this implementation.
+ *   solve    one batched PCG (cglb_pcg_solve_multi's loop) on the S columns from zero with the class's preconditioner - the one of the last
+ *            evaluation at the current data and hyper-parameters; without one it is built first, as in cglb_itergp_predict - no restart steps, stop
+ *            on 1/2 sum_s r_s^T P^-1 r_s <= max_error or max_cg_iter steps (steps, half_rz: as returned by that loop)
+ *   bound    P = Q_ff + noise I with the Nystrom term Q_ff (jitter included) below K_ff in the Loewner order, so P is below K and
+ *            r_s^T K^-1 r_s <= r_s^T P^-1 r_s, the sum of which over s is <= 2 max_error at the stop; with
+ *            d_s = K^-1 r_s the error of U_s, |k_*^T d_s| <= sqrt(k_*^T K^-1 k_*) sqrt(r_s^T K^-1 r_s) <= sqrt(variance) sqrt(2 max_error): every
+ *            sample value is within sqrt(2 variance max_error) of its value at the exact solve
+ *   product  K_*f U through cglb_cross_matmat's kernel up to 32 input dimensions, column by column through cglb_cross_matvec's beyond
+ * f_out: dev [S, n_new], sample s contiguous; U_out: dev [S, n_total] or NULL (the solves, for tests).  Two calls with the same inputs return
+ * bitwise equal samples.  The stored alpha and the variance cache are left as they are.  Scope of cglb_itergp_predict. */
+int cglb_itergp_sample(cglb_ctx* ctx, const void* xnew, int64_t n_new, const void* omega, const void* phase, const void* W, const void* eps, int64_t F,
+                       int S, double max_error, int max_cg_iter, void* f_out, void* U_out, int* steps, double* half_rz);
 /* The gradient pass of the class on its own (tests, timing): out host double[d + 1], out[k] = sum_b u_b^T (dK_ff / dl_k) v_b for k < d and
  * out[d] = sum_b u_b^T kappa v_b (kappa = K_ff / variance), b < S.  U, V: dev [S, n_total], pair b contiguous.  Every kernel value is evaluated
  * once per unordered pair for up to 8 pairs of vectors (fp64, d <= 32: csrc/kernels_grad_multi.hip; wider inputs run S single passes); S > 8
@@ -389,7 +420,8 @@ int cglb_time_kernel(cglb_ctx* ctx, int which, int reps, double* ms_avg);
  * "itergp_select_ms" | "itergp_solve_ms" | "itergp_grad_ms": device time of the phases of the last cglb_itergp_objective_and_grad - pivots and
  * common terms | right-hand sides and the batched solve | gradient; 0 for a phase that evaluation did not run;
  * "itergp_cache_ms" | "itergp_var_ms": device time of the last cglb_itergp_var_cache | of the variance part (product and row norms) of the last
- * cglb_itergp_predict_cached; "itergp_cache_request": the rank the valid variance cache was asked for, 0 without a valid cache. */
+ * cglb_itergp_predict_cached; "itergp_cache_request": the rank the valid variance cache was asked for, 0 without a valid cache;
+ * "feature_ms": device time of the last feature product (kernel and slab sums of every group) of cglb_feature_matmat or cglb_itergp_sample. */
 int cglb_get_stat(cglb_ctx* ctx, const char* name, double* value);
 /* Tunables: name = "kff_variant" | "kff_jsplit" | "kff_rows" | "sym_chunk" | "precond_mode" | "chol_mode" | "pcg_lookahead" | "sym_order" | "aat_block" | "grad_gram" | "k1_profile" |
  * "grad_trsm" (gradient algebra against L = chol(K_uu): 0 products with the explicit inverse, 1 backward-stable triangular solves, 2 = default:
