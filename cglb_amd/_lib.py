@@ -112,6 +112,15 @@ SIGNATURES = {
     "cglb_time_feature_matmat": (c_int, [c_void_p, c_int64, c_int64, c_int, c_int, POINTER(c_double)]),
     "cglb_itergp_sample": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_double, c_int, c_void_p, c_void_p,
                                    POINTER(c_int), POINTER(c_double)]),
+    # input gradients of predictive and sample paths (csrc/kernels_input_grad.hip)
+    "cglb_cross_grad_matmat": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int, c_void_p, c_void_p]),
+    "cglb_time_cross_grad_matmat": (c_int, [c_void_p, c_int64, c_int, c_int, POINTER(c_double)]),
+    "cglb_feature_grad_matmat": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p]),
+    "cglb_time_feature_grad_matmat": (c_int, [c_void_p, c_int64, c_int64, c_int, c_int, POINTER(c_double)]),
+    "cglb_itergp_predict_grad": (c_int, [c_void_p, c_void_p, c_int64, c_double, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "cglb_itergp_paths_solve": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_double, c_int, c_void_p, POINTER(c_int),
+                                        POINTER(c_double)]),
+    "cglb_itergp_paths_eval": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p]),
     "cglb_grad_kff_multi": (c_int, [c_void_p, c_void_p, c_void_p, c_int, POINTER(c_double)]),
     "cglb_time_grad_kff_multi": (c_int, [c_void_p, c_int, c_int, POINTER(c_double)]),
 }

@@ -762,6 +762,97 @@ class SampleIterGPR(nn.Module):
         return res.samples.reshape(S, -1, 1)
 
 
+class PredictGradIterGPR(nn.Module):
+    """`PredictGradIterGPR(model)(xnew)` -> (mean [n, 1], dmean [n, d], var [n, 1], dvar [n, d]): predict_f of the iterative model and its
+    gradients with respect to the new points (cglb_itergp_predict_grad).  The variances come from the Lanczos variance cache of rank `var_rank`
+    (None: the model's `pred_var_rank`), built on demand as PredictIterGPR builds it; `dvar` is the exact gradient of that cache's variance
+    (an upper bound of the exact variance), not of the exact variance.  Rank 0: `var` and `dvar` are None."""
+
+    def __init__(self, model: IterGPR, max_error: float = 1e-3, var_rank: Optional[int] = None):
+        if not isinstance(model, IterGPR):
+            raise ValueError(f"IterGPR model expected in the constructor of the {self.__class__}")
+        super().__init__()
+        object.__setattr__(self, "model", model)
+        self.max_error = float(max_error)
+        self.var_rank = int(model.pred_var_rank if var_rank is None else var_rank)
+
+    def forward(self, xnew: Tensor):
+        model, hip = self.model, self.model.hip
+        with torch.no_grad():
+            model.push_hypers(get_cholesky_jitter())
+            rank = min(self.var_rank, hip.N, 1024)
+            if rank > 0 and int(hip.get_stat("itergp_cache_request")) != rank:
+                hip.itergp_var_cache(rank)
+            mean, dmean, var, dvar = hip.itergp_predict_grad(xnew, self.max_error, model.max_cg_iter, with_var=rank > 0)
+        return mean.reshape(-1, 1), dmean, None if var is None else var.reshape(-1, 1), dvar
+
+
+class _PathValues(torch.autograd.Function):
+    """paths(x) with the library's gradient: backward contracts the incoming [S, n, 1] gradient with the stored [S, n, d] block."""
+
+    @staticmethod
+    def forward(ctx, paths, x):
+        f, g = paths.value_and_grad(x)
+        ctx.save_for_backward(g)
+        ctx.x_shape, ctx.x_device = x.shape, x.device
+        return f
+
+    @staticmethod
+    def backward(ctx, grad_f):
+        (g,) = ctx.saved_tensors
+        return None, (grad_f.to(g.device) * g).sum(dim=0).reshape(ctx.x_shape).to(ctx.x_device)
+
+
+class PathsIterGPR(nn.Module):
+    """`paths = PathsIterGPR(model, num_samples)`: `num_samples` posterior sample paths of the iterative model that are solved ONCE, here
+    (cglb_itergp_paths_solve), and evaluated anywhere afterwards without a solve (cglb_itergp_paths_eval): `paths(x)` -> [S, n, 1],
+    `paths.value_and_grad(x)` -> ([S, n, 1], [S, n, d]) with the gradients with respect to x.  When `x.requires_grad`, `paths(x)` is
+    differentiable by autograd.  Frequencies, phases, weights and noise are drawn from `model.generator` in the order of
+    SampleIterGPR.forward (fixed_features False): with the same seed the paths are the samples that class returns.  The paths belong to the
+    hyper-parameters and targets they were solved at: evaluating after either changed raises RuntimeError."""
+
+    def __init__(self, model: IterGPR, num_samples: int, num_features: int = 1024, max_error: float = 1e-3):
+        if not isinstance(model, IterGPR):
+            raise ValueError(f"IterGPR model expected in the constructor of the {self.__class__}")
+        super().__init__()
+        object.__setattr__(self, "model", model)
+        self.num_samples, self.num_features, self.max_error = int(num_samples), int(num_features), float(max_error)
+        S = self.num_samples
+        with torch.no_grad():
+            self.omega, self.b = draw_features(model.covar_module.base_kernel.kind, model.hip.D, self.num_features, model.generator)
+            self.W = torch.randn(S, self.num_features, dtype=torch.float64, generator=model.generator)
+            eps = torch.randn(S, model.hip.N, dtype=torch.float64, generator=model.generator)
+            model.push_hypers(get_cholesky_jitter())
+            res = model.hip.itergp_paths_solve(self.omega, self.b, self.W, eps, self.max_error, model.max_cg_iter)
+        self.W = self.W.to(model.hip.device)
+        self.solves, self.steps, self.residual_error = res.solves, res.steps, res.residual_error
+        self._solved_at = self._state()
+
+    def _state(self):
+        model = self.model
+        ls, var, noise, mean = [t.detach() for t in model.hyper_tensors()]
+        return (ls.cpu().numpy().tobytes(), float(var), float(noise), float(mean), id(model.hip), model.hip.state_version)
+
+    def _check(self):
+        if self._state() != self._solved_at:
+            raise RuntimeError("the sample paths were solved at other hyper-parameters or data: draw new paths (PathsIterGPR) after a change of either")
+
+    def _eval(self, x, with_grad):
+        self._check()
+        with torch.no_grad():
+            f, g = self.model.hip.itergp_paths_eval(x.detach(), self.omega, self.b, self.W, self.solves, with_grad=with_grad)
+        return f.reshape(self.num_samples, -1, 1), g
+
+    def value_and_grad(self, x: Tensor) -> Tuple[Tensor, Tensor]:
+        return self._eval(torch.as_tensor(x), True)
+
+    def forward(self, x: Tensor) -> Tensor:
+        x = torch.as_tensor(x)
+        if x.requires_grad:
+            return _PathValues.apply(self, x)
+        return self._eval(x, False)[0]
+
+
 class _PredictLogdensity:
     """Mixed in before a predictor: `forward((x, y))` is the log density of y under that predictor's predictive at x, summed over the outputs."""
 

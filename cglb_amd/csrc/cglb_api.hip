@@ -1264,6 +1264,62 @@ int fill_cyclic(cglb_ctx* c, double* dst, int64_t n, const double* src, int64_t 
     return CGLB_OK;
 }
 
+// the two halves of a pathwise sample, shared by cglb_itergp_sample and cglb_itergp_paths_solve / cglb_itergp_paths_eval
+// buffers of the solve (w, it_V, it_eps, ft_G for max(N, rows_G) rows) and the preconditioner of the last evaluation at the current data and
+// hyper-parameters; without one it is built first.  it_alpha and it_valid stay as they are: the next predictive call finds what it would have found
+int sample_reserve(cglb_ctx* c, int S, int64_t rows_G, multi_work* w) {
+    CGLB_TRY(multi_reserve(c, S, w));
+    CGLB_TRY(itergp_reserve(c, S, (size_t)S * c->N));
+    CGLB_TRY(c->mem.reserve(c, &c->ft_G, &c->ft_G_cap, (size_t)std::max(c->N, rows_G) * S * sizeof(double)));
+    if (!(c->it_valid && c->have_terms)) CGLB_TRY(itergp_common_terms(c));
+    return CGLB_OK;
+}
+// c->it_V <- U = K^-1 B, B_s = e - Phi(X) w_s - sqrt(noise) eps_s; leaves the operand records of (omega, phase, W) in c->ft_rec
+int sample_solve(cglb_ctx* c, const multi_work& w, const void* omega, const void* phase, const void* W, const void* eps, int64_t F, int S, double max_error,
+                 int max_cg_iter, int* st, double* half) {
+    const int64_t N = c->N;
+    const size_t col = (size_t)N * sizeof(double);
+    CGLB_TRY(launch_feature_operand(c, omega, phase, W, F, S));
+    CGLB_TRY(feature_product(c, (const double*)c->X, N, F, S, c->ft_G));
+    HIP_CHECK(c, hipMemcpyAsync(c->it_eps, eps, (size_t)S * col, hipMemcpyDefault, c->stream));
+    hipLaunchKernelGGL(sample_rhs_kernel, dim3(grid1d_full((int64_t)S * N)), dim3(256), 0, c->stream, (const double*)c->y, c->mean, (const double*)c->ft_G,
+                       (const double*)c->it_eps, std::sqrt(c->noise), N, S, (double*)w.b);
+    CGLB_LAUNCH_CHECK(c);
+    // U = K^-1 B: one batched solve from zero, no restart steps, stopped on 1/2 sum_s r_s^T P^-1 r_s <= max_error
+    HIP_CHECK(c, hipMemsetAsync(c->it_V, 0, (size_t)S * col, c->stream));
+    if (S == 1) CGLB_TRY(pcg_solve(c, fused_ops(c), w.b, c->it_V, max_error, max_cg_iter, 0, st, half));
+    else CGLB_TRY(pcg_solve(c, multi_ops(c, w, S), w.b, c->it_V, max_error, max_cg_iter, 0, st, half));
+    return CGLB_OK;
+}
+// f_s = mean + Phi(X*) w_s + K_*f U_s through the value kernels, from the records in c->ft_rec and the solves U (dev [S][N]); xr, xs, xa: the
+// caller's [n_new][D], [n_new][Dp], [n_new]
+int sample_eval(cglb_ctx* c, const void* xnew, int64_t n_new, void* xr, void* xs, void* xa, const double* U, int64_t F, int S, void* f_out) {
+    const int64_t N = c->N;
+    HIP_CHECK(c, hipMemcpyAsync(xr, xnew, (size_t)n_new * c->D * sizeof(double), hipMemcpyDefault, c->stream));
+    CGLB_TRY(launch_prep_scaled(c, xr, n_new, xs, xa, true));  // hot units for the pair kernels
+    CGLB_TRY(feature_product(c, (const double*)xr, n_new, F, S, c->ft_G));
+    int64_t ki = S, ks = 1;
+    if (is_wide(c)) {  // column by column, as the predictive mean of a wide context
+        for (int s = 0; s < S; ++s) CGLB_TRY(launch_cross_matvec(c, xs, xa, n_new, U + (size_t)s * N, c->ft_KU + (size_t)s * n_new));
+        ki = 1; ks = n_new;
+    } else {
+        int64_t ldv = 0;
+        CGLB_TRY(launch_cross_multi_operand(c, U, S, &ldv));
+        CGLB_TRY(launch_cross_multi(c, xs, xa, n_new, (const double*)c->cm_vi, ldv, S, c->ft_KU, S));
+    }
+    hipLaunchKernelGGL(sample_combine_kernel, dim3(grid1d_full((int64_t)S * n_new)), dim3(256), 0, c->stream, c->mean, (const double*)c->ft_G,
+                       (const double*)c->ft_KU, ki, ks, n_new, S, (double*)f_out);
+    CGLB_LAUNCH_CHECK(c);
+    return CGLB_OK;
+}
+
+// the scope of the input-gradient entries: the class's own, up to 32 input dimensions
+int require_input_grad_ok(cglb_ctx* c) {
+    CGLB_TRY(require_itergp_ok(c));
+    if (is_wide(c)) return cglb_fail(c, CGLB_ERR_BAD_ARG, "the input-gradient products have no wide path yet: they are available up to 32 input dimensions");
+    return CGLB_OK;
+}
+
 }  // namespace
 
 // =================================================== C ABI ====================================================
@@ -2095,6 +2151,9 @@ int cglb_get_matrix(cglb_ctx* c, int which, void* dst) {
     } else if (which == 1 || which == 2) {  // column-major lower -> row-major lower via transpose into Mtmp2
         CGLB_TRY(launch_transpose(c, which == 1 ? c->Lc : c->LBc, c->Mtmp2));
         HIP_CHECK(c, hipMemcpyAsync(dst, c->Mtmp2, (size_t)c->M * c->M * e, hipMemcpyDefault, c->stream));
+    } else if (which == 3) {  // alpha [n_total] of the iterative exact-GP class: the solve its last predictive call (or evaluation) stored
+        if (!c->it_alpha || !c->it_valid) return cglb_fail(c, CGLB_ERR_STATE, "no stored alpha: an evaluation or a predictive call of the iterative exact GP class comes first");
+        HIP_CHECK(c, hipMemcpyAsync(dst, c->it_alpha, (size_t)c->N * sizeof(double), hipMemcpyDefault, c->stream));
     } else {
         return cglb_fail(c, CGLB_ERR_BAD_ARG, "unknown matrix id");
     }
@@ -2647,16 +2706,10 @@ int cglb_itergp_sample(cglb_ctx* c, const void* xnew, int64_t n_new, const void*
     CGLB_TRY(require_itergp_ok(c));
     if (n_new == 0) return CGLB_OK;
     HIP_CHECK(c, hipSetDevice(c->device));
-    const int64_t N = c->N;
-    const size_t col = (size_t)N * sizeof(double);
+    const size_t col = (size_t)c->N * sizeof(double);
     multi_work w;
-    CGLB_TRY(multi_reserve(c, S, &w));
-    CGLB_TRY(itergp_reserve(c, S, (size_t)S * N));
-    CGLB_TRY(c->mem.reserve(c, &c->ft_G, &c->ft_G_cap, (size_t)std::max(N, n_new) * S * sizeof(double)));
+    CGLB_TRY(sample_reserve(c, S, n_new, &w));
     CGLB_TRY(c->mem.reserve(c, &c->ft_KU, &c->ft_KU_cap, (size_t)n_new * S * sizeof(double)));
-    // the preconditioner of the last evaluation at the current data and hyper-parameters; without one it is built first.  it_alpha and it_valid
-    // stay as they are: the next predictive call finds what it would have found
-    if (!(c->it_valid && c->have_terms)) CGLB_TRY(itergp_common_terms(c));
     void *xr = nullptr, *xs = nullptr, *xa = nullptr;
     DevTemps tmp;  // freed on every path below
     CGLB_TRY(tmp.alloc(c, &xr, (size_t)n_new * c->D * sizeof(double)));
@@ -2665,33 +2718,8 @@ int cglb_itergp_sample(cglb_ctx* c, const void* xnew, int64_t n_new, const void*
     int st = 0;
     double half = 0.0;
     auto body = [&]() -> int {
-        // B_s = e - Phi(X) w_s - sqrt(noise) eps_s
-        CGLB_TRY(launch_feature_operand(c, omega, phase, W, F, S));
-        CGLB_TRY(feature_product(c, (const double*)c->X, N, F, S, c->ft_G));
-        HIP_CHECK(c, hipMemcpyAsync(c->it_eps, eps, (size_t)S * col, hipMemcpyDefault, c->stream));
-        hipLaunchKernelGGL(sample_rhs_kernel, dim3(grid1d_full((int64_t)S * N)), dim3(256), 0, c->stream, (const double*)c->y, c->mean, (const double*)c->ft_G,
-                           (const double*)c->it_eps, std::sqrt(c->noise), N, S, (double*)w.b);
-        CGLB_LAUNCH_CHECK(c);
-        // U = K^-1 B: one batched solve from zero, no restart steps, stopped on 1/2 sum_s r_s^T P^-1 r_s <= max_error
-        HIP_CHECK(c, hipMemsetAsync(c->it_V, 0, (size_t)S * col, c->stream));
-        if (S == 1) CGLB_TRY(pcg_solve(c, fused_ops(c), w.b, c->it_V, max_error, max_cg_iter, 0, &st, &half));
-        else CGLB_TRY(pcg_solve(c, multi_ops(c, w, S), w.b, c->it_V, max_error, max_cg_iter, 0, &st, &half));
-        // f_s = mean + Phi(X*) w_s + K_*f U_s
-        HIP_CHECK(c, hipMemcpyAsync(xr, xnew, (size_t)n_new * c->D * sizeof(double), hipMemcpyDefault, c->stream));
-        CGLB_TRY(launch_prep_scaled(c, xr, n_new, xs, xa, true));  // hot units for the pair kernels
-        CGLB_TRY(feature_product(c, (const double*)xr, n_new, F, S, c->ft_G));
-        int64_t ki = S, ks = 1;
-        if (is_wide(c)) {  // column by column, as the predictive mean of a wide context
-            for (int s = 0; s < S; ++s) CGLB_TRY(launch_cross_matvec(c, xs, xa, n_new, c->it_V + (size_t)s * N, c->ft_KU + (size_t)s * n_new));
-            ki = 1; ks = n_new;
-        } else {
-            int64_t ldv = 0;
-            CGLB_TRY(launch_cross_multi_operand(c, c->it_V, S, &ldv));
-            CGLB_TRY(launch_cross_multi(c, xs, xa, n_new, (const double*)c->cm_vi, ldv, S, c->ft_KU, S));
-        }
-        hipLaunchKernelGGL(sample_combine_kernel, dim3(grid1d_full((int64_t)S * n_new)), dim3(256), 0, c->stream, c->mean, (const double*)c->ft_G,
-                           (const double*)c->ft_KU, ki, ks, n_new, S, (double*)f_out);
-        CGLB_LAUNCH_CHECK(c);
+        CGLB_TRY(sample_solve(c, w, omega, phase, W, eps, F, S, max_error, max_cg_iter, &st, &half));
+        CGLB_TRY(sample_eval(c, xnew, n_new, xr, xs, xa, c->it_V, F, S, f_out));
         if (U_out) HIP_CHECK(c, hipMemcpyAsync(U_out, c->it_V, (size_t)S * col, hipMemcpyDeviceToDevice, c->stream));
         return CGLB_OK;
     };
@@ -2701,6 +2729,210 @@ int cglb_itergp_sample(cglb_ctx* c, const void* xnew, int64_t n_new, const void*
         if (steps) *steps = st;
         if (half_rz) *half_rz = half;
     }
+    return rc;
+}
+
+// ---- input gradients of predictive and sample paths (kernels_input_grad.hip) ------------------------------------------------------------------
+int cglb_cross_grad_matmat(cglb_ctx* c, const void* xnew, int64_t n_new, const void* V, int S, void* out, void* gout) {
+    if (c) c->obj_valid = false;
+    if (!c || !xnew || !V || !gout || n_new < 0 || S < 1) return c ? cglb_fail(c, CGLB_ERR_BAD_ARG, "bad argument") : CGLB_ERR_BAD_ARG;
+    CGLB_TRY(require_input_grad_ok(c));
+    if (n_new == 0) return CGLB_OK;
+    HIP_CHECK(c, hipSetDevice(c->device));
+    void *xr = nullptr, *xs = nullptr, *xa = nullptr;
+    DevTemps tmp;  // freed on every path below
+    CGLB_TRY(tmp.alloc(c, &xr, (size_t)n_new * c->D * sizeof(double)));
+    CGLB_TRY(tmp.alloc(c, &xs, (size_t)n_new * c->Dp * sizeof(double)));
+    CGLB_TRY(tmp.alloc(c, &xa, (size_t)n_new * sizeof(double)));
+    auto body = [&]() -> int {
+        HIP_CHECK(c, hipMemcpyAsync(xr, xnew, (size_t)n_new * c->D * sizeof(double), hipMemcpyDefault, c->stream));
+        CGLB_TRY(launch_prep_scaled(c, xr, n_new, xs, xa, true));  // rows of the pair kernel: hot units
+        int64_t ldv = 0;
+        CGLB_TRY(launch_cross_multi_operand(c, V, S, &ldv));
+        return launch_cross_grad(c, xs, n_new, (const double*)c->cm_vi, ldv, S, (double*)out, S, (double*)gout);
+    };
+    const int rc = body();
+    (void)hipStreamSynchronize(c->stream);  // before `tmp` releases the buffers the kernels use
+    return rc;
+}
+
+int cglb_time_cross_grad_matmat(cglb_ctx* c, int64_t n_new, int S, int reps, double* ms_avg) {
+    if (c) c->obj_valid = false;
+    if (!c || !ms_avg || reps <= 0 || S < 1 || n_new < 1) return c ? cglb_fail(c, CGLB_ERR_BAD_ARG, "bad argument") : CGLB_ERR_BAD_ARG;
+    CGLB_TRY(require_input_grad_ok(c));
+    if (n_new > c->N) return cglb_fail(c, CGLB_ERR_BAD_ARG, "the timed product takes its new points from the training rows: n_new <= n_total");
+    HIP_CHECK(c, hipSetDevice(c->device));
+    multi_work w;
+    CGLB_TRY(multi_reserve(c, S, &w));
+    void *out = nullptr, *gout = nullptr;
+    DevTemps tmp;
+    CGLB_TRY(tmp.alloc(c, &out, (size_t)n_new * S * sizeof(double)));
+    CGLB_TRY(tmp.alloc(c, &gout, (size_t)n_new * S * c->D * sizeof(double)));
+    // operands as cglb_time_cross_matmat forms them: the first n_new training rows as new points, S copies of y as columns
+    for (int b = 0; b < S; ++b) HIP_CHECK(c, hipMemcpyAsync(w.p + (size_t)b * c->N * c->esz, c->y, (size_t)c->N * c->esz, hipMemcpyDeviceToDevice, c->stream));
+    const int rc = time_repeated(c, reps, [&]() -> int {
+        int64_t ldv = 0;
+        CGLB_TRY(launch_cross_multi_operand(c, w.p, S, &ldv));
+        return launch_cross_grad(c, c->Xh, n_new, (const double*)c->cm_vi, ldv, S, (double*)out, S, (double*)gout);
+    }, ms_avg);
+    (void)hipStreamSynchronize(c->stream);
+    return rc;
+}
+
+int cglb_feature_grad_matmat(cglb_ctx* c, const void* x, int64_t n_rows, const void* omega, const void* phase, const void* W, int64_t F, int S, void* out,
+                             void* gout) {
+    if (c) c->obj_valid = false;
+    if (!c || !omega || !phase || !W || !gout || n_rows < 0 || F < 1 || S < 1) return c ? cglb_fail(c, CGLB_ERR_BAD_ARG, "bad argument") : CGLB_ERR_BAD_ARG;
+    CGLB_TRY(require_input_grad_ok(c));
+    if (!x && n_rows != c->N) return cglb_fail(c, CGLB_ERR_BAD_ARG, "the feature product of the training rows (x NULL) has n_rows = n_total");
+    if (n_rows == 0) return CGLB_OK;
+    HIP_CHECK(c, hipSetDevice(c->device));
+    void* xr = nullptr;
+    DevTemps tmp;  // freed on every path below
+    if (x) CGLB_TRY(tmp.alloc(c, &xr, (size_t)n_rows * c->D * sizeof(double)));
+    auto body = [&]() -> int {
+        if (x) HIP_CHECK(c, hipMemcpyAsync(xr, x, (size_t)n_rows * c->D * sizeof(double), hipMemcpyDefault, c->stream));
+        CGLB_TRY(launch_feature_operand(c, omega, phase, W, F, S));
+        return launch_feature_grad(c, x ? (const double*)xr : (const double*)c->X, n_rows, F, S, (double*)out, S, (double*)gout);
+    };
+    const int rc = body();
+    (void)hipStreamSynchronize(c->stream);  // before `tmp` releases the buffer the kernels use, and the caller its omega and phase
+    return rc;
+}
+
+int cglb_time_feature_grad_matmat(cglb_ctx* c, int64_t n_rows, int64_t F, int S, int reps, double* ms_avg) {
+    if (c) c->obj_valid = false;
+    if (!c || !ms_avg || reps <= 0 || S < 1 || F < 1 || n_rows < 1) return c ? cglb_fail(c, CGLB_ERR_BAD_ARG, "bad argument") : CGLB_ERR_BAD_ARG;
+    CGLB_TRY(require_input_grad_ok(c));
+    if (n_rows > c->N) return cglb_fail(c, CGLB_ERR_BAD_ARG, "the timed product takes its rows from the training rows: n_rows <= n_total");
+    HIP_CHECK(c, hipSetDevice(c->device));
+    void *om = nullptr, *ph = nullptr, *W = nullptr, *out = nullptr, *gout = nullptr;
+    DevTemps tmp;
+    CGLB_TRY(tmp.alloc(c, &om, (size_t)F * c->D * sizeof(double)));
+    CGLB_TRY(tmp.alloc(c, &ph, (size_t)F * sizeof(double)));
+    CGLB_TRY(tmp.alloc(c, &W, (size_t)S * F * sizeof(double)));
+    CGLB_TRY(tmp.alloc(c, &out, (size_t)n_rows * S * sizeof(double)));
+    CGLB_TRY(tmp.alloc(c, &gout, (size_t)n_rows * S * c->D * sizeof(double)));
+    // operands as cglb_time_feature_matmat forms them: the training inputs as frequencies, the targets as phases and weights
+    const auto fill = [&]() -> int {
+        CGLB_TRY(fill_cyclic(c, (double*)om, F * c->D, (const double*)c->X, c->N * c->D));
+        CGLB_TRY(fill_cyclic(c, (double*)ph, F, (const double*)c->y, c->N));
+        return fill_cyclic(c, (double*)W, (int64_t)S * F, (const double*)c->y, c->N);
+    };
+    int rc = fill();
+    if (rc == CGLB_OK)
+        rc = time_repeated(c, reps, [&]() -> int {
+            CGLB_TRY(launch_feature_operand(c, om, ph, W, F, S));
+            return launch_feature_grad(c, (const double*)c->X, n_rows, F, S, (double*)out, S, (double*)gout);
+        }, ms_avg);
+    (void)hipStreamSynchronize(c->stream);
+    return rc;
+}
+
+int cglb_itergp_predict_grad(cglb_ctx* c, const void* xnew, int64_t n_new, double max_error, int max_cg_iter, void* f_mean, void* g_mean, void* f_var,
+                             void* g_var) {
+    if (c) c->obj_valid = false;
+    if (!c || !xnew || !f_mean || !g_mean || (!f_var) != (!g_var) || n_new < 0 || max_cg_iter < 0)
+        return c ? cglb_fail(c, CGLB_ERR_BAD_ARG, "bad argument") : CGLB_ERR_BAD_ARG;
+    CGLB_TRY(require_input_grad_ok(c));
+    if (f_var && c->it_cache_rank < 1)
+        return cglb_fail(c, CGLB_ERR_STATE, "cglb_itergp_var_cache must precede cglb_itergp_predict_cached at the current data and hyper-parameters");
+    if (n_new == 0) return CGLB_OK;
+    HIP_CHECK(c, hipSetDevice(c->device));
+    multi_work w;
+    CGLB_TRY(itergp_predict_alpha(c, max_error, max_cg_iter, &w));
+    const int gw = cross_multi_width(), r_pad = f_var ? (c->it_cache_rank + gw - 1) / gw * gw : 0;
+    // the gradient block over the cache columns, a row block at a time: at most 2^23 doubles whatever n_new is
+    const int64_t rows_blk = f_var ? std::max<int64_t>(1, std::min<int64_t>(n_new, ((int64_t)1 << 23) / ((int64_t)r_pad * c->D))) : 0;
+    if (f_var) {
+        CGLB_TRY(c->mem.reserve(c, &c->it_blk, &c->it_blk_cap, (size_t)n_new * r_pad * sizeof(double)));
+        CGLB_TRY(c->mem.reserve(c, &c->ig_gk, &c->ig_gk_cap, (size_t)rows_blk * r_pad * c->D * sizeof(double)));
+    }
+    void *xr = nullptr, *xs = nullptr, *xa = nullptr;
+    DevTemps tmp;  // freed on every path below
+    CGLB_TRY(tmp.alloc(c, &xr, (size_t)n_new * c->D * sizeof(double)));
+    CGLB_TRY(tmp.alloc(c, &xs, (size_t)n_new * c->Dp * sizeof(double)));
+    CGLB_TRY(tmp.alloc(c, &xa, (size_t)n_new * sizeof(double)));
+    auto body = [&]() -> int {
+        CGLB_TRY(itergp_predict_mean(c, xnew, n_new, xr, xs, xa, f_mean));  // the mean of both predictives, bitwise
+        // g_mean = grad (K_*f alpha): the stored alpha as the single column of the gradient product
+        int64_t ldv = 0;
+        CGLB_TRY(launch_cross_multi_operand(c, c->it_alpha, 1, &ldv));
+        CGLB_TRY(launch_cross_grad(c, xs, n_new, (const double*)c->cm_vi, ldv, 1, nullptr, 1, (double*)g_mean));
+        if (!f_var) return CGLB_OK;
+        // f_var as cglb_itergp_predict_cached forms it (B = K_*f R through the value kernel, bitwise), then g_var = -2 sum_s B G
+        CGLB_TRY(launch_cross_multi(c, xs, xa, n_new, c->it_cache, c->it_cache_ld, r_pad, c->it_blk, r_pad));
+        CGLB_TRY(launch_cross_multi_var(c, c->it_blk, n_new, r_pad, r_pad, (double*)f_var));
+        for (int64_t i0 = 0; i0 < n_new; i0 += rows_blk) {
+            const int64_t nr = std::min(rows_blk, n_new - i0);
+            CGLB_TRY(launch_cross_grad(c, (const double*)xs + i0 * c->Dp, nr, c->it_cache, c->it_cache_ld, r_pad, nullptr, r_pad, c->ig_gk));
+            CGLB_TRY(launch_input_grad_var(c, c->it_blk + i0 * r_pad, r_pad, c->ig_gk, nr, r_pad, (double*)g_var + i0 * c->D));
+        }
+        return CGLB_OK;
+    };
+    const int rc = body();
+    (void)hipStreamSynchronize(c->stream);  // before `tmp` releases the buffers the kernels use
+    return rc;
+}
+
+int cglb_itergp_paths_solve(cglb_ctx* c, const void* omega, const void* phase, const void* W, const void* eps, int64_t F, int S, double max_error,
+                            int max_cg_iter, void* U_out, int* steps, double* half_rz) {
+    if (c) c->obj_valid = false;
+    if (!c || !omega || !phase || !W || !eps || !U_out || F < 1 || S < 1 || max_cg_iter < 0)
+        return c ? cglb_fail(c, CGLB_ERR_BAD_ARG, "bad argument") : CGLB_ERR_BAD_ARG;
+    CGLB_TRY(require_input_grad_ok(c));
+    HIP_CHECK(c, hipSetDevice(c->device));
+    multi_work w;
+    CGLB_TRY(sample_reserve(c, S, 0, &w));
+    int st = 0;
+    double half = 0.0;
+    auto body = [&]() -> int {
+        CGLB_TRY(sample_solve(c, w, omega, phase, W, eps, F, S, max_error, max_cg_iter, &st, &half));
+        HIP_CHECK(c, hipMemcpyAsync(U_out, c->it_V, (size_t)S * c->N * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+        return CGLB_OK;
+    };
+    const int rc = body();
+    (void)hipStreamSynchronize(c->stream);  // the caller's host arrays are read until here
+    if (rc == CGLB_OK) {
+        if (steps) *steps = st;
+        if (half_rz) *half_rz = half;
+    }
+    return rc;
+}
+
+int cglb_itergp_paths_eval(cglb_ctx* c, const void* xnew, int64_t n_new, const void* omega, const void* phase, const void* W, const void* U, int64_t F, int S,
+                           void* f_out, void* g_out) {
+    if (c) c->obj_valid = false;
+    if (!c || !xnew || !omega || !phase || !W || !U || !f_out || n_new < 0 || F < 1 || S < 1)
+        return c ? cglb_fail(c, CGLB_ERR_BAD_ARG, "bad argument") : CGLB_ERR_BAD_ARG;
+    CGLB_TRY(require_input_grad_ok(c));
+    if (n_new == 0) return CGLB_OK;
+    HIP_CHECK(c, hipSetDevice(c->device));
+    CGLB_TRY(c->mem.reserve(c, &c->ft_G, &c->ft_G_cap, (size_t)n_new * S * sizeof(double)));
+    CGLB_TRY(c->mem.reserve(c, &c->ft_KU, &c->ft_KU_cap, (size_t)n_new * S * sizeof(double)));
+    if (g_out) {
+        CGLB_TRY(c->mem.reserve(c, &c->ig_gk, &c->ig_gk_cap, (size_t)n_new * S * c->D * sizeof(double)));
+        CGLB_TRY(c->mem.reserve(c, &c->ig_gf, &c->ig_gf_cap, (size_t)n_new * S * c->D * sizeof(double)));
+    }
+    void *xr = nullptr, *xs = nullptr, *xa = nullptr;
+    DevTemps tmp;  // freed on every path below
+    CGLB_TRY(tmp.alloc(c, &xr, (size_t)n_new * c->D * sizeof(double)));
+    CGLB_TRY(tmp.alloc(c, &xs, (size_t)n_new * c->Dp * sizeof(double)));
+    CGLB_TRY(tmp.alloc(c, &xa, (size_t)n_new * sizeof(double)));
+    auto body = [&]() -> int {
+        CGLB_TRY(launch_feature_operand(c, omega, phase, W, F, S));
+        if (!g_out) return sample_eval(c, xnew, n_new, xr, xs, xa, (const double*)U, F, S, f_out);  // the value kernels of cglb_itergp_sample, bitwise
+        // values and gradients from the two fused passes
+        HIP_CHECK(c, hipMemcpyAsync(xr, xnew, (size_t)n_new * c->D * sizeof(double), hipMemcpyDefault, c->stream));
+        CGLB_TRY(launch_prep_scaled(c, xr, n_new, xs, xa, true));
+        CGLB_TRY(launch_feature_grad(c, (const double*)xr, n_new, F, S, c->ft_G, S, c->ig_gf));
+        int64_t ldv = 0;
+        CGLB_TRY(launch_cross_multi_operand(c, U, S, &ldv));
+        CGLB_TRY(launch_cross_grad(c, xs, n_new, (const double*)c->cm_vi, ldv, S, c->ft_KU, S, c->ig_gk));
+        return launch_input_grad_paths(c, c->ft_G, c->ft_KU, c->ig_gf, c->ig_gk, n_new, S, (double*)f_out, (double*)g_out);
+    };
+    const int rc = body();
+    (void)hipStreamSynchronize(c->stream);  // before `tmp` releases the buffers the kernels use, and the caller its host arrays
     return rc;
 }
 

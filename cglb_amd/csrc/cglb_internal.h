@@ -259,6 +259,10 @@ struct cglb_ctx {
     double* ft_G = nullptr;                             // [rows][S] feature product of a sampling call (training rows, then the new points)
     double* ft_KU = nullptr;                            // [n_new][S] K_*f U of a sampling call
     size_t ft_G_cap = 0, ft_KU_cap = 0;
+    double* ig_part = nullptr;                          // partial-sum slabs [jsplit][rows][G][Dp + 1] of the input-gradient products
+    double* ig_gk = nullptr;                            // [rows][S][D] gradient block of the cross product (predictive: a row block over the cache columns)
+    double* ig_gf = nullptr;                            // [rows][S][D] gradient block of the feature product of cglb_itergp_paths_eval
+    size_t ig_part_cap = 0, ig_gk_cap = 0, ig_gf_cap = 0;
     hipEvent_t ft_ev[2] = {nullptr, nullptr};           // start | end of the last feature product ("feature_ms")
     bool ft_ev_set = false;
     std::string err;
@@ -417,6 +421,15 @@ int launch_feature_operand(cglb_ctx* c, const void* omega, const void* phase, co
 int launch_feature_multi(cglb_ctx* c, const double* X, int64_t nrows, int64_t F, int S, double* out, int64_t ldo);
 int feature_rows_per_block(const cglb_ctx* c);      // rows per workgroup at the context's width
 void feature_split(const cglb_ctx* c, int64_t nrows, int64_t F, int64_t* jsplit_out, int64_t* jchunk_out);  // feature chunks of one launch
+// kernels_input_grad.hip: value (out may be NULL) and input gradient gout[(i * S + s) * D + k] of the two products above, one evaluation of a pair per
+// group of input_grad_width(c) columns; the operands of launch_cross_multi (hot-scaled rows, Vi [N][ldv]) / of launch_feature_multi (records first).
+// fp64, Dp <= 32.  Bitwise repeatable.
+int launch_cross_grad(cglb_ctx* c, const void* XhRow, int64_t nrows, const double* Vi, int64_t ldv, int S, double* out, int64_t ldo, double* gout);
+int launch_feature_grad(cglb_ctx* c, const double* X, int64_t nrows, int64_t F, int S, double* out, int64_t ldo, double* gout);
+int launch_input_grad_var(cglb_ctx* c, const double* B, int64_t ldb, const double* G, int64_t nrows, int sp, double* g_var);  // g_var[i][k] = -2 sum_s B[i][s] G[i][s][k]
+int launch_input_grad_paths(cglb_ctx* c, const double* Gf, const double* KU, const double* gf, const double* gk, int64_t n, int S, double* f, double* g);
+int input_grad_rows_per_block(const cglb_ctx* c);   // new points per workgroup at the context's width
+int input_grad_width(const cglb_ctx* c);            // columns per group at the context's width (8, 4 or 2)
 // kernels_vec.hip
 // dot, update_v_r, update_p: s columns of length n ([s][n], one launch each; per-column device scalars [s]); s = 1 is the one-column form.
 // A zero denominator gives a zero factor.

@@ -115,6 +115,33 @@ __device__ __forceinline__ double cos_turns(double phi) {
     p = __builtin_fma(p, v, 1.0);
     return __builtin_copysign(p, d);
 }
+// C(v) ~ cos(2 pi sqrt(v)) on 0 <= v <= 1/16: the polynomial of cos_turns, in its Horner order
+__device__ __forceinline__ double cos_turns_poly(double v) {
+    double p = 0x1.179a329ef4140p-2;
+    p = __builtin_fma(p, v, -0x1.b6a6feabe52e9p+0);
+    p = __builtin_fma(p, v, 0x1.f9d2c1f3b2167p+2);
+    p = __builtin_fma(p, v, -0x1.a6d1f12b0bef2p+4);
+    p = __builtin_fma(p, v, 0x1.e1f5068620bcbp+5);
+    p = __builtin_fma(p, v, -0x1.55d3c7e3c9051p+6);
+    p = __builtin_fma(p, v, 0x1.03c1f081b5a9fp+6);
+    p = __builtin_fma(p, v, -0x1.3bd3cc9be45dep+4);
+    return __builtin_fma(p, v, 1.0);
+}
+// cos(2 pi phi) AND sin(2 pi phi) from ONE range reduction (input-gradient feature product, kernels_input_grad.hip).  The cosine is cos_turns
+// operation by operation (bitwise).  The sine reuses its first fold: with t and d = 1/4 - |t| as there, |d| <= 1/4 and
+//   sin(2 pi t) = sign(t) sin(2 pi |t|) = sign(t) cos(2 pi (1/4 - |t|)) = sign(t) C(d^2):
+// the same polynomial on the same interval, at an argument that carries ONE rounding (d; exact for |t| >= 1/8) where the cosine's a = 1/4 - |d|
+// carries up to two.  The sine therefore adds no rounding to the cosine's count and its absolute error bound is the cosine's:
+// CGLB_SIN_TURNS_ERR = CGLB_COS_TURNS_ERR + 0.  sin_turns(integer) = +-C(1/16), the polynomial's residual at a quarter turn (|.| <= 5.7e-17), not an
+// exact zero.  Branch-free, exact reduction at any magnitude below 2^51.  9 instructions on top of cos_turns: mul, 8 fma (the sign is one v_bfi_b32).
+#define CGLB_SIN_TURNS_ERR CGLB_COS_TURNS_ERR
+__device__ __forceinline__ void sincos_turns(double phi, double& cv, double& sv) {
+    const double t = phi - __builtin_rint(phi);
+    const double d = 0.25 - __builtin_fabs(t);
+    const double a = 0.25 - __builtin_fabs(d);
+    cv = __builtin_copysign(cos_turns_poly(a * a), d);
+    sv = __builtin_copysign(cos_turns_poly(d * d), t);
+}
 
 // ---- precision levels of the pair kernels (cglb_set_option "precision") ------------------------------------------------------
 // The figures below are those of the EVALUATOR (table, polynomial, square root) for the squared distance it is handed.  A kernel value of a
@@ -535,6 +562,21 @@ template <typename T, int KIND, bool CLAMP, int PREC> __device__ __forceinline__
         return matern_hpoly<T, KIND>(rT, CGLB_LN2 / CGLB_HOT_UNITS) * exp2_tab<CLAMP, PREC>(-rT, tab);
     } else {
         return (void)cglb_kind_unknown<KIND>{}, T(0);
+    }
+}
+// kernel value AND gradient factor from one exact squared distance in hot units (input-gradient cross product, kernels_input_grad.hip): hv is
+// hfac_hot_from_d2<double, KIND, true, PREC> operation by operation, kv the value form on the same root and the same table exponential
+// (RBF: kv = hv).  Always the range-clamped 2^x.
+template <int KIND, int PREC> __device__ __forceinline__ void kappa_hfac_hot_from_d2(double d2h, const double* __restrict__ tab, double& kv, double& hv) {
+    if constexpr (KIND == CGLB_RBF) {
+        kv = hv = exp2_tab<true, PREC>(-0.5 * d2h, tab);
+    } else {
+        static_assert(cglb_kind_matern<KIND>(), "unknown kernel kind");
+        const double rT = 2.0 * sqrt_pos(d2h);
+        const double e = exp2_tab<true, PREC>(-rT, tab);
+        if constexpr (KIND == CGLB_MATERN32) hv = 3.0 * e;
+        else hv = matern_hpoly<double, KIND>(rT, CGLB_LN2 / CGLB_HOT_UNITS) * e;
+        kv = matern_kpoly<double, KIND>(rT, CGLB_LN2 / CGLB_HOT_UNITS) * e;
     }
 }
 // cooperative load of the exp2 table into LDS (call from every thread of the block, before any early exit)

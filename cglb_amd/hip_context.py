@@ -100,6 +100,7 @@ class HipContext:
         self.r0, self.r1 = (0, self.N) if row_range is None else (int(row_range[0]), int(row_range[1]))
         self.nloc = self.r1 - self.r0
         self._ctx = c_void_p()
+        self.state_version = 0   # counts set_hypers / set_targets: the events after which the library's alpha, preconditioner and variance cache are void
         with torch.cuda.device(self.device):
             stream = torch.cuda.current_stream(self.device).cuda_stream
             rc = self.lib.cglb_ctx_create(byref(self._ctx), self.N, self.r0, self.r1, self.D, self.M,
@@ -154,6 +155,7 @@ class HipContext:
         _lib.check(rc, self._ctx)
         torch.cuda.synchronize(self.device)
         self.noise = float(noise)
+        self.state_version += 1
 
     def setup(self):
         _lib.check(self.lib.cglb_setup(self._ctx), self._ctx)
@@ -175,8 +177,8 @@ class HipContext:
         return out.value
 
     def get_matrix(self, which: str) -> torch.Tensor:
-        idx = {"A": 0, "L": 1, "LB": 2}[which]
-        shape = (self.M, self.nloc) if idx == 0 else (self.M, self.M)
+        idx = {"A": 0, "L": 1, "LB": 2, "alpha": 3}[which]   # "alpha": the stored solve [N] of the iterative exact-GP class
+        shape = (self.M, self.nloc) if idx == 0 else ((self.N,) if idx == 3 else (self.M, self.M))
         out = torch.empty(shape, dtype=self.dtype, device=self.device)
         _lib.check(self.lib.cglb_get_matrix(self._ctx, idx, _ptr(out)), self._ctx)
         return out
@@ -226,6 +228,7 @@ class HipContext:
         _lib.check(self.lib.cglb_set_targets(self._ctx, _ptr(Yt), int(Yt.shape[0])), self._ctx)
         self.P = int(Yt.shape[0])
         self.y = Yt[0].clone() if self.P == 1 else Yt.t().contiguous()
+        self.state_version += 1
 
     def matmat(self, V) -> torch.Tensor:
         """(K_ff + noise I) V for V [N, S]: one evaluation of every kernel value for up to 8 columns (cglb_matmat)."""
@@ -449,6 +452,87 @@ class HipContext:
                                          int(max_cg_iter), _ptr(f), _ptr(U), byref(steps), byref(half))
         _lib.check(rc, self._ctx)
         return IterGPSamples(f, steps.value, half.value, U)
+
+    # -- input gradients of predictive and sample paths (cglb_*_grad_matmat, cglb_itergp_predict_grad, cglb_itergp_paths_*): with respect to the
+    #    raw coordinates of the new points; the scope of itergp_predict, up to 32 input dimensions ----
+    def _out(self, out, shape, what):
+        if out is None:
+            return torch.empty(shape, dtype=self.dtype, device=self.device)
+        if out.device != self.device or out.dtype != self.dtype or tuple(out.shape) != tuple(shape) or not out.is_contiguous():
+            raise ValueError(f"{what} must be a contiguous device tensor {list(shape)} in the context dtype")
+        return out
+
+    def cross_grad_matmat(self, xnew, V, out: Optional[torch.Tensor] = None, gout: Optional[torch.Tensor] = None, with_value=True):
+        """(variance kappa(xnew, X) V [n_new, S] or None, its gradient in xnew [n_new, S, D]) for V [N, S], one evaluation of every pair for both
+        (cglb_cross_grad_matmat).  `out`, `gout`: contiguous device tensors to write into; with_value False: the gradient alone."""
+        xn = self._xnew(xnew)
+        Vt = self._cols(V)
+        n, S = xn.shape[0], int(Vt.shape[0])
+        out = self._out(out, (n, S), "out") if with_value else None
+        gout = self._out(gout, (n, S, self.D), "gout")
+        _lib.check(self.lib.cglb_cross_grad_matmat(self._ctx, _ptr(xn), n, _ptr(Vt), S, _ptr(out), _ptr(gout)), self._ctx)
+        return out, gout
+
+    def time_cross_grad_matmat(self, n_new: int, s: int, reps: int) -> float:
+        """ms per value-and-gradient product with s columns at the first n_new training rows (the operands of time_cross_matmat)."""
+        ms = c_double()
+        _lib.check(self.lib.cglb_time_cross_grad_matmat(self._ctx, int(n_new), int(s), int(reps), byref(ms)), self._ctx)
+        return ms.value
+
+    def feature_grad_matmat(self, x, omega, phase, W, out: Optional[torch.Tensor] = None, gout: Optional[torch.Tensor] = None, with_value=True):
+        """(the feature product of feature_matmat [n_rows, S] or None, its gradient in x [n_rows, S, D]): one phase and one range reduction per
+        (row, feature) for cosine and sine (cglb_feature_grad_matmat)."""
+        xr = None if x is None else self._xnew(x)
+        n = self.N if xr is None else xr.shape[0]
+        om, ph, Wt = self._features(omega, phase, W)
+        S = int(Wt.shape[0])
+        out = self._out(out, (n, S), "out") if with_value else None
+        gout = self._out(gout, (n, S, self.D), "gout")
+        rc = self.lib.cglb_feature_grad_matmat(self._ctx, _ptr(xr), n, _ptr(om), _ptr(ph), _ptr(Wt), int(om.shape[0]), S, _ptr(out), _ptr(gout))
+        _lib.check(rc, self._ctx)
+        return out, gout
+
+    def time_feature_grad_matmat(self, n_rows: int, f: int, s: int, reps: int) -> float:
+        ms = c_double()
+        _lib.check(self.lib.cglb_time_feature_grad_matmat(self._ctx, int(n_rows), int(f), int(s), int(reps), byref(ms)), self._ctx)
+        return ms.value
+
+    def itergp_predict_grad(self, xnew, max_error=1e-3, max_cg_iter=1000, with_var=True):
+        """(mean [n], dmean [n, D], var [n] or None, dvar [n, D] or None) at xnew (cglb_itergp_predict_grad).  with_var needs a valid variance
+        cache (itergp_var_cache): var is the cache's variance and dvar its exact gradient - not the gradient of the exact variance."""
+        xn = self._xnew(xnew)
+        n = xn.shape[0]
+        mean, dmean = self.empty(n), torch.empty((n, self.D), dtype=self.dtype, device=self.device)
+        var = self.empty(n) if with_var else None
+        dvar = torch.empty((n, self.D), dtype=self.dtype, device=self.device) if with_var else None
+        rc = self.lib.cglb_itergp_predict_grad(self._ctx, _ptr(xn), n, float(max_error), int(max_cg_iter), _ptr(mean), _ptr(dmean), _ptr(var), _ptr(dvar))
+        _lib.check(rc, self._ctx)
+        return mean, dmean, var, dvar
+
+    def itergp_paths_solve(self, omega, phase, W, eps, max_error=1e-3, max_cg_iter=1000) -> IterGPSamples:
+        """The solves U [S, N] of S sample paths (cglb_itergp_paths_solve: the first half of itergp_sample); `samples` is None."""
+        om, ph, Wt = self._features(omega, phase, W)
+        S = int(Wt.shape[0])
+        e = torch.as_tensor(eps, dtype=self.dtype).reshape(S, self.N).contiguous().to(self.device)
+        U = torch.empty((S, self.N), dtype=self.dtype, device=self.device)
+        steps, half = c_int(), c_double()
+        rc = self.lib.cglb_itergp_paths_solve(self._ctx, _ptr(om), _ptr(ph), _ptr(Wt), _ptr(e), int(om.shape[0]), S, float(max_error), int(max_cg_iter),
+                                              _ptr(U), byref(steps), byref(half))
+        _lib.check(rc, self._ctx)
+        return IterGPSamples(None, steps.value, half.value, U)
+
+    def itergp_paths_eval(self, xnew, omega, phase, W, U, with_grad=False):
+        """(f [S, n_new], df [S, n_new, D] or None) of the paths with solves U [S, N] at xnew, without a solve (cglb_itergp_paths_eval).  Without
+        gradients the values are bitwise those of itergp_sample."""
+        xn = self._xnew(xnew)
+        om, ph, Wt = self._features(omega, phase, W)
+        S, n = int(Wt.shape[0]), xn.shape[0]
+        Ut = torch.as_tensor(U, dtype=self.dtype).reshape(S, self.N).contiguous().to(self.device)
+        f = torch.empty((S, n), dtype=self.dtype, device=self.device)
+        g = torch.empty((S, n, self.D), dtype=self.dtype, device=self.device) if with_grad else None
+        rc = self.lib.cglb_itergp_paths_eval(self._ctx, _ptr(xn), n, _ptr(om), _ptr(ph), _ptr(Wt), _ptr(Ut), int(om.shape[0]), S, _ptr(f), _ptr(g))
+        _lib.check(rc, self._ctx)
+        return f, g
 
     def grad_kff_multi(self, U, V) -> np.ndarray:
         """[sum_b u_b^T (dK_ff / dl_d) v_b for d < D, sum_b u_b^T kappa v_b] for U, V [N, S]: one evaluation of every kernel value for up to 8 pairs."""

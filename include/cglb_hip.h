@@ -368,6 +368,53 @@ int cglb_time_feature_matmat(cglb_ctx* ctx, int64_t n_rows, int64_t F, int S, in
  * bitwise equal samples.  The stored alpha and the variance cache are left as they are.  Scope of cglb_itergp_predict. */
 int cglb_itergp_sample(cglb_ctx* ctx, const void* xnew, int64_t n_new, const void* omega, const void* phase, const void* W, const void* eps, int64_t F,
                        int S, double max_error, int max_cg_iter, void* f_out, void* U_out, int* steps, double* half_rz);
+/* ---- input gradients of predictive and sample paths (csrc/kernels_input_grad.hip) ----
+ * All gradients below are with respect to the RAW coordinates of the new point (not centred, not scaled).  Scope of every entry: that of
+ * cglb_itergp_predict (fp64, one rank, one target column, the default bound) and d <= 32 - the gradient products have no wide path yet; else
+ * CGLB_ERR_BAD_ARG with a message.  Not covered: fp32, N ranks, wide inputs, the gpr / cglb / sgpr predictors (cglb_cross_grad_matmat serves any V).
+ *
+ * Value and input gradient of K_*f V in one pass over the pairs:
+ *   out [i, s]    =  variance sum_j kappa(x*_i, x_j) V[s, j]
+ *   gout[i, s, k] = -variance sum_j h(x*_i, x_j) (x*_ik - x_jk) / l_k^2 V[s, j]
+ * h: the radial derivative factor of the lengthscale gradient (RBF kappa; Matern-3/2 3 e^(-sqrt3 r); Matern-5/2 (5/3)(1 + sqrt5 r) e^(-sqrt5 r)).
+ * xnew, V: the convention of cglb_cross_matmat; out: dev [n_new, S] or NULL; gout: dev [n_new, S, d], k fastest.  A pair is formed from direct
+ * differences (not the Gram chain), so a coincident pair adds exactly zero to the gradient and nothing is NaN at r = 0; always the range-clamped
+ * 2^x.  One evaluation of a pair serves a group of 8 (d_p <= 8), 4 (d_p <= 16) or 2 columns.  No atomics: bitwise reproducible, and gout is
+ * bitwise the same with out NULL. */
+int cglb_cross_grad_matmat(cglb_ctx* ctx, const void* xnew, int64_t n_new, const void* V, int S, void* out, void* gout);
+/* average duration (ms) of `reps` back-to-back value-and-gradient products with S columns, on the operands of cglb_time_cross_matmat */
+int cglb_time_cross_grad_matmat(cglb_ctx* ctx, int64_t n_new, int S, int reps, double* ms_avg);
+/* Value and input gradient of the random-feature product (arguments of cglb_feature_matmat; out may be NULL; gout: dev [n_rows, S, d]):
+ *   out [i, s]    =  sqrt(2 variance / F) sum_j W[s, j] cos(phi_ij),   phi_ij = sum_k omega[j, k] (x_ik - c_k) / l_k + b_j
+ *   gout[i, s, k] = -sqrt(2 variance / F) sum_j W[s, j] sin(phi_ij) omega[j, k] / l_k
+ * One phase and one range reduction per (row, feature) serve cosine and sine (sincos_turns of csrc/devmath.h: absolute error <= 3e-16 each at any
+ * phase magnitude).  Bitwise reproducible. */
+int cglb_feature_grad_matmat(cglb_ctx* ctx, const void* x, int64_t n_rows, const void* omega, const void* phase, const void* W, int64_t F, int S, void* out,
+                             void* gout);
+/* average duration (ms) of `reps` back-to-back value-and-gradient feature products, on the operands of cglb_time_feature_matmat */
+int cglb_time_feature_grad_matmat(cglb_ctx* ctx, int64_t n_rows, int64_t F, int S, int reps, double* ms_avg);
+/* Predictive mean, variance and their input gradients.  f_mean (dev [n_new]) is bitwise that of cglb_itergp_predict / cglb_itergp_predict_cached
+ * (same solve for alpha, same mean routine); g_mean (dev [n_new, d]) = grad (K_*f alpha), the gradient product with the stored alpha as its single
+ * column: within sqrt(C variance) / l_k sqrt(2 max_error) of the gradient at the exact solve (C = 1, 3, 5/3 by kind: the prior variance of
+ * df / dx_k is C variance / l_k^2, and the bound of cglb_itergp_sample applies with it in the place of the variance).
+ * f_var, g_var (dev [n_new], [n_new, d]): both NULL or both set; they need a valid variance cache (CGLB_ERR_STATE otherwise).  f_var is bitwise
+ * that of cglb_itergp_predict_cached; g_var[i, k] = -2 sum_s B[i, s] G[i, s, k] with B = K_*f R and G its input gradient, contracted in column
+ * order, the new points taken in row blocks so that the G workspace is bounded.  g_var is the exact gradient of the CACHE's variance (the
+ * Galerkin upper bound f - |R^T k_*|^2), not of the exact variance.  The stored alpha and the variance cache stay valid. */
+int cglb_itergp_predict_grad(cglb_ctx* ctx, const void* xnew, int64_t n_new, double max_error, int max_cg_iter, void* f_mean, void* g_mean, void* f_var,
+                             void* g_var);
+/* Sample paths that are solved once.  cglb_itergp_paths_solve is the first half of cglb_itergp_sample (the same code): the right-hand sides
+ * e - Phi(X) w_s - sqrt(noise) eps_s and one batched solve from zero with the class's preconditioner; U_out: dev [S, n_total], bitwise the U_out of
+ * cglb_itergp_sample for the same draws.  cglb_itergp_paths_eval runs NO solve:
+ *   f_s(x*) = mean + Phi(x*) w_s + K_*f U_s          f_out: dev [S, n_new]
+ *   grad f_s(x*) = grad Phi(x*) w_s + grad K_*f U_s   g_out: dev [S, n_new, d], or NULL
+ * With g_out NULL the values go through the kernels of cglb_itergp_sample and are bitwise its samples when U is that call's U_out; with g_out
+ * set, values and gradients come from the two fused products above.  omega, phase, W: as in cglb_itergp_sample, at the CURRENT lengthscales and
+ * data - U is only meaningful at the hyper-parameters and data it was solved at (the caller keeps track; the backend's PathsIterGPR does). */
+int cglb_itergp_paths_solve(cglb_ctx* ctx, const void* omega, const void* phase, const void* W, const void* eps, int64_t F, int S, double max_error,
+                            int max_cg_iter, void* U_out, int* steps, double* half_rz);
+int cglb_itergp_paths_eval(cglb_ctx* ctx, const void* xnew, int64_t n_new, const void* omega, const void* phase, const void* W, const void* U, int64_t F,
+                           int S, void* f_out, void* g_out);
 /* The gradient pass of the class on its own (tests, timing): out host double[d + 1], out[k] = sum_b u_b^T (dK_ff / dl_k) v_b for k < d and
  * out[d] = sum_b u_b^T kappa v_b (kappa = K_ff / variance), b < S.  U, V: dev [S, n_total], pair b contiguous.  Every kernel value is evaluated
  * once per unordered pair for up to 8 pairs of vectors (fp64, d <= 32: csrc/kernels_grad_multi.hip; wider inputs run S single passes); S > 8
@@ -389,7 +436,8 @@ int cglb_select_inducing(cglb_ctx* ctx, const double* lengthscales, double varia
                          double* trace_out);
 
 /* ---- introspection / measurement ------------------------------------------------------------------ */
-/* Copy common-term matrices out (tests): which = 0:A [m,n_local] 1:L [m,m] lower 2:LB [m,m] lower; dst: any. */
+/* Copy common-term matrices out (tests): which = 0:A [m,n_local] 1:L [m,m] lower 2:LB [m,m] lower; 3: the stored alpha [n_total] of the
+ * iterative exact-GP class (fp64; CGLB_ERR_STATE without one); dst: any. */
 int cglb_get_matrix(cglb_ctx* ctx, int which, void* dst);
 /* Average duration (ms, HIP events on the ctx stream) of `reps` back-to-back launches of one kernel family:
  * which = 0: K_ff mat-vec (pair kernel + slab combine), 1: preconditioner apply, 2: gradient bilinear pass,
