@@ -318,6 +318,24 @@ struct DevTemps {
     }
 };
 
+// The new points of one call, staged on the device for the kernels it enqueues on c->stream: xr [n][D] the rows as given, xs [n][Dp] and xa [n]
+// their scaled form (absent where a call reads the raw rows alone).  The destructor waits for the stream and only then frees: no buffer, of these
+// or of `tmp`, is released while a kernel enqueued by the call may read it, on any exit path, and the caller's host arrays are its own again.
+// (Methods: cglb_api.hip.)
+struct StagedPoints {
+    cglb_ctx* c;
+    int64_t n = 0;
+    size_t esz = 0;
+    void *xr = nullptr, *xs = nullptr, *xa = nullptr;
+    DevTemps tmp;  // the further temporaries of the call
+    explicit StagedPoints(cglb_ctx* cc) : c(cc) {}
+    StagedPoints(const StagedPoints&) = delete;
+    ~StagedPoints() { (void)hipStreamSynchronize(c->stream); }  // `tmp` frees after this body
+    int alloc(int64_t n_points, size_t elem, bool scaled = true);  // n points of element size elem; not scaled: xr alone
+    int stage(const void* xnew, bool hot = true);                  // xr <- xnew (host or device), then (xs, xa) in hot or plain units where allocated
+    int scale(bool hot);                                           // (xs, xa) from xr once more, in the units asked for
+};
+
 static inline int pad_dim(int d) {
     const int sizes[] = {1, 2, 3, 4, 6, 8, 10, 12, 16, 20, 24, 28, 32};  // 10, 20 and 28: the reference's own data sets have D = 9, 17, 18, 26, 27
     for (int s : sizes)
@@ -341,7 +359,6 @@ int wide_after_hypers(cglb_ctx* c);
 int wide_prep_hot(cglb_ctx* c);   // Xh (N x Dh, zero padded), xah in hot units for the register-resident mat-vec of a mid-width context
 int wide_kuf(cglb_ctx* c);
 int wide_kuu(cglb_ctx* c);
-int wide_kus(cglb_ctx* c, const void* XsNew, int64_t n_new, int64_t ld, void* out);
 int wide_kpanel(cglb_ctx* c, const void* Zs, int M, const void* XsNew, int64_t n_new, int64_t ld, void* out);  // out[m * ld + n] = var K(z_m, xnew_n), any two scaled sets
 // out[i * ldo + s] = var * sum_j kappa(row_i, x_j) Vi[j * ldv + s], s < S (fp64): what launch_cross_multi is to narrow inputs, through the Gram tiles
 int wide_cross_multi(cglb_ctx* c, const void* XsRow, const void* xaRow, int64_t nrows, const double* Vi, int64_t ldv, int S, double* out, int64_t ldo);

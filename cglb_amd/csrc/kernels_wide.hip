@@ -477,9 +477,6 @@ int wide_kpanel(cglb_ctx* c, const void* Zs, int M, const void* XsNew, int64_t n
     return CGLB_OK;
 }
 
-// out[m * ld + n] = var * K(z_m, xnew_n)   (models.py:337)
-int wide_kus(cglb_ctx* c, const void* XsNew, int64_t n_new, int64_t ld, void* out) { return wide_kpanel(c, c->Zs, c->M, XsNew, n_new, ld, out); }
-
 // Multi-column cross product of wide inputs (the cached predictive variance of the iterative exact GP class): per tile the Gram GEMM, the
 // kernel profile in place, then one GEMM of the tile against the matching rows of Vi, accumulated over the column tiles.  Vi [N][ldv]
 // row-major is column-major ldv x N; out [nrows][ldo] row-major is column-major ldo x nrows: out^T = Vi_J^T K_IJ^T.
