@@ -118,6 +118,10 @@ SIGNATURES = {
     "cglb_feature_grad_matmat": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p]),
     "cglb_time_feature_grad_matmat": (c_int, [c_void_p, c_int64, c_int64, c_int, c_int, POINTER(c_double)]),
     "cglb_itergp_predict_grad": (c_int, [c_void_p, c_void_p, c_int64, c_double, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "cglb_cross_grad_weighted": (c_int, [c_void_p, c_int, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "cglb_predict_grad": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "cglb_gpr_predict_grad": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "cglb_time_predict_grad": (c_int, [c_void_p, c_int64, c_int, c_int, POINTER(c_double)]),
     "cglb_itergp_paths_solve": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_double, c_int, c_void_p, POINTER(c_int),
                                         POINTER(c_double)]),
     "cglb_itergp_paths_eval": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p]),

@@ -616,6 +616,17 @@ class PredictCG(LowerBoundCG):
         _refuse_full_cov(full_cov)
         model, hip = self.model, self.model.hip
         with torch.no_grad():
+            self._solve()
+            if getattr(model, "num_outputs", 1) > 1:
+                f_mean, f_var = hip.predict_multi(self.v_vec, xnew)                    # f_mean [n_new, P]; one variance for all outputs
+                return f_mean, f_var.reshape(-1, 1).repeat(1, f_mean.shape[1])         # tiled over the outputs (tensorflow/models.py:245)
+            f_mean, f_var = hip.predict(self.v_vec.reshape(-1), xnew)                  # models.py:334-352
+        return f_mean.reshape(-1, 1), f_var.reshape(-1, 1)
+
+    def _solve(self):
+        """The solve for v at the current hyper-parameters, once (until clear_cache)."""
+        model, hip = self.model, self.model.hip
+        with torch.no_grad():
             if not self.cached:
                 model.push_hypers(get_cholesky_jitter())
                 hip.setup()                                                            # models.py:327
@@ -630,11 +641,6 @@ class PredictCG(LowerBoundCG):
                     new_v, _stats = self.cg_opt(KernelOperator(hip), err, self.v_vec, NystromPreconditioner(hip))  # :329
                 self.v_vec.data.copy_(new_v.reshape(self.v_vec.shape))
                 self.cached = True
-            if getattr(model, "num_outputs", 1) > 1:
-                f_mean, f_var = hip.predict_multi(self.v_vec, xnew)                    # f_mean [n_new, P]; one variance for all outputs
-                return f_mean, f_var.reshape(-1, 1).repeat(1, f_mean.shape[1])         # tiled over the outputs (tensorflow/models.py:245)
-            f_mean, f_var = hip.predict(self.v_vec.reshape(-1), xnew)                  # models.py:334-352
-        return f_mean.reshape(-1, 1), f_var.reshape(-1, 1)
 
 
 class _Predict(nn.Module):
@@ -785,6 +791,105 @@ class PredictGradIterGPR(nn.Module):
                 hip.itergp_var_cache(rank)
             mean, dmean, var, dvar = hip.itergp_predict_grad(xnew, self.max_error, model.max_cg_iter, with_var=rank > 0)
         return mean.reshape(-1, 1), dmean, None if var is None else var.reshape(-1, 1), dvar
+
+
+class _PredictValues(torch.autograd.Function):
+    """(mean, var) [n, 1] each of a gradient predictor with the library's gradients: backward contracts the two incoming gradients with the stored
+    [n, d] blocks - the only arithmetic torch does."""
+
+    @staticmethod
+    def forward(ctx, predictor, x):
+        mean, dmean, var, dvar = predictor.forward(x)
+        ctx.save_for_backward(dmean, dvar)
+        ctx.x_shape, ctx.x_device = x.shape, x.device
+        return mean, var
+
+    @staticmethod
+    def backward(ctx, grad_mean, grad_var):
+        dmean, dvar = ctx.saved_tensors
+        g = grad_mean.to(dmean.device).reshape(-1, 1) * dmean + grad_var.to(dvar.device).reshape(-1, 1) * dvar
+        return None, g.reshape(ctx.x_shape).to(ctx.x_device)
+
+
+class _PredictGrad:
+    """What the gradient predictors of the cglb / sgpr / gpr classes share: `forward(xnew)` -> (mean [n, 1], dmean [n, d], var [n, 1], dvar [n, d]),
+    the gradients with respect to the new points; `mean_and_variance(xnew)` -> (mean, var), differentiable by autograd when `xnew.requires_grad`
+    (one torch.autograd.Function whose backward contracts the incoming gradients with dmean and dvar), so any torch acquisition function
+    differentiates through the library."""
+
+    @staticmethod
+    def _refuse(model):
+        name = type(model).__name__
+        if getattr(model, "num_outputs", 1) > 1:
+            raise NotImplementedError(f"the input gradients of {name} are not available for more than one target column (only CGLB takes [N, P] targets)")
+        if getattr(model.hip, "world", 1) > 1:
+            raise NotImplementedError(_ONE_RANK.format(name=f"the input gradients of {name}"))
+
+    def value_and_grad(self, xnew):
+        raise NotImplementedError()
+
+    def forward(self, xnew: Tensor):
+        with torch.no_grad():
+            mean, dmean, var, dvar = self.value_and_grad(xnew.detach())
+        return mean.reshape(-1, 1), dmean, var.reshape(-1, 1), dvar
+
+    def mean_and_variance(self, xnew: Tensor):
+        if isinstance(xnew, torch.Tensor) and xnew.requires_grad:
+            return _PredictValues.apply(self, xnew)
+        mean, _, var, _ = self.forward(xnew)
+        return mean, var
+
+
+class PredictGradCG(_PredictGrad, PredictCG):
+    """`PredictGradCG(model)(xnew)`: PredictCG (its solve for v, cached until `clear_cache`) with the input gradients of mean and variance
+    (cglb_predict_grad).  Takes CGLB, CGLBN2M and CGLBNM2; fp64, one rank, one target column, up to 32 input dimensions."""
+
+    def __init__(self, model: CGLB, cg_opt: Optional[ConjugateGradient] = None):
+        if not isinstance(model, CGLB):
+            raise ValueError(f"CGLB model expected in the constructor of the {self.__class__}")
+        self._refuse(model)
+        PredictCG.__init__(self, model, cg_opt)
+
+    def value_and_grad(self, xnew):
+        self._solve()
+        return self.model.hip.predict_grad(self.v_vec.reshape(-1), xnew)
+
+
+class PredictGradSGPR(_PredictGrad, nn.Module):
+    """`PredictGradSGPR(model)(xnew)`: Titsias' predictive (PredictSGPR: v = 0, no solve) with the input gradients of mean and variance.  Takes
+    SGPR and SGPRN2M."""
+
+    def __init__(self, model: SGPR):
+        if not isinstance(model, SGPR) or isinstance(model, CGLB):
+            raise ValueError(f"SGPR model expected in the constructor of the {self.__class__}")
+        self._refuse(model)
+        nn.Module.__init__(self)
+        object.__setattr__(self, "model", model)
+        self.cached = False
+
+    def value_and_grad(self, xnew):
+        model = self.model
+        if not self.cached:
+            model.push_hypers(get_cholesky_jitter())
+            model.hip.setup()
+            self.cached = True
+        return model.hip.predict_grad(model._zero_v, xnew)
+
+
+class PredictGradGPR(_PredictGrad, nn.Module):
+    """`PredictGradGPR(model)(xnew)`: predict_f of the exact model (PredictGPR) with the input gradients of mean and variance
+    (cglb_gpr_predict_grad); this class's variance, and so its gradient, is exact."""
+
+    def __init__(self, model: ExactGPR):
+        if not isinstance(model, ExactGPR):
+            raise ValueError(f"ExactGPR model expected in the constructor of the {self.__class__}")
+        self._refuse(model)
+        nn.Module.__init__(self)
+        object.__setattr__(self, "model", model)
+
+    def value_and_grad(self, xnew):
+        self.model.push_hypers()
+        return self.model.hip.gpr_predict_grad(xnew)
 
 
 class _PathValues(torch.autograd.Function):

@@ -1056,6 +1056,7 @@ int cglb_ctx_destroy(cglb_ctx* c) {
     for (hipEvent_t ev : c->it_ev) if (ev) (void)hipEventDestroy(ev);
     for (hipEvent_t ev : c->it_cev) if (ev) (void)hipEventDestroy(ev);
     for (hipEvent_t ev : c->ft_ev) if (ev) (void)hipEventDestroy(ev);
+    for (hipEvent_t ev : c->pg_ev) if (ev) (void)hipEventDestroy(ev);
     if (c->it_log.host_pap) (void)hipHostFree(c->it_log.host_pap);
     for (hipEvent_t ev : c->k1_events) (void)hipEventDestroy(ev);
     for (hipEvent_t ev : c->eval_events) (void)hipEventDestroy(ev);
@@ -1562,7 +1563,9 @@ static int predict_u_local(cglb_ctx* c, const void* Kv_local, void* u_partial) {
 }
 
 // c = LB^-1 u / sigma (:343) into w_u, then for the n_new points of xnew: cg_mean (:334), K_us panel, tmp1, tmp2 (:344-345), mean / var (:347-351)
-static int predict_rows(cglb_ctx* c, const void* v_full, const void* u, const void* xnew, int64_t n_new, void* f_mean, void* f_var) {
+// g_mean (and g_var with it, or NULL): the input gradients of both outputs besides (cglb_predict_grad; fp64, narrow inputs), from the same panels
+static int predict_rows(cglb_ctx* c, const void* v_full, const void* u, const void* xnew, int64_t n_new, void* f_mean, void* f_var, void* g_mean = nullptr,
+                        void* g_var = nullptr) {
     const int M = c->M;
     const int64_t ld = (n_new + 7) & ~(int64_t)7;
     void *t1 = nullptr, *t2 = nullptr;
@@ -1573,6 +1576,17 @@ static int predict_rows(cglb_ctx* c, const void* v_full, const void* u, const vo
     CGLB_TRY(pts.stage(xnew, true));                                                       // hot units for the pair kernel
     if (c->quad_term == 1) HIP_CHECK(c, hipMemsetAsync(f_mean, 0, (size_t)n_new * c->esz, c->stream));  // cg_mean = 0 at v = 0
     else CGLB_TRY(launch_cross_matvec(c, pts.xs, pts.xa, n_new, v_full, f_mean));         // cg_mean = ksf @ v   (models.py:334)
+    void *xh = nullptr, *qv = nullptr;
+    if (g_mean) {  // grad (K_*f v) while the new points are in hot units, which the row-weighted kernel below reads from a copy
+        CGLB_TRY(pts.tmp.alloc(c, &xh, (size_t)n_new * c->Dp * sizeof(double)));
+        CGLB_TRY(pts.tmp.alloc(c, &qv, (size_t)M * sizeof(double)));
+        HIP_CHECK(c, hipMemcpyAsync(xh, pts.xs, (size_t)n_new * c->Dp * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+        if (c->quad_term != 1) {
+            int64_t ldv = 0;
+            CGLB_TRY(launch_cross_multi_operand(c, v_full, 1, &ldv));
+            CGLB_TRY(launch_cross_grad(c, xh, n_new, (const double*)c->cm_vi, ldv, 1, nullptr, 1, (double*)g_mean));
+        }
+    }
     CGLB_TRY(pts.scale(false));                                                            // plain scaled units for the K_us panel
     if (u != c->w_u) HIP_CHECK(c, hipMemcpyAsync(c->w_u, u, (size_t)M * c->esz, hipMemcpyDeviceToDevice, c->stream));
     CGLB_DISPATCH_T(c->dtype, {
@@ -1592,7 +1606,24 @@ static int predict_rows(cglb_ctx* c, const void* v_full, const void* u, const vo
                            (const T*)c->w_u, n_new, (T)c->mean, (T)c->var, (T*)f_mean, (T*)f_var);
     });
     CGLB_LAUNCH_CHECK(c);
-    return CGLB_OK;
+    if (!g_mean) return CGLB_OK;
+    // q = L^-T LB^-T c; C^T = L^-T (tmp1 - LB^-T tmp2) in place of tmp2 (two more solves from the right on the [M][ld] panels); one pass over the
+    // n_new x M pairs against Z for both sums
+    const double one = 1.0, mone = -1.0;
+    HIP_CHECK(c, hipMemcpyAsync(qv, c->w_u, (size_t)M * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+    BLAS_CHECK(c, rocblas_dtrsv(c->blas, rocblas_fill_lower, rocblas_operation_transpose, rocblas_diagonal_non_unit, M, (const double*)c->LBc, M, (double*)qv, 1));
+    BLAS_CHECK(c, rocblas_dtrsv(c->blas, rocblas_fill_lower, rocblas_operation_transpose, rocblas_diagonal_non_unit, M, (const double*)c->Lc, M, (double*)qv, 1));
+    if (g_var) {
+        BLAS_CHECK(c, rocblas_dtrsm(c->blas, rocblas_side_right, rocblas_fill_lower, rocblas_operation_none, rocblas_diagonal_non_unit, (int)n_new, M, &one,
+                                    (const double*)c->LBc, M, (double*)t2, (int)ld));
+        // t2 <- t1 - t2 (geam over the (ld x M) column-major panels)
+        BLAS_CHECK(c, rocblas_dgeam(c->blas, rocblas_operation_none, rocblas_operation_none, (int)n_new, M, &one, (const double*)t1, (int)ld, &mone,
+                                    (const double*)t2, (int)ld, (double*)t2, (int)ld));
+        BLAS_CHECK(c, rocblas_dtrsm(c->blas, rocblas_side_right, rocblas_fill_lower, rocblas_operation_none, rocblas_diagonal_non_unit, (int)n_new, M, &one,
+                                    (const double*)c->Lc, M, (double*)t2, (int)ld));
+    }
+    return launch_weighted_grad(c, c->ls, c->var, (const double*)xh, n_new, (const double*)c->Zh, M, (const double*)qv, g_var ? (const double*)t2 : nullptr, ld,
+                                nullptr, (double*)g_mean, c->quad_term != 1, nullptr, (double*)g_var, -2.0);
 }
 
 int cglb_predict(cglb_ctx* c, const void* v_full, const void* xnew, int64_t n_new, void* f_mean, void* f_var) {
@@ -1607,6 +1638,75 @@ int cglb_predict(cglb_ctx* c, const void* v_full, const void* xnew, int64_t n_ne
     else CGLB_TRY(launch_kff_matvec(c, v_full, c->w_Kv, nullptr));          // cov @ v            (:335)
     CGLB_TRY(predict_u_local(c, c->w_Kv, c->w_u));                          // a_res = A @ res    (:340)
     return predict_rows(c, v_full, c->w_u, xnew, n_new, f_mean, f_var);
+}
+
+// the scope of the input-gradient entries of the sparse predictors: fp64, one rank, one target column, at most 32 input dimensions
+static int require_predict_grad_ok(cglb_ctx* c) {
+    if (c->dtype != CGLB_F64)
+        return cglb_fail(c, CGLB_ERR_BAD_ARG, "the input gradients of the predictive need an fp64 context (-t fp64): the gradient kernels have no fp32 instances");
+    if (c->par_world > 1 || c->comm) return cglb_fail(c, CGLB_ERR_BAD_ARG, "the input gradients of the predictive are not available on more than one rank");
+    if (c->p != 1) return cglb_fail(c, CGLB_ERR_BAD_ARG, "the input gradients of the predictive take one target column");
+    if (is_wide(c)) return cglb_fail(c, CGLB_ERR_BAD_ARG, "the input-gradient products have no wide path yet: they are available up to 32 input dimensions");
+    return CGLB_OK;
+}
+
+int cglb_predict_grad(cglb_ctx* c, const void* v_full, const void* xnew, int64_t n_new, void* f_mean, void* g_mean, void* f_var, void* g_var) {
+    if (c) c->obj_valid = false;
+    if (!c || !v_full || !xnew || !f_mean || !g_mean || (!f_var) != (!g_var) || n_new < 0) return c ? cglb_fail(c, CGLB_ERR_BAD_ARG, "bad argument") : CGLB_ERR_BAD_ARG;
+    CGLB_TRY(require_predict_grad_ok(c));
+    CGLB_TRY(require_single(c));
+    CGLB_TRY(require_terms(c));
+    CGLB_TRY(require_variant_ok(c));
+    if (n_new == 0) return CGLB_OK;
+    HIP_CHECK(c, hipSetDevice(c->device));
+    DevTemps tmp;
+    void* var_tmp = nullptr;  // the value routine always writes a variance
+    if (!f_var) CGLB_TRY(tmp.alloc(c, &var_tmp, (size_t)n_new * sizeof(double)));
+    // the steps of cglb_predict, then the gradients from its panels
+    if (c->quad_term == 1) HIP_CHECK(c, hipMemsetAsync(c->w_Kv, 0, (size_t)c->nloc * c->esz, c->stream));
+    else CGLB_TRY(launch_kff_matvec(c, v_full, c->w_Kv, nullptr));
+    CGLB_TRY(predict_u_local(c, c->w_Kv, c->w_u));
+    return predict_rows(c, v_full, c->w_u, xnew, n_new, f_mean, f_var ? f_var : var_tmp, g_mean, g_var);
+}
+
+int cglb_cross_grad_weighted(cglb_ctx* c, int set, const void* xnew, int64_t n_new, const void* u, const void* Wt, int64_t ldw, void* out_u, void* gout_u,
+                             void* out_w, void* gout_w) {
+    if (c) c->obj_valid = false;
+    if (!c || !xnew || n_new < 0 || (set != 0 && set != 1)) return c ? cglb_fail(c, CGLB_ERR_BAD_ARG, "bad argument") : CGLB_ERR_BAD_ARG;
+    CGLB_TRY(require_predict_grad_ok(c));
+    CGLB_TRY(require_single(c));
+    if (!c->have_data || !c->have_hypers) return cglb_fail(c, CGLB_ERR_STATE, "set_data and set_hypers must precede the row-weighted gradient product");
+    if (!u && !Wt) return cglb_fail(c, CGLB_ERR_BAD_ARG, "the row-weighted gradient product needs at least one of the weights u and Wt");
+    if ((!u && (out_u || gout_u)) || (!Wt && (out_w || gout_w))) return cglb_fail(c, CGLB_ERR_BAD_ARG, "the outputs of an absent weight must be NULL");
+    if (Wt && ldw < n_new) return cglb_fail(c, CGLB_ERR_BAD_ARG, "the leading dimension of Wt must be at least n_new");
+    if (n_new == 0) return CGLB_OK;
+    HIP_CHECK(c, hipSetDevice(c->device));
+    StagedPoints pts(c);
+    CGLB_TRY(pts.alloc(n_new, sizeof(double)));
+    CGLB_TRY(pts.stage(xnew, true));
+    return launch_weighted_grad(c, c->ls, c->var, (const double*)pts.xs, n_new, set == 0 ? (const double*)c->Xh : (const double*)c->Zh, set == 0 ? c->N : (int64_t)c->M,
+                                (const double*)u, (const double*)Wt, ldw, (double*)out_u, (double*)gout_u, false, (double*)out_w, (double*)gout_w, 1.0);
+}
+
+int cglb_time_predict_grad(cglb_ctx* c, int64_t n_new, int with_grad, int reps, double* ms_avg) {
+    if (c) c->obj_valid = false;
+    if (!c || !ms_avg || reps <= 0 || n_new < 1) return c ? cglb_fail(c, CGLB_ERR_BAD_ARG, "bad argument") : CGLB_ERR_BAD_ARG;
+    CGLB_TRY(require_predict_grad_ok(c));
+    CGLB_TRY(require_terms(c));
+    if (n_new > c->N) return cglb_fail(c, CGLB_ERR_BAD_ARG, "the timed predictive takes its new points from the training rows: n_new <= n_total");
+    HIP_CHECK(c, hipSetDevice(c->device));
+    CGLB_TRY(ensure_zero_vec(c));
+    void *fm = nullptr, *fv = nullptr, *gm = nullptr, *gv = nullptr;
+    DevTemps tmp;
+    CGLB_TRY(tmp.alloc(c, &fm, (size_t)n_new * sizeof(double)));
+    CGLB_TRY(tmp.alloc(c, &fv, (size_t)n_new * sizeof(double)));
+    CGLB_TRY(tmp.alloc(c, &gm, (size_t)n_new * c->D * sizeof(double)));
+    CGLB_TRY(tmp.alloc(c, &gv, (size_t)n_new * c->D * sizeof(double)));
+    const int rc = time_repeated(c, reps, [&]() -> int {
+        return with_grad ? cglb_predict_grad(c, c->w_zero, c->X, n_new, fm, gm, fv, gv) : cglb_predict(c, c->w_zero, c->X, n_new, fm, fv);
+    }, ms_avg);
+    (void)hipStreamSynchronize(c->stream);
+    return rc;
 }
 
 int cglb_shard_predict_u(cglb_ctx* c, const void* Kv_local, void* u_partial) {
@@ -1804,6 +1904,10 @@ int cglb_get_stat(cglb_ctx* c, const char* name, double* value) {
         for (int k = 0; k < 4; ++k)
             if (!strcmp(name, names[k])) { CGLB_TRY(eval_collect(c)); *value = c->eval_ms[k]; return CGLB_OK; }
         if (!strcmp(name, "eval_count")) { CGLB_TRY(eval_collect(c)); *value = (double)c->eval_count; return CGLB_OK; }
+    }
+    {
+        const int rc = predict_grad_stat(c, name, value);  // "predict_grad_kernel_ms"
+        if (rc != -1) return rc;
     }
     {
         const int rc = gpr_stat(c, name, value);  // "gpr_bytes", "gpr_fill_ms" | "gpr_factor_ms" | "gpr_solve_ms" | "gpr_inverse_ms" | "gpr_grad_ms"

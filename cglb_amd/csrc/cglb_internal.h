@@ -219,6 +219,9 @@ struct cglb_ctx {
     int* gpr_info = nullptr;                            // pivot status of the current diagonal block; potri status
     double *gpr_Ks = nullptr, *gpr_xnew = nullptr;      // prediction: K_f* (N x batch, column-major) and the scaled new points
     size_t gpr_Ks_cap = 0, gpr_xnew_cap = 0;
+    double *gpr_Xh = nullptr, *gpr_xh = nullptr, *gpr_Ct = nullptr;  // input gradients: X and the batch in hot units at gpr_ls, C = K^-1 K_f* as [N][ld]
+    size_t gpr_xh_cap = 0, gpr_Ct_cap = 0;
+    bool gpr_hot_valid = false;                         // gpr_Xh holds X at the current data and lengthscales
     size_t gpr_bytes = 0;                               // device bytes the pool holds (cglb_get_stat "gpr_bytes")
     hipEvent_t gpr_ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};  // start | fill | factor | solves | inverse | gradient of the last evaluation
     int gpr_ev_last = 0;                                // index of the last event that evaluation recorded (2: no solve reached, 3: value only, 5: with gradient)
@@ -265,6 +268,8 @@ struct cglb_ctx {
     size_t ig_part_cap = 0, ig_gk_cap = 0, ig_gf_cap = 0;
     hipEvent_t ft_ev[2] = {nullptr, nullptr};           // start | end of the last feature product ("feature_ms")
     bool ft_ev_set = false;
+    hipEvent_t pg_ev[2] = {nullptr, nullptr};           // start | end of the last row-weighted gradient product ("predict_grad_kernel_ms")
+    bool pg_ev_set = false;
     std::string err;
 };
 
@@ -445,6 +450,14 @@ int launch_cross_grad(cglb_ctx* c, const void* XhRow, int64_t nrows, const doubl
 int launch_feature_grad(cglb_ctx* c, const double* X, int64_t nrows, int64_t F, int S, double* out, int64_t ldo, double* gout);
 int launch_input_grad_var(cglb_ctx* c, const double* B, int64_t ldb, const double* G, int64_t nrows, int sp, double* g_var);  // g_var[i][k] = -2 sum_s B[i][s] G[i][s][k]
 int launch_input_grad_paths(cglb_ctx* c, const double* Gf, const double* KU, const double* gf, const double* gk, int64_t n, int S, double* f, double* g);
+// kernels_predict_grad.hip: row-weighted value and input gradient of a cross product between two explicit hot-unit point sets (lengthscales ls, host):
+// out_u / gout_u with the shared weight u [npts], out_w / gout_w with new point i's own weights Wt[m * ldw + i]; gout_w times wscale, gout_u added to if add_u
+int launch_weighted_grad(cglb_ctx* c, const double* ls, double var, const double* XhRow, int64_t nrows, const double* Ph, int64_t npts, const double* u,
+                         const double* Wt, int64_t ldw, double* out_u, double* gout_u, bool add_u, double* out_w, double* gout_w, double wscale);
+int launch_hot_points(cglb_ctx* c, const double* ls, const double* x, int64_t n, double* out);  // out [n][Dp] <- x [n][D] in hot units at ls
+int launch_transpose(cglb_ctx* c, const double* src, int64_t lds, int64_t rows, int64_t cols, double* dst, int64_t ldd);  // dst[j * ldd + i] = src[i * lds + j]
+int predict_grad_rows_per_block(const cglb_ctx* c);  // new points per workgroup of the row-weighted kernel at the context's width
+int predict_grad_stat(cglb_ctx* c, const char* name, double* value);  // "predict_grad_kernel_ms"; -1: not this name
 int input_grad_rows_per_block(const cglb_ctx* c);   // new points per workgroup at the context's width
 int input_grad_width(const cglb_ctx* c);            // columns per group at the context's width (8, 4 or 2)
 // kernels_vec.hip

@@ -334,6 +334,7 @@ int gpr_evaluate(cglb_ctx* c, double* out3, double* grad) {
     const int D = c->D;
     const int64_t nb = std::min<int64_t>(c->gpr_block, (N + 63) & ~(int64_t)63);
     c->gpr_factored = false;
+    c->gpr_hot_valid = false;
     CGLB_TRY(gpr_mark(c, 0));
     CGLB_TRY(gpr_fill(c, nb));
     CGLB_TRY(gpr_mark(c, 1));
@@ -375,12 +376,83 @@ int gpr_evaluate(cglb_ctx* c, double* out3, double* grad) {
     return CGLB_OK;
 }
 
+// cglb_gpr_predict, and with g_mean set cglb_gpr_predict_grad (var_out / g_var NULL: the mean and its gradient alone), batch by batch
+int gpr_predict_batches(cglb_ctx* c, const void* xnew, int64_t n_new, double* mean_out, double* g_mean, double* var_out, double* g_var) {
+    CGLB_TRY(gpr_require(c));
+    if (!c->gpr_factored) CGLB_TRY(gpr_evaluate(c, nullptr, nullptr));
+    HIP_CHECK(c, hipSetDevice(c->device));
+    const int64_t N = c->N;
+    const int D = c->D;
+    const int64_t bmax = std::min(GPR_PREDICT_BATCH, n_new);
+    if (bmax == 0) return CGLB_OK;
+    const int64_t ldc = (bmax + 7) & ~(int64_t)7;
+    if (g_mean) {  // X and the batch in the pair kernel's units, C as [N][ldc]: checked against the free memory like the factor
+        size_t need = 0;
+        if (!c->gpr_Xh) need += (size_t)N * c->Dp * sizeof(double);
+        if (c->gpr_Ks_cap < (size_t)N * bmax * sizeof(double)) need += (size_t)N * bmax * sizeof(double);
+        if (g_var && c->gpr_Ct_cap < (size_t)N * ldc * sizeof(double)) need += (size_t)N * ldc * sizeof(double);
+        if (need > 0) {
+            size_t free_b = 0, total_b = 0;
+            HIP_CHECK(c, hipMemGetInfo(&free_b, &total_b));
+            if (need > free_b)
+                return cglb_fail(c, CGLB_ERR_HIP, "the exact GPR input gradients at N = " + std::to_string(N) + " need " + std::to_string(need >> 20) +
+                                                      " MiB for the panels of a batch but only " + std::to_string(free_b >> 20) + " MiB of device memory are free");
+        }
+        CGLB_TRY(gpr_alloc(c, &c->gpr_Xh, (size_t)N * c->Dp));
+        CGLB_TRY(gpr_reserve(c, &c->gpr_xh, &c->gpr_xh_cap, (size_t)bmax * c->Dp));
+        if (g_var) CGLB_TRY(gpr_reserve(c, &c->gpr_Ct, &c->gpr_Ct_cap, (size_t)N * ldc));
+        if (!c->gpr_hot_valid) {  // once per hyper-parameter set
+            CGLB_TRY(launch_hot_points(c, c->gpr_ls.data(), (const double*)c->X, N, c->gpr_Xh));
+            c->gpr_hot_valid = true;
+        }
+    }
+    CGLB_TRY(gpr_reserve(c, &c->gpr_Ks, &c->gpr_Ks_cap, (size_t)N * bmax));
+    CGLB_TRY(gpr_reserve(c, &c->gpr_xnew, &c->gpr_xnew_cap, (size_t)2 * bmax * D));
+    DevTemps tmp;
+    double* var_tmp = nullptr;  // the column-norm kernel always writes a variance
+    if (!var_out) CGLB_TRY(tmp.alloc(c, (void**)&var_tmp, (size_t)bmax * sizeof(double)));
+    const double one = 1.0, zero = 0.0;
+    int rc = CGLB_OK;
+    for (int64_t off = 0; off < n_new && rc == CGLB_OK; off += GPR_PREDICT_BATCH) rc = [&]() -> int {
+        const int64_t b = std::min(GPR_PREDICT_BATCH, n_new - off);
+        double* raw = c->gpr_xnew + bmax * D;
+        HIP_CHECK(c, hipMemcpyAsync(raw, (const double*)xnew + off * D, (size_t)b * D * sizeof(double), hipMemcpyDefault, c->stream));
+        hipLaunchKernelGGL(n2m_scale_kernel, dim3((unsigned)std::min<int64_t>(1024, (b * D + 255) / 256)), dim3(256), 0, c->stream, (const double*)raw,
+                           (const double*)c->gpr_lsd, b, D, c->gpr_xnew);
+        CGLB_LAUNCH_CHECK(c);
+        dim3 grid((unsigned)((N + 255) / 256), (unsigned)b);
+        CGLB_DISPATCH_KIND(c->kind, hipLaunchKernelGGL((gpr_cross_kernel<KIND>), grid, dim3(256), 0, c->stream, (const double*)c->gpr_Xn,
+                                                       (const double*)c->gpr_xnew, N, D, c->gpr_var, c->gpr_Ks));
+        CGLB_LAUNCH_CHECK(c);
+        // mean = K_*f alpha (+ c below); variance = f - |L^-1 K_f*|^2 column-wise
+        BLAS_CHECK(c, rocblas_dgemv(c->blas, rocblas_operation_transpose, (int)N, (int)b, &one, c->gpr_Ks, (int)N, c->gpr_alpha, 1, &zero, mean_out + off, 1));
+        BLAS_CHECK(c, rocblas_dtrsm(c->blas, rocblas_side_left, rocblas_fill_lower, rocblas_operation_none, rocblas_diagonal_non_unit, (int)N, (int)b, &one,
+                                    c->gpr_L, (int)N, c->gpr_Ks, (int)N));
+        hipLaunchKernelGGL(gpr_colnorm_kernel, dim3((unsigned)b), dim3(256), 0, c->stream, (const double*)c->gpr_Ks, N, c->gpr_var, c->gpr_mean,
+                           mean_out + off, var_out ? var_out + off : var_tmp);
+        CGLB_LAUNCH_CHECK(c);
+        if (!g_mean) return CGLB_OK;
+        // C = L^-T (L^-1 K_f*) in place, transposed to [N][ldc] (a transpose pass); one launch against X with u = alpha, Wt = C
+        CGLB_TRY(launch_hot_points(c, c->gpr_ls.data(), raw, b, c->gpr_xh));
+        if (g_var) {
+            BLAS_CHECK(c, rocblas_dtrsm(c->blas, rocblas_side_left, rocblas_fill_lower, rocblas_operation_transpose, rocblas_diagonal_non_unit, (int)N, (int)b,
+                                        &one, c->gpr_L, (int)N, c->gpr_Ks, (int)N));
+            CGLB_TRY(launch_transpose(c, c->gpr_Ks, N, b, N, c->gpr_Ct, ldc));
+        }
+        return launch_weighted_grad(c, c->gpr_ls.data(), c->gpr_var, c->gpr_xh, b, c->gpr_Xh, N, c->gpr_alpha, g_var ? c->gpr_Ct : nullptr, ldc, nullptr,
+                                    g_mean + off * D, false, nullptr, g_var ? g_var + off * D : nullptr, -2.0);
+    }();
+    if (var_tmp) (void)hipStreamSynchronize(c->stream);  // before `tmp` frees
+    return rc;
+}
+
 }  // namespace
 
 void gpr_free(cglb_ctx* c) {
     c->gpr_mem.release();
     c->gpr_bytes = 0;
     c->gpr_factored = false;
+    c->gpr_hot_valid = false;
 }
 
 int gpr_stat(cglb_ctx* c, const char* name, double* value) {
@@ -428,38 +500,14 @@ int cglb_gpr_objective_and_grad(cglb_ctx* c, double* out3, double* grad) {
 
 int cglb_gpr_predict(cglb_ctx* c, const void* xnew, int64_t n_new, void* f_mean, void* f_var) {
     if (!c || !xnew || !f_mean || !f_var || n_new < 0) return c ? cglb_fail(c, CGLB_ERR_BAD_ARG, "NULL argument") : CGLB_ERR_BAD_ARG;
+    return gpr_predict_batches(c, xnew, n_new, (double*)f_mean, nullptr, (double*)f_var, nullptr);
+}
+
+int cglb_gpr_predict_grad(cglb_ctx* c, const void* xnew, int64_t n_new, void* f_mean, void* g_mean, void* f_var, void* g_var) {
+    if (!c || !xnew || !f_mean || !g_mean || (!f_var) != (!g_var) || n_new < 0) return c ? cglb_fail(c, CGLB_ERR_BAD_ARG, "bad argument") : CGLB_ERR_BAD_ARG;
     CGLB_TRY(gpr_require(c));
-    if (!c->gpr_factored) CGLB_TRY(gpr_evaluate(c, nullptr, nullptr));
-    HIP_CHECK(c, hipSetDevice(c->device));
-    const int64_t N = c->N;
-    const int D = c->D;
-    const int64_t bmax = std::min(GPR_PREDICT_BATCH, n_new);
-    if (bmax == 0) return CGLB_OK;
-    CGLB_TRY(gpr_reserve(c, &c->gpr_Ks, &c->gpr_Ks_cap, (size_t)N * bmax));
-    CGLB_TRY(gpr_reserve(c, &c->gpr_xnew, &c->gpr_xnew_cap, (size_t)2 * bmax * D));
-    const double one = 1.0, zero = 0.0;
-    double* mean_out = (double*)f_mean;
-    double* var_out = (double*)f_var;
-    for (int64_t off = 0; off < n_new; off += GPR_PREDICT_BATCH) {
-        const int64_t b = std::min(GPR_PREDICT_BATCH, n_new - off);
-        double* raw = c->gpr_xnew + bmax * D;
-        HIP_CHECK(c, hipMemcpyAsync(raw, (const double*)xnew + off * D, (size_t)b * D * sizeof(double), hipMemcpyDefault, c->stream));
-        hipLaunchKernelGGL(n2m_scale_kernel, dim3((unsigned)std::min<int64_t>(1024, (b * D + 255) / 256)), dim3(256), 0, c->stream, (const double*)raw,
-                           (const double*)c->gpr_lsd, b, D, c->gpr_xnew);
-        CGLB_LAUNCH_CHECK(c);
-        dim3 grid((unsigned)((N + 255) / 256), (unsigned)b);
-        CGLB_DISPATCH_KIND(c->kind, hipLaunchKernelGGL((gpr_cross_kernel<KIND>), grid, dim3(256), 0, c->stream, (const double*)c->gpr_Xn,
-                                                       (const double*)c->gpr_xnew, N, D, c->gpr_var, c->gpr_Ks));
-        CGLB_LAUNCH_CHECK(c);
-        // mean = K_*f alpha (+ c below); variance = f - |L^-1 K_f*|^2 column-wise
-        BLAS_CHECK(c, rocblas_dgemv(c->blas, rocblas_operation_transpose, (int)N, (int)b, &one, c->gpr_Ks, (int)N, c->gpr_alpha, 1, &zero, mean_out + off, 1));
-        BLAS_CHECK(c, rocblas_dtrsm(c->blas, rocblas_side_left, rocblas_fill_lower, rocblas_operation_none, rocblas_diagonal_non_unit, (int)N, (int)b, &one,
-                                    c->gpr_L, (int)N, c->gpr_Ks, (int)N));
-        hipLaunchKernelGGL(gpr_colnorm_kernel, dim3((unsigned)b), dim3(256), 0, c->stream, (const double*)c->gpr_Ks, N, c->gpr_var, c->gpr_mean,
-                           mean_out + off, var_out + off);
-        CGLB_LAUNCH_CHECK(c);
-    }
-    return CGLB_OK;
+    if (is_wide(c)) return cglb_fail(c, CGLB_ERR_BAD_ARG, "the input-gradient products have no wide path yet: they are available up to 32 input dimensions");
+    return gpr_predict_batches(c, xnew, n_new, (double*)f_mean, (double*)g_mean, (double*)f_var, (double*)g_var);
 }
 
 }  // extern "C"

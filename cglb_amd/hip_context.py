@@ -509,6 +509,67 @@ class HipContext:
         _lib.check(rc, self._ctx)
         return mean, dmean, var, dvar
 
+    # -- input gradients of the CGLB / SGPR / exact-GP predictive (cglb_cross_grad_weighted, cglb_predict_grad, cglb_gpr_predict_grad) ----
+    def cross_grad_weighted(self, xnew, u=None, Wt=None, point_set="train", out_u=None, gout_u=None, out_w=None, gout_w=None,
+                            with_value=True, with_grad=True):
+        """Row-weighted value and input gradient of the cross product against the training inputs (point_set "train") or the inducing points
+        ("inducing"): (out_u [n], gout_u [n, D], out_w [n], gout_w [n, D]) for the shared weight u [n_pts] and / or the per-point weights
+        Wt [n_pts, ldw >= n] (new-point index fastest; the columns from n on are never used); the outputs of an absent weight are None
+        (cglb_cross_grad_weighted).  `out_*`, `gout_*`: contiguous device tensors to write into; with_value / with_grad False: that half of the
+        outputs is not computed."""
+        if point_set not in ("train", "inducing"):
+            raise ValueError("point_set is 'train' or 'inducing'")
+        xn = self._xnew(xnew)
+        n, npts = xn.shape[0], (self.N if point_set == "train" else self.M)
+        ut = None if u is None else self._dev(u, npts)
+        wt, ldw = None, 0
+        if Wt is not None:
+            wt = torch.as_tensor(Wt, dtype=self.dtype, device=self.device)
+            if wt.dim() != 2 or wt.shape[0] != npts or wt.shape[1] < n:
+                raise ValueError(f"Wt must be [{npts}, ldw >= {n}]")
+            wt = wt.contiguous()
+            ldw = int(wt.shape[1])
+        for name, t, w in (("out_u", out_u, ut), ("gout_u", gout_u, ut), ("out_w", out_w, wt), ("gout_w", gout_w, wt)):
+            if t is not None and w is None:
+                raise ValueError(f"{name} was given without its weight")
+        res = []
+        for w, o, g, names in ((ut, out_u, gout_u, ("out_u", "gout_u")), (wt, out_w, gout_w, ("out_w", "gout_w"))):
+            res.append(self._out(o, (n,), names[0]) if (w is not None and with_value) else None)
+            res.append(self._out(g, (n, self.D), names[1]) if (w is not None and with_grad) else None)
+        rc = self.lib.cglb_cross_grad_weighted(self._ctx, 0 if point_set == "train" else 1, _ptr(xn), n, _ptr(ut), _ptr(wt), ldw,
+                                               _ptr(res[0]), _ptr(res[1]), _ptr(res[2]), _ptr(res[3]))
+        _lib.check(rc, self._ctx)
+        return tuple(res)
+
+    def _predict_grad_outs(self, n, with_var, f_mean, g_mean, f_var, g_var):
+        if not with_var and (f_var is not None or g_var is not None):
+            raise ValueError("f_var / g_var were given with with_var False")
+        return (self._out(f_mean, (n,), "f_mean"), self._out(g_mean, (n, self.D), "g_mean"),
+                self._out(f_var, (n,), "f_var") if with_var else None, self._out(g_var, (n, self.D), "g_var") if with_var else None)
+
+    def predict_grad(self, v_full, xnew, with_var=True, f_mean=None, g_mean=None, f_var=None, g_var=None):
+        """(mean [n], dmean [n, D], var [n] or None, dvar [n, D] or None) of the CGLB / SGPR predictive at xnew, the gradients with respect to
+        the new points (cglb_predict_grad); mean and var are bitwise those of `predict`."""
+        xn = self._xnew(xnew)
+        v = self._dev(v_full, self.N)
+        outs = self._predict_grad_outs(xn.shape[0], with_var, f_mean, g_mean, f_var, g_var)
+        _lib.check(self.lib.cglb_predict_grad(self._ctx, _ptr(v), _ptr(xn), xn.shape[0], *[_ptr(t) for t in outs]), self._ctx)
+        return outs
+
+    def gpr_predict_grad(self, xnew, with_var=True, f_mean=None, g_mean=None, f_var=None, g_var=None):
+        """(mean [n], dmean [n, D], var [n] or None, dvar [n, D] or None) of the exact-GP predictive at xnew (cglb_gpr_predict_grad); mean and
+        var are bitwise those of `gpr_predict`."""
+        xn = self._xnew(xnew)
+        outs = self._predict_grad_outs(xn.shape[0], with_var, f_mean, g_mean, f_var, g_var)
+        _lib.check(self.lib.cglb_gpr_predict_grad(self._ctx, _ptr(xn), xn.shape[0], *[_ptr(t) for t in outs]), self._ctx)
+        return outs
+
+    def time_predict_grad(self, n_new: int, with_grad: bool, reps: int) -> float:
+        """ms per `predict` (with_grad False) or `predict_grad` call at the first n_new training rows and v = 0."""
+        ms = c_double()
+        _lib.check(self.lib.cglb_time_predict_grad(self._ctx, int(n_new), int(bool(with_grad)), int(reps), byref(ms)), self._ctx)
+        return ms.value
+
     def itergp_paths_solve(self, omega, phase, W, eps, max_error=1e-3, max_cg_iter=1000) -> IterGPSamples:
         """The solves U [S, N] of S sample paths (cglb_itergp_paths_solve: the first half of itergp_sample); `samples` is None."""
         om, ph, Wt = self._features(omega, phase, W)

@@ -371,7 +371,7 @@ int cglb_itergp_sample(cglb_ctx* ctx, const void* xnew, int64_t n_new, const voi
 /* ---- input gradients of predictive and sample paths (csrc/kernels_input_grad.hip) ----
  * All gradients below are with respect to the RAW coordinates of the new point (not centred, not scaled).  Scope of every entry: that of
  * cglb_itergp_predict (fp64, one rank, one target column, the default bound) and d <= 32 - the gradient products have no wide path yet; else
- * CGLB_ERR_BAD_ARG with a message.  Not covered: fp32, N ranks, wide inputs, the gpr / cglb / sgpr predictors (cglb_cross_grad_matmat serves any V).
+ * CGLB_ERR_BAD_ARG with a message.  Not covered: fp32, N ranks, wide inputs.  The gpr / cglb / sgpr predictors have their own entries further down (cglb_predict_grad, cglb_gpr_predict_grad).
  *
  * Value and input gradient of K_*f V in one pass over the pairs:
  *   out [i, s]    =  variance sum_j kappa(x*_i, x_j) V[s, j]
@@ -403,6 +403,39 @@ int cglb_time_feature_grad_matmat(cglb_ctx* ctx, int64_t n_rows, int64_t F, int 
  * Galerkin upper bound f - |R^T k_*|^2), not of the exact variance.  The stored alpha and the variance cache stay valid. */
 int cglb_itergp_predict_grad(cglb_ctx* ctx, const void* xnew, int64_t n_new, double max_error, int max_cg_iter, void* f_mean, void* g_mean, void* f_var,
                              void* g_var);
+/* ---- input gradients of the CGLB, SGPR and exact-GP predictive (csrc/kernels_predict_grad.hip) ----
+ * Gradients with respect to the RAW coordinates of the new point, as above.  Not covered: fp32, N ranks, wide inputs (d > 32), more than one
+ * target column; CGLB_ERR_BAD_ARG with a message.
+ *
+ * Row-weighted value and input gradient of a cross product, one pass over the pairs for up to two weights:
+ *   out_u[i] =  variance sum_m u[m]     kappa(x*_i, p_m)     gout_u[i, k] = -variance sum_m u[m]     h(x*_i, p_m) (x*_ik - p_mk) / l_k^2
+ *   out_w[i] =  variance sum_m Wt[m, i] kappa(x*_i, p_m)     gout_w[i, k] = -variance sum_m Wt[m, i] h(x*_i, p_m) (x*_ik - p_mk) / l_k^2
+ * set: 0 the training inputs (n_pts = n_total), 1 the inducing points Z of the current hyper-parameters (n_pts = m).  xnew: any [n_new, d];
+ * u: dev [n_pts] or NULL; Wt: dev [n_pts, ldw] or NULL, the new-point index fastest, ldw >= n_new (the layout of the predictive panels; what the
+ * columns [n_new, ldw) hold never reaches an output); at least one of the two.  out_*: dev [n_new]; gout_*: dev [n_new, d], k fastest; the outputs
+ * of an absent weight must be NULL, any output of a present one may be.  Pairs from direct differences, always the range-clamped 2^x, as
+ * cglb_cross_grad_matmat: a coincident pair adds exactly zero to the gradient.  No atomics: bitwise reproducible, and every output is bitwise the
+ * same whichever of the others are requested.  Scope: a context with hyper-parameters set (cglb_set_hypers), fp64, one rank, d <= 32.
+ * "predict_grad_kernel_ms" (cglb_get_stat): device time of the pair kernel and slab sums of the last product. */
+int cglb_cross_grad_weighted(cglb_ctx* ctx, int set, const void* xnew, int64_t n_new, const void* u, const void* Wt, int64_t ldw, void* out_u, void* gout_u,
+                             void* out_w, void* gout_w);
+/* cglb_predict with the input gradients of both outputs.  f_mean, f_var (dev [n_new]) come from the routines of cglb_predict and are bitwise its
+ * outputs; g_mean, g_var: dev [n_new, d], k fastest; f_var and g_var are both NULL or both set.  With tmp1 = L^-1 K_u*, tmp2 = LB^-1 tmp1 and
+ * c = LB^-1 A res / sigma of cglb_predict:
+ *   g_mean[i, k] = grad (K_*f v)[i, k] + sum_m q_m dk(x*_i, z_m)/dx*_k,    q = L^-T LB^-T c
+ *   g_var [i, k] = -2 sum_m C^T[m, i] dk(x*_i, z_m)/dx*_k,                 C^T = L^-T (tmp1 - LB^-T tmp2)   (f_var = variance - sum_m C^T[m, i] k(x*_i, z_m))
+ * grad (K_*f v) is cglb_cross_grad_matmat's product with v as its single column (quad_term 1: skipped, v is not read); the sums over m are ONE launch
+ * of the row-weighted kernel against Z.  Scope: that of cglb_predict (quad_term 0 and 1, every logdet_bound) in fp64, on one rank, with one
+ * target column and d <= 32.  v, the common terms and every cached state are left as they are. */
+int cglb_predict_grad(cglb_ctx* ctx, const void* v_full, const void* xnew, int64_t n_new, void* f_mean, void* g_mean, void* f_var, void* g_var);
+/* cglb_gpr_predict with the input gradients of both outputs, in its batches.  f_mean, f_var are bitwise those of cglb_gpr_predict (the same gemv,
+ * trsm and column-norm calls).  g_mean = sum_j alpha_j dk_ij, g_var = -2 sum_j C[j, i] dk_ij with C = K^-1 K_f* from one further trsm on the
+ * panel, transposed to [n_total][ld]: one launch of the row-weighted kernel against X per batch.  X and each batch are staged in the kernel's units
+ * at the class's own lengthscales.  The extra 8 n_total (batch + d_p) bytes are checked against the free device memory first.  d <= 32. */
+int cglb_gpr_predict_grad(cglb_ctx* ctx, const void* xnew, int64_t n_new, void* f_mean, void* g_mean, void* f_var, void* g_var);
+/* average duration (ms) of `reps` back-to-back cglb_predict (with_grad 0) or cglb_predict_grad (with_grad 1) calls at the first n_new training rows
+ * as new points (n_new <= n_total) and v = 0, HIP events on the context stream */
+int cglb_time_predict_grad(cglb_ctx* ctx, int64_t n_new, int with_grad, int reps, double* ms_avg);
 /* Sample paths that are solved once.  cglb_itergp_paths_solve is the first half of cglb_itergp_sample (the same code): the right-hand sides
  * e - Phi(X) w_s - sqrt(noise) eps_s and one batched solve from zero with the class's preconditioner; U_out: dev [S, n_total], bitwise the U_out of
  * cglb_itergp_sample for the same draws.  cglb_itergp_paths_eval runs NO solve:
