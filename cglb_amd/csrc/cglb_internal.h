@@ -253,7 +253,7 @@ struct cglb_ctx {
     void* cm_vi = nullptr;                              // [N][S rounded up to 8] interleaved column operand of cglb_cross_matmat
     size_t cm_vi_cap = 0;
     // random-feature product (kernels_feature_multi.hip) and the pathwise posterior samples built on it (cglb_itergp_sample)
-    double* ft_rec = nullptr;                           // [groups][F][FEATURE_REC] operand records {b_j | omega_j | W[8 g .., j]} in turns
+    double* ft_rec = nullptr;                           // [groups][F][FEATURE_REC (row_slab.h)] operand records {b_j | omega_j | W[8 g .., j]} in turns
     double* ft_in = nullptr;                            // [F][D] omega and [F] phases as the caller gave them (device copy)
     double* ft_par = nullptr;                           // [D] 1 / (2 pi l_k), [D] centre c_k
     double* ft_part = nullptr;                          // partial-sum slabs [jsplit][rows][8]
@@ -429,6 +429,7 @@ int launch_cross_matvec(cglb_ctx* c, const void* Xs_new, const void* xa_new, int
 // One evaluation of every kernel value for up to 8 pairs where grad_multi_native(c), S single passes elsewhere.
 bool grad_multi_native(const cglb_ctx* c);
 int launch_grad_kff_multi(cglb_ctx* c, const void* U, const void* V, int S, double* out);
+// The row-slab products (decomposition, chunk rules, layout constants and the shared value finish kernel: row_slab.h), one file each:
 // kernels_cross_multi.hip: out[i * ldo + s] = var * sum_j kappa(row_i, x_j) Vi[j * ldv + s], s < S; Vi dev [N][ldv] row-major (ldv a multiple of 8, zero
 // padded), rows hot-scaled; every kernel value evaluated once per group of 8 columns.  fp64, Dp <= 32.  Bitwise repeatable.
 int launch_cross_multi(cglb_ctx* c, const void* XsRow, const void* xaRow, int64_t nrows, const double* Vi, int64_t ldv, int S, double* out, int64_t ldo);
@@ -442,7 +443,6 @@ int cross_multi_width();                            // columns per group (8): th
 int launch_feature_operand(cglb_ctx* c, const void* omega, const void* phase, const void* W, int64_t F, int S);
 int launch_feature_multi(cglb_ctx* c, const double* X, int64_t nrows, int64_t F, int S, double* out, int64_t ldo);
 int feature_rows_per_block(const cglb_ctx* c);      // rows per workgroup at the context's width
-void feature_split(const cglb_ctx* c, int64_t nrows, int64_t F, int64_t* jsplit_out, int64_t* jchunk_out);  // feature chunks of one launch
 // kernels_input_grad.hip: value (out may be NULL) and input gradient gout[(i * S + s) * D + k] of the two products above, one evaluation of a pair per
 // group of input_grad_width(c) columns; the operands of launch_cross_multi (hot-scaled rows, Vi [N][ldv]) / of launch_feature_multi (records first).
 // fp64, Dp <= 32.  Bitwise repeatable.

@@ -3,22 +3,16 @@
 // V = the N x r_pad factor R with K^-1 ~ R R^T; the reference reaches the same estimator through gpytorch.settings.fast_pred_var(),
 // pytorch/interface.py:582) and is exposed on its own as cglb_cross_matmat.
 //
-// The decomposition is that of the plain pair kernel behind launch_cross_matvec (kernels_kff.hip: kff_matvec_kernel): a lane owns R new
-// points (x_i, the row seed and R x 8 accumulators in VGPRs for the whole launch); a training point is wave-uniform and arrives by scalar
-// loads; the column range is split over blockIdx.y by the kff_jsplit rule; partial sums go to a slab [jsplit][nrows][8] that exactly one
-// workgroup writes, and a finish kernel adds the slabs in fixed order: no atomics, bitwise repeatable.
-// New here: the column side is row-major Vi[N][ldv] (ldv a multiple of 8), so the 8 values of a training point for one group are ONE contiguous
+// A row-slab product (row_slab.h) of the plain pair kernel's pairs: a lane keeps x_i, the row seed and R x 8 accumulators; the column range is
+// split by the kff_jsplit rule; slab [jsplit][nrows][8].  The column side is row-major Vi[N][ldv] (ldv a multiple of 8), so the 8 values of a training point for one group are ONE contiguous
 // scalar load next to x_j (kernels_grad_multi.hip interleaves its operands the same way), and every kernel value feeds 8 v_fma_f64 with a
 // scalar source: k + 8 vector-fp64 instructions per pair and group against 8 (k + 1) for 8 single products.  S > 8 runs in groups of 8; a short
 // group reads zero padding.  Always the range-clamped 2^x: new points may lie anywhere.  fp64, Dp <= 32.
 // Register use of every instance: DESIGN.md section 4f.
 #include "pair_common.h"
+#include "row_slab.h"
 
-#ifndef CROSS_MULTI_SP
-#define CROSS_MULTI_SP 8          // columns per group: the one instantiated width (16 was tried as a variant build: DESIGN.md section 4f)
-#endif
-#define CROSS_MULTI_SLOTS 256     // most column chunks of one launch
-#define CROSS_MULTI_ROWS 16384    // new points per launch: bounds the slab at CROSS_MULTI_SLOTS * CROSS_MULTI_ROWS * 8 doubles
+#define CROSS_MULTI_ROWS 16384    // new points per launch: bounds the slab at ROW_SLAB_SLOTS * CROSS_MULTI_ROWS * 8 doubles
 
 // rows per lane: the rule of the plain kernel (4 up to padded width 8, 2 up to 16, 1 beyond), halved while the R (DP + 8) row-resident doubles
 // exceed 64 (half of the 256 VGPRs): with 8 accumulators per row the rule holds as it stands (64 at DP = 8, 48 at DP = 16, 40 at DP = 32)
@@ -50,13 +44,11 @@ __global__ __launch_bounds__(256) void cross_multi_kernel(const double* __restri
     double xi[R][DP], ai[R], acc[R][SP];
 #pragma unroll
     for (int k = 0; k < R; ++k) {
-        int64_t row = rbase + (int64_t)k * 256;
-        row = row < nrows ? row : nrows - 1;
+        const int64_t row = row_slab_clamped(rbase, k, nrows);
 #pragma unroll
         for (int d = 0; d < DP; ++d) xi[k][d] = XsRow[row * DP + d];
         ai[k] = cglb_kind_matern<KIND>() ? -0.5 * xaRow[row] : xaRow[row];  // seed of the Gram chain (any Matern kind: -|x|^2 / 2)
-#pragma unroll
-        for (int b = 0; b < SP; ++b) acc[k][b] = 0.0;
+        row_slab_zero(acc[k]);
     }
     const int64_t j0 = (int64_t)blockIdx.y * jchunk;
     const int64_t j1 = (j0 + jchunk < ncols) ? j0 + jchunk : ncols;
@@ -87,27 +79,7 @@ __global__ __launch_bounds__(256) void cross_multi_kernel(const double* __restri
         }
     }
 #pragma unroll
-    for (int k = 0; k < R; ++k) {
-        const int64_t row = rbase + (int64_t)k * 256;
-        if (row < nrows) {
-            double* __restrict__ o = part + ((int64_t)blockIdx.y * nrows + row) * SP;
-#pragma unroll
-            for (int b = 0; b < SP; ++b) o[b] = acc[k][b];
-        }
-    }
-}
-
-// out[i * ldo + b] = var * sum_js part[js][i][b], b < sg: the slabs in fixed order
-__global__ __launch_bounds__(256) void cross_multi_finish_kernel(const double* __restrict__ part, int jsplit, int64_t nrows, int sg, double var,
-                                                                 double* __restrict__ out, int64_t ldo) {
-    const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= nrows * CROSS_MULTI_SP) return;
-    const int64_t i = idx / CROSS_MULTI_SP;
-    const int b = (int)(idx - i * CROSS_MULTI_SP);
-    if (b >= sg) return;
-    double s = 0.0;
-    for (int js = 0; js < jsplit; ++js) s += part[(int64_t)js * nrows * CROSS_MULTI_SP + idx];
-    out[i * ldo + b] = var * s;
+    for (int k = 0; k < R; ++k) row_slab_store(part, nrows, rbase + (int64_t)k * 256, acc[k]);
 }
 
 // f_var[i] = var - sum_{s < sp} blk[i][s]^2 in column order: the variance of the cached path from the summed block, not a second pass over pairs
@@ -128,24 +100,15 @@ static int cross_multi_group(cglb_ctx* c, const double* XsRow, const double* xaR
     constexpr int R = cross_multi_rows_per_lane(DP);
     const int64_t ncols = c->N;
     const int64_t bx = (nrows + 256 * R - 1) / (256 * R);
-    // the column split of the plain kernel (kernels_kff.hip: kff_pairs_range)
-    int64_t jsplit = c->kff_jsplit > 0 ? c->kff_jsplit : (8192 + bx - 1) / bx;
-    if (jsplit > CROSS_MULTI_SLOTS) jsplit = CROSS_MULTI_SLOTS;
-    if (jsplit > (ncols + 63) / 64) jsplit = (ncols + 63) / 64;
-    if (jsplit < 1) jsplit = 1;
-    int64_t jchunk = (ncols + jsplit - 1) / jsplit;
-    jchunk = (jchunk + 1) & ~(int64_t)1;
-    jsplit = (ncols + jchunk - 1) / jchunk;
+    int64_t jsplit = 0, jchunk = 0;
+    row_slab_pair_split(c->kff_jsplit, bx, ncols, ROW_SLAB_SLOTS, true, &jsplit, &jchunk);
     CGLB_TRY(c->mem.reserve(c, &c->cm_part, &c->cm_part_cap, (size_t)jsplit * nrows * CROSS_MULTI_SP * sizeof(double)));
     using T = double;
     CGLB_DISPATCH_PREC(c, hipLaunchKernelGGL((cross_multi_kernel<KIND, DP, R, PREC>), dim3((unsigned)bx, (unsigned)jsplit), dim3(256), 0, c->stream, XsRow,
                                              xaRow, nrows, (const double*)c->Xh, (const double*)c->xah, Vi, ldv, ncols, jchunk, (double*)c->cm_part,
                                              (const double*)c->exp_tab));
     CGLB_LAUNCH_CHECK(c);
-    hipLaunchKernelGGL(cross_multi_finish_kernel, dim3((unsigned)((nrows * CROSS_MULTI_SP + 255) / 256)), dim3(256), 0, c->stream,
-                       (const double*)c->cm_part, (int)jsplit, nrows, sg, c->var, out, ldo);
-    CGLB_LAUNCH_CHECK(c);
-    return CGLB_OK;
+    return row_slab_finish<CROSS_MULTI_SP>(c, (const double*)c->cm_part, jsplit, nrows, sg, c->var, out, ldo);
 }
 
 int cross_multi_rows_per_block(const cglb_ctx* c) { return 256 * cross_multi_rows_per_lane(c->Dp); }

@@ -2,23 +2,17 @@
 // term Phi(.) w of a pathwise posterior sample (cglb_itergp_sample; Wilson et al. 2020), exposed on its own as cglb_feature_matmat.  The N x F
 // feature matrix is never formed: every cosine is evaluated ONCE per group of 8 columns and consumed from a register.
 //
-// The decomposition is that of cross_multi_kernel (kernels_cross_multi.hip) with a feature in the place of a training point: a lane owns R rows
-// (x_i - c and R x 8 accumulators in VGPRs for the whole launch); feature j is wave-uniform, its operand record
+// A row-slab product (row_slab.h) with a feature in the place of a training point: a lane keeps x_i - c and R x 8 accumulators; feature j's
+// operand record
 //   { b_j / 2 pi | omega_j[k] / (2 pi l_k), k < DP (zero padded) | W[8 g .. 8 g + 7, j] }          (FEATURE_REC(DP) doubles, one record per group g)
-// is ONE contiguous run of scalar loads; the feature range is split over blockIdx.y; partial sums go to a slab [jsplit][nrows][8] that exactly
-// one workgroup writes, and a finish kernel adds the slabs in fixed order: no atomics, bitwise repeatable.  S > 8 runs in groups of 8; a short
-// group reads the zero padding of its records.
+// is ONE contiguous run of scalar loads; the feature range is split by row_slab_feature_split; slab [jsplit][nrows][8].  S > 8 runs in groups of
+// 8; a short group reads the zero padding of its records.
 // The records are in TURNS, so the range reduction of cos_turns (devmath.h) is exact at any magnitude.  Per (row, feature, group): DP fma for the
 // phase, 14 for the cosine, 8 for the columns.  Instances: the padded widths of dispatch.h (rows register-resident) and ONE looping instance
 // for wider inputs, which reads x_ik in the k-loop (once per batch of 16 features, whose phases it advances together) and keeps the
 // scalar-side features.  Register use of every instance: DESIGN.md section 4g.
 #include "pair_common.h"
-
-#define FEATURE_SP 8            // columns per group
-#define FEATURE_SLOTS 256       // most feature chunks of one launch
-#define FEATURE_MIN_CHUNK 64    // fewest features of a chunk (but the last): below it the slab traffic outweighs the R x 8 accumulators a workgroup keeps
-#define FEATURE_TARGET_WG 2048  // workgroups a launch aims at: 8 per CU
-#define FEATURE_REC(dp) (((dp) + 1 + FEATURE_SP + 1) & ~1)  // doubles per record, even: every record starts 16-byte aligned
+#include "row_slab.h"
 
 // rows per lane: the rule of cross_multi_rows_per_lane (4 up to padded width 8, 2 up to 16, 1 beyond, halved while the R (DP + 8) row-resident
 // doubles exceed 64, half of the 256 VGPRs): a row keeps DP centred coordinates and 8 accumulators here as there, and no seed
@@ -50,23 +44,19 @@ __global__ __launch_bounds__(256) void feature_operand_kernel(const double* __re
     rec[idx] = v;
 }
 
-struct FeatureCentre { double c[CGLB_MAX_D_NARROW]; };
-
 // grid (row blocks of 256 R rows, feature chunks of jchunk); rec points at the first record of the group
 template <int DP, int R>
-__global__ __launch_bounds__(256) void feature_multi_kernel(const double* __restrict__ X, int d, FeatureCentre cen, int64_t nrows, const double* __restrict__ rec,
+__global__ __launch_bounds__(256) void feature_multi_kernel(const double* __restrict__ X, int d, RowSlabCentre cen, int64_t nrows, const double* __restrict__ rec,
                                                             int64_t F, int64_t jchunk, double* __restrict__ part) {
     constexpr int SP = FEATURE_SP, RL = FEATURE_REC(DP);
     const int64_t rbase = (int64_t)blockIdx.x * (256 * R) + threadIdx.x;
     double z[R][DP], acc[R][SP];
 #pragma unroll
     for (int k = 0; k < R; ++k) {
-        int64_t row = rbase + (int64_t)k * 256;
-        row = row < nrows ? row : nrows - 1;
+        const int64_t row = row_slab_clamped(rbase, k, nrows);
 #pragma unroll
         for (int q = 0; q < DP; ++q) z[k][q] = q < d ? X[row * d + q] - cen.c[q] : 0.0;
-#pragma unroll
-        for (int b = 0; b < SP; ++b) acc[k][b] = 0.0;
+        row_slab_zero(acc[k]);
     }
     const int64_t j0 = (int64_t)blockIdx.y * jchunk;
     const int64_t j1 = (j0 + jchunk < F) ? j0 + jchunk : F;
@@ -89,14 +79,7 @@ __global__ __launch_bounds__(256) void feature_multi_kernel(const double* __rest
         }
     }
 #pragma unroll
-    for (int k = 0; k < R; ++k) {
-        const int64_t row = rbase + (int64_t)k * 256;
-        if (row < nrows) {
-            double* __restrict__ o = part + ((int64_t)blockIdx.y * nrows + row) * SP;
-#pragma unroll
-            for (int b = 0; b < SP; ++b) o[b] = acc[k][b];
-        }
-    }
+    for (int k = 0; k < R; ++k) row_slab_store(part, nrows, rbase + (int64_t)k * 256, acc[k]);
 }
 
 // the looping instance (d > 32): one row per lane, its coordinates read in the k-loop - once per FEATURE_LOOP_JC features, whose phases advance
@@ -109,10 +92,9 @@ __global__ __launch_bounds__(256) void feature_multi_loop_kernel(const double* _
     constexpr int SP = FEATURE_SP, JC = FEATURE_LOOP_JC;
     const int rl = FEATURE_REC(d);
     const int64_t row0 = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    const double* __restrict__ xi = X + (row0 < nrows ? row0 : nrows - 1) * d;
+    const double* __restrict__ xi = X + (row0 < nrows ? row0 : nrows - 1) * d;  // one row per lane: the clamp of row_slab_clamped
     double acc[SP];
-#pragma unroll
-    for (int b = 0; b < SP; ++b) acc[b] = 0.0;
+    row_slab_zero(acc);
     const int64_t j0 = (int64_t)blockIdx.y * jchunk;
     const int64_t j1 = (j0 + jchunk < F) ? j0 + jchunk : F;
     for (int64_t jb = j0; jb < j1; jb += JC) {
@@ -135,40 +117,10 @@ __global__ __launch_bounds__(256) void feature_multi_loop_kernel(const double* _
             for (int b = 0; b < SP; ++b) acc[b] = __builtin_fma(cv, rj[jj][1 + d + b], acc[b]);
         }
     }
-    if (row0 < nrows) {
-        double* __restrict__ o = part + ((int64_t)blockIdx.y * nrows + row0) * SP;
-#pragma unroll
-        for (int b = 0; b < SP; ++b) o[b] = acc[b];
-    }
-}
-
-// out[i * ldo + b] = amp * sum_js part[js][i][b], b < sg: the slabs in fixed order
-__global__ __launch_bounds__(256) void feature_finish_kernel(const double* __restrict__ part, int jsplit, int64_t nrows, int sg, double amp,
-                                                             double* __restrict__ out, int64_t ldo) {
-    const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= nrows * FEATURE_SP) return;
-    const int64_t i = idx / FEATURE_SP;
-    const int b = (int)(idx - i * FEATURE_SP);
-    if (b >= sg) return;
-    double s = 0.0;
-    for (int js = 0; js < jsplit; ++js) s += part[(int64_t)js * nrows * FEATURE_SP + idx];
-    out[i * ldo + b] = amp * s;
+    row_slab_store(part, nrows, row0, acc);
 }
 
 int feature_rows_per_block(const cglb_ctx* c) { return is_wide(c) ? 256 : 256 * feature_rows_per_lane(c->Dp); }
-
-// the feature split of one launch: chunks of ceil(F / jsplit) features, jsplit = ceil(FEATURE_TARGET_WG / row blocks) within
-// 1 .. min(FEATURE_SLOTS, ceil(F / FEATURE_MIN_CHUNK)), then the chunk count that chunk length gives
-void feature_split(const cglb_ctx* c, int64_t nrows, int64_t F, int64_t* jsplit_out, int64_t* jchunk_out) {
-    const int64_t rb = feature_rows_per_block(c), bx = (nrows + rb - 1) / rb;
-    int64_t jsplit = (FEATURE_TARGET_WG + bx - 1) / bx;
-    if (jsplit > FEATURE_SLOTS) jsplit = FEATURE_SLOTS;
-    if (jsplit > (F + FEATURE_MIN_CHUNK - 1) / FEATURE_MIN_CHUNK) jsplit = (F + FEATURE_MIN_CHUNK - 1) / FEATURE_MIN_CHUNK;
-    if (jsplit < 1) jsplit = 1;
-    const int64_t jchunk = (F + jsplit - 1) / jsplit;
-    *jchunk_out = jchunk;
-    *jsplit_out = (F + jchunk - 1) / jchunk;
-}
 
 // c->ft_rec <- the records of (omega, phase, W) at the current lengthscales, c->ft_par <- {1 / (2 pi l_k), c_k}.  omega [F][d] and phase [F]: host or
 // device; W: dev [S][F]
@@ -197,9 +149,8 @@ int launch_feature_operand(cglb_ctx* c, const void* omega, const void* phase, co
 template <int DP>
 static int feature_group(cglb_ctx* c, const double* X, int64_t nrows, const double* rec, int64_t F, int64_t jsplit, int64_t jchunk, unsigned bx) {
     constexpr int R = feature_rows_per_lane(DP);
-    FeatureCentre cen;
-    for (int k = 0; k < CGLB_MAX_D_NARROW; ++k) cen.c[k] = k < c->D ? c->xmean[k] : 0.0;
-    hipLaunchKernelGGL((feature_multi_kernel<DP, R>), dim3(bx, (unsigned)jsplit), dim3(256), 0, c->stream, X, c->D, cen, nrows, rec, F, jchunk, c->ft_part);
+    hipLaunchKernelGGL((feature_multi_kernel<DP, R>), dim3(bx, (unsigned)jsplit), dim3(256), 0, c->stream, X, c->D, row_slab_centre(c), nrows, rec, F, jchunk,
+                       c->ft_part);
     CGLB_LAUNCH_CHECK(c);
     return CGLB_OK;
 }
@@ -211,8 +162,8 @@ int launch_feature_multi(cglb_ctx* c, const double* X, int64_t nrows, int64_t F,
     if (S < 1 || F < 1 || ldo < S) return cglb_fail(c, CGLB_ERR_BAD_ARG, "bad feature count, column count or leading dimension of the feature product");
     if (nrows == 0) return CGLB_OK;
     int64_t jsplit = 0, jchunk = 0;
-    feature_split(c, nrows, F, &jsplit, &jchunk);
     const int64_t rb = feature_rows_per_block(c), bx = (nrows + rb - 1) / rb;
+    row_slab_feature_split(rb, nrows, F, ROW_SLAB_SLOTS, &jsplit, &jchunk);
     if (bx > 0x7fffffffLL) return cglb_fail(c, CGLB_ERR_BAD_ARG, "too many rows for one launch of the feature product");
     CGLB_TRY(c->mem.reserve(c, &c->ft_part, &c->ft_part_cap, (size_t)jsplit * nrows * FEATURE_SP * sizeof(double)));
     const double amp = std::sqrt(2.0 * c->var / (double)F);
@@ -227,9 +178,7 @@ int launch_feature_multi(cglb_ctx* c, const double* X, int64_t nrows, int64_t F,
         } else {
             CGLB_DISPATCH_DP(c->Dp, CGLB_TRY((feature_group<DP>(c, X, nrows, rec, F, jsplit, jchunk, (unsigned)bx))));
         }
-        hipLaunchKernelGGL(feature_finish_kernel, dim3((unsigned)((nrows * FEATURE_SP + 255) / 256)), dim3(256), 0, c->stream, (const double*)c->ft_part,
-                           (int)jsplit, nrows, sg, amp, out + b0, ldo);
-        CGLB_LAUNCH_CHECK(c);
+        CGLB_TRY(row_slab_finish<FEATURE_SP>(c, (const double*)c->ft_part, jsplit, nrows, sg, amp, out + b0, ldo));
     }
     return CGLB_OK;
 }

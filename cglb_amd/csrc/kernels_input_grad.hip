@@ -4,11 +4,9 @@
 // with h the radial derivative factor of the lengthscale gradient (devmath.h: hfac_hot_from_d2; d kappa / d x_ik = -h delta_k / l_k) and
 // amp = sqrt(2 var / F).  Gradients are with respect to the RAW coordinates of the new point.
 //
-// The decomposition is that of cross_multi_kernel / feature_multi_kernel: a lane owns R new points (coordinates and R x G x (DP + 1) accumulators in
-// VGPRs for the whole launch); the training point (feature) and its G column values are wave-uniform and arrive by scalar loads; the column
-// range is split over blockIdx.y (the kff_jsplit rule for the cross product, the feature product's chunk rule for the other); partial sums go
-// to a slab [jsplit][nrows][G][DP + 1] that exactly one workgroup writes, and ONE finish kernel adds the slabs in fixed order and applies the
-// constants: no atomics, bitwise repeatable.
+// Row-slab products (row_slab.h) of cross_multi_kernel's and feature_multi_kernel's operands: a lane keeps the coordinates and R x G x (DP + 1)
+// accumulators; the range is split by the kff_jsplit rule (cross) or the feature rule, each capped by the slab [jsplit][nrows][G][DP + 1]; ONE
+// finish kernel applies the constants.
 // Cross pair: DIRECT differences delta_k = xh*_k - xh_jk in hot units, d2 = sum delta_k^2, kappa and h from that exact d2
 // (kappa_hfac_hot_from_d2; always the range-clamped 2^x) - not the Gram chain, whose cancellation error in r would show in h, which is not flat at
 // r = 0 for the Matern kinds.  A coincident pair has delta = 0 exactly: it adds exactly zero to the gradient.  Per pair and column: one multiply
@@ -19,21 +17,14 @@
 // interleave blocks of 8, so any ldv that is a multiple of 8 serves (the variance cache as it lies) and the feature records are the existing ones.
 // fp64, Dp <= 32.  Register use of every instance: DESIGN.md section 4h.
 #include "pair_common.h"
+#include "row_slab.h"
 
-#define INPUT_GRAD_SLOTS 256            // most column chunks of one launch
 #define INPUT_GRAD_ROWS 4096            // new points per launch
-#define INPUT_GRAD_SLAB (1 << 24)       // doubles of the slab of one launch (128 MiB): caps the chunk count
-#define INPUT_GRAD_REC_SP 8             // columns per feature record / interleave block (FEATURE_SP, CROSS_MULTI_SP)
-#define INPUT_GRAD_FEATURE_MIN_CHUNK 64 // as FEATURE_MIN_CHUNK
-#define INPUT_GRAD_FEATURE_TARGET_WG 2048
-#define INPUT_GRAD_FEATURE_REC(dp) (((dp) + 1 + INPUT_GRAD_REC_SP + 1) & ~1)  // FEATURE_REC of kernels_feature_multi.hip
 
 // rows per lane and columns per group by padded width, chosen so that R (DP + G (DP + 1)) + DP row-resident doubles stay near 100 (200 of the 256
 // VGPRs of two waves per SIMD): 2 x 8 up to width 4 (88 + 4), 1 x 8 up to 8 (80 + 8), 1 x 4 up to 16 (84 + 16), 1 x 2 beyond (98 + 32)
 static constexpr int input_grad_rows_per_lane(int dp) { return dp <= 4 ? 2 : 1; }
 static constexpr int input_grad_group_width(int dp) { return dp <= 8 ? 8 : (dp <= 16 ? 4 : 2); }
-
-struct InputGradScale { double g[CGLB_MAX_D_NARROW]; };  // constant of gradient component k
 
 // grid (row blocks of 256 R new points, column chunks of jchunk training points); Vi points at the first column of the group
 template <int KIND, int DP, int R, int G, int PREC>
@@ -46,14 +37,10 @@ __global__ __launch_bounds__(256) void cross_grad_kernel(const double* __restric
     double xi[R][DP], acc[R][G][DP + 1];
 #pragma unroll
     for (int k = 0; k < R; ++k) {
-        int64_t row = rbase + (int64_t)k * 256;
-        row = row < nrows ? row : nrows - 1;
+        const int64_t row = row_slab_clamped(rbase, k, nrows);
 #pragma unroll
         for (int d = 0; d < DP; ++d) xi[k][d] = XhRow[row * DP + d];
-#pragma unroll
-        for (int b = 0; b < G; ++b)
-#pragma unroll
-            for (int d = 0; d <= DP; ++d) acc[k][b][d] = 0.0;
+        row_slab_zero(acc[k]);
     }
     const int64_t j0 = (int64_t)blockIdx.y * jchunk;
     const int64_t j1 = (j0 + jchunk < ncols) ? j0 + jchunk : ncols;
@@ -66,7 +53,7 @@ __global__ __launch_bounds__(256) void cross_grad_kernel(const double* __restric
         for (int b = 0; b < G; ++b) vj[b] = cj[b];
 #pragma unroll
         for (int k = 0; k < R; ++k) {
-            double df[DP];
+            double df[DP];  // the difference loop stays written out: as a function of its own it moves the register allocation of all 81 instances
             double d2 = 0.0;
 #pragma unroll
             for (int d = 0; d < DP; ++d) {
@@ -76,46 +63,26 @@ __global__ __launch_bounds__(256) void cross_grad_kernel(const double* __restric
             double kv, hv;
             kappa_hfac_hot_from_d2<KIND, PREC>(d2, tab, kv, hv);
 #pragma unroll
-            for (int b = 0; b < G; ++b) {
-                const double t = hv * vj[b];
-#pragma unroll
-                for (int d = 0; d < DP; ++d) acc[k][b][d] = __builtin_fma(t, df[d], acc[k][b][d]);
-                acc[k][b][DP] = __builtin_fma(kv, vj[b], acc[k][b][DP]);
-            }
+            for (int b = 0; b < G; ++b) row_slab_grad_acc(acc[k][b], hv, kv, vj[b], df);
         }
     }
 #pragma unroll
-    for (int k = 0; k < R; ++k) {
-        const int64_t row = rbase + (int64_t)k * 256;
-        if (row < nrows) {
-            double* __restrict__ o = part + ((int64_t)blockIdx.y * nrows + row) * (G * (DP + 1));
-#pragma unroll
-            for (int b = 0; b < G; ++b)
-#pragma unroll
-                for (int d = 0; d <= DP; ++d) o[b * (DP + 1) + d] = acc[k][b][d];
-        }
-    }
+    for (int k = 0; k < R; ++k) row_slab_store(part, nrows, rbase + (int64_t)k * 256, acc[k]);
 }
-
-struct InputGradCentre { double c[CGLB_MAX_D_NARROW]; };
 
 // grid (row blocks of 256 R rows, feature chunks of jchunk); rec points at the first record of the block of 8 columns, sub at the group inside it
 template <int DP, int R, int G>
-__global__ __launch_bounds__(256) void feature_grad_kernel(const double* __restrict__ X, int d, InputGradCentre cen, int64_t nrows,
+__global__ __launch_bounds__(256) void feature_grad_kernel(const double* __restrict__ X, int d, RowSlabCentre cen, int64_t nrows,
                                                            const double* __restrict__ rec, int sub, int64_t F, int64_t jchunk, double* __restrict__ part) {
-    constexpr int RL = INPUT_GRAD_FEATURE_REC(DP);
+    constexpr int RL = FEATURE_REC(DP);
     const int64_t rbase = (int64_t)blockIdx.x * (256 * R) + threadIdx.x;
     double z[R][DP], acc[R][G][DP + 1];
 #pragma unroll
     for (int k = 0; k < R; ++k) {
-        int64_t row = rbase + (int64_t)k * 256;
-        row = row < nrows ? row : nrows - 1;
+        const int64_t row = row_slab_clamped(rbase, k, nrows);
 #pragma unroll
         for (int q = 0; q < DP; ++q) z[k][q] = q < d ? X[row * d + q] - cen.c[q] : 0.0;
-#pragma unroll
-        for (int b = 0; b < G; ++b)
-#pragma unroll
-            for (int q = 0; q <= DP; ++q) acc[k][b][q] = 0.0;
+        row_slab_zero(acc[k]);
     }
     const int64_t j0 = (int64_t)blockIdx.y * jchunk;
     const int64_t j1 = (j0 + jchunk < F) ? j0 + jchunk : F;
@@ -135,31 +102,17 @@ __global__ __launch_bounds__(256) void feature_grad_kernel(const double* __restr
             double cv, sv;
             sincos_turns(ph, cv, sv);
 #pragma unroll
-            for (int b = 0; b < G; ++b) {
-                const double t = sv * wj[b];
-#pragma unroll
-                for (int q = 0; q < DP; ++q) acc[k][b][q] = __builtin_fma(t, om[q], acc[k][b][q]);
-                acc[k][b][DP] = __builtin_fma(cv, wj[b], acc[k][b][DP]);
-            }
+            for (int b = 0; b < G; ++b) row_slab_grad_acc(acc[k][b], sv, cv, wj[b], om);
         }
     }
 #pragma unroll
-    for (int k = 0; k < R; ++k) {
-        const int64_t row = rbase + (int64_t)k * 256;
-        if (row < nrows) {
-            double* __restrict__ o = part + ((int64_t)blockIdx.y * nrows + row) * (G * (DP + 1));
-#pragma unroll
-            for (int b = 0; b < G; ++b)
-#pragma unroll
-                for (int q = 0; q <= DP; ++q) o[b * (DP + 1) + q] = acc[k][b][q];
-        }
-    }
+    for (int k = 0; k < R; ++k) row_slab_store(part, nrows, rbase + (int64_t)k * 256, acc[k]);
 }
 
 // the slabs in fixed order, then the constants: gout[(i * S + b) * d + k] = gs.g[k] * sum_js part[js][i][b][k] (k < d), out[i * ldo + b] = vscale * sum_js
 // part[js][i][b][dp] (out may be NULL), b < sg.  out / gout point at the group's first column; one thread per (i, b, k <= dp)
 __global__ __launch_bounds__(256) void input_grad_finish_kernel(const double* __restrict__ part, int jsplit, int64_t nrows, int g, int sg, int dp, int d,
-                                                                double vscale, InputGradScale gs, double* __restrict__ out, int64_t ldo,
+                                                                double vscale, RowSlabGradScale gs, double* __restrict__ out, int64_t ldo,
                                                                 double* __restrict__ gout, int64_t S) {
     const int64_t per = (int64_t)g * (dp + 1);
     const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -202,12 +155,7 @@ __global__ __launch_bounds__(256) void input_grad_paths_kernel(double mean, cons
 int input_grad_rows_per_block(const cglb_ctx* c) { return 256 * input_grad_rows_per_lane(c->Dp); }
 int input_grad_width(const cglb_ctx* c) { return input_grad_group_width(c->Dp); }
 
-static int64_t input_grad_slot_cap(int64_t nrows, int g, int dp) {
-    const int64_t cap = (int64_t)INPUT_GRAD_SLAB / (nrows * g * (dp + 1));
-    return std::max<int64_t>(1, std::min<int64_t>(INPUT_GRAD_SLOTS, cap));
-}
-
-static int input_grad_finish(cglb_ctx* c, int64_t jsplit, int64_t nrows, int g, int sg, double vscale, const InputGradScale& gs, double* out, int64_t ldo,
+static int input_grad_finish(cglb_ctx* c, int64_t jsplit, int64_t nrows, int g, int sg, double vscale, const RowSlabGradScale& gs, double* out, int64_t ldo,
                              double* gout, int64_t S) {
     const int64_t total = nrows * g * (c->Dp + 1);
     hipLaunchKernelGGL(input_grad_finish_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, c->stream, (const double*)c->ig_part, (int)jsplit, nrows, g,
@@ -218,19 +166,13 @@ static int input_grad_finish(cglb_ctx* c, int64_t jsplit, int64_t nrows, int g, 
 
 // one group of G columns for the rows (XhRow, nrows <= INPUT_GRAD_ROWS)
 template <int KIND, int DP>
-static int cross_grad_group(cglb_ctx* c, const double* XhRow, int64_t nrows, const double* Vi, int64_t ldv, int sg, const InputGradScale& gs, double* out,
+static int cross_grad_group(cglb_ctx* c, const double* XhRow, int64_t nrows, const double* Vi, int64_t ldv, int sg, const RowSlabGradScale& gs, double* out,
                             int64_t ldo, double* gout, int64_t S) {
     constexpr int R = input_grad_rows_per_lane(DP), G = input_grad_group_width(DP);
     const int64_t ncols = c->N;
     const int64_t bx = (nrows + 256 * R - 1) / (256 * R);
-    // the column split of the plain kernel (kernels_kff.hip: kff_pairs_range), capped by the slab
-    int64_t jsplit = c->kff_jsplit > 0 ? c->kff_jsplit : (8192 + bx - 1) / bx;
-    jsplit = std::min(jsplit, input_grad_slot_cap(nrows, G, DP));
-    if (jsplit > (ncols + 63) / 64) jsplit = (ncols + 63) / 64;
-    if (jsplit < 1) jsplit = 1;
-    int64_t jchunk = (ncols + jsplit - 1) / jsplit;
-    jchunk = (jchunk + 1) & ~(int64_t)1;
-    jsplit = (ncols + jchunk - 1) / jchunk;
+    int64_t jsplit = 0, jchunk = 0;
+    row_slab_pair_split(c->kff_jsplit, bx, ncols, row_slab_slot_cap(nrows, G * (DP + 1)), true, &jsplit, &jchunk);
     CGLB_TRY(c->mem.reserve(c, &c->ig_part, &c->ig_part_cap, (size_t)jsplit * nrows * G * (DP + 1) * sizeof(double)));
     using T = double;
     CGLB_DISPATCH_PREC(c, hipLaunchKernelGGL((cross_grad_kernel<KIND, DP, R, G, PREC>), dim3((unsigned)bx, (unsigned)jsplit), dim3(256), 0, c->stream, XhRow, nrows,
@@ -243,11 +185,9 @@ static int cross_grad_group(cglb_ctx* c, const double* XhRow, int64_t nrows, con
 // S .. ldv - 1 readable.  XhRow: hot-scaled new points.  Rows in blocks of INPUT_GRAD_ROWS, columns in groups of input_grad_group_width.
 int launch_cross_grad(cglb_ctx* c, const void* XhRow, int64_t nrows, const double* Vi, int64_t ldv, int S, double* out, int64_t ldo, double* gout) {
     if (c->dtype != CGLB_F64 || is_wide(c)) return cglb_fail(c, CGLB_ERR_BAD_ARG, "the input-gradient cross product needs an fp64 context of at most 32 input dimensions");
-    if (S < 1 || ldv < S || (ldv % INPUT_GRAD_REC_SP) || !gout || (out && ldo < S))
+    if (S < 1 || ldv < S || (ldv % CROSS_MULTI_SP) || !gout || (out && ldo < S))
         return cglb_fail(c, CGLB_ERR_BAD_ARG, "bad column count, leading dimension or output of the input-gradient cross product");
-    InputGradScale gs;
-    const double ks = cglb_kscale(c) * cglb_hot_scale(c);  // delta_hot = ks (x*_k - x_jk) / l_k
-    for (int k = 0; k < CGLB_MAX_D_NARROW; ++k) gs.g[k] = k < c->D ? -c->var / (c->ls[k] * ks) : 0.0;
+    const RowSlabGradScale gs = row_slab_cross_grad_scale(c, c->ls, c->var);
     const int G = input_grad_group_width(c->Dp);
     for (int64_t i0 = 0; i0 < nrows; i0 += INPUT_GRAD_ROWS) {
         const int64_t nr = std::min<int64_t>(INPUT_GRAD_ROWS, nrows - i0);
@@ -264,39 +204,33 @@ int launch_cross_grad(cglb_ctx* c, const void* XhRow, int64_t nrows, const doubl
 template <int DP>
 static int feature_grad_group(cglb_ctx* c, const double* X, int64_t nrows, const double* rec, int sub, int64_t F, int64_t jsplit, int64_t jchunk, unsigned bx) {
     constexpr int R = input_grad_rows_per_lane(DP), G = input_grad_group_width(DP);
-    InputGradCentre cen;
-    for (int k = 0; k < CGLB_MAX_D_NARROW; ++k) cen.c[k] = k < c->D ? c->xmean[k] : 0.0;
-    hipLaunchKernelGGL((feature_grad_kernel<DP, R, G>), dim3(bx, (unsigned)jsplit), dim3(256), 0, c->stream, X, c->D, cen, nrows, rec, sub, F, jchunk,
-                       (double*)c->ig_part);
+    hipLaunchKernelGGL((feature_grad_kernel<DP, R, G>), dim3(bx, (unsigned)jsplit), dim3(256), 0, c->stream, X, c->D, row_slab_centre(c), nrows, rec, sub, F,
+                       jchunk, (double*)c->ig_part);
     CGLB_LAUNCH_CHECK(c);
     return CGLB_OK;
 }
 
-// out[i * ldo + s] (out may be NULL) and gout[(i * S + s) * D + k] from the records launch_feature_operand left.  X: dev [nrows][D] raw rows.  The chunk
-// rule of feature_split at this kernel's rows per block, capped by the slab
+// out[i * ldo + s] (out may be NULL) and gout[(i * S + s) * D + k] from the records launch_feature_operand left.  X: dev [nrows][D] raw rows.  The feature
+// rule (row_slab_feature_split) at this kernel's rows per block, capped by the slab
 int launch_feature_grad(cglb_ctx* c, const double* X, int64_t nrows, int64_t F, int S, double* out, int64_t ldo, double* gout) {
     if (c->dtype != CGLB_F64 || is_wide(c)) return cglb_fail(c, CGLB_ERR_BAD_ARG, "the input-gradient feature product needs an fp64 context of at most 32 input dimensions");
     if (S < 1 || F < 1 || !gout || (out && ldo < S)) return cglb_fail(c, CGLB_ERR_BAD_ARG, "bad feature count, column count or output of the input-gradient feature product");
     const int G = input_grad_group_width(c->Dp);
     const double amp = std::sqrt(2.0 * c->var / (double)F);
-    InputGradScale gs;
+    RowSlabGradScale gs;
     for (int k = 0; k < CGLB_MAX_D_NARROW; ++k) gs.g[k] = k < c->D ? -6.283185307179586476925286766559 * amp : 0.0;  // the records hold omega / (2 pi l)
-    const int64_t rl = INPUT_GRAD_FEATURE_REC(c->Dp);
+    const int64_t rl = FEATURE_REC(c->Dp);
     const int64_t rb = input_grad_rows_per_block(c);
     for (int64_t i0 = 0; i0 < nrows; i0 += INPUT_GRAD_ROWS) {
         const int64_t nr = std::min<int64_t>(INPUT_GRAD_ROWS, nrows - i0);
         const int64_t bx = (nr + rb - 1) / rb;
-        int64_t jsplit = (INPUT_GRAD_FEATURE_TARGET_WG + bx - 1) / bx;
-        jsplit = std::min(jsplit, input_grad_slot_cap(nr, G, c->Dp));
-        if (jsplit > (F + INPUT_GRAD_FEATURE_MIN_CHUNK - 1) / INPUT_GRAD_FEATURE_MIN_CHUNK) jsplit = (F + INPUT_GRAD_FEATURE_MIN_CHUNK - 1) / INPUT_GRAD_FEATURE_MIN_CHUNK;
-        if (jsplit < 1) jsplit = 1;
-        const int64_t jchunk = (F + jsplit - 1) / jsplit;
-        jsplit = (F + jchunk - 1) / jchunk;
+        int64_t jsplit = 0, jchunk = 0;
+        row_slab_feature_split(rb, nr, F, row_slab_slot_cap(nr, G * (c->Dp + 1)), &jsplit, &jchunk);
         CGLB_TRY(c->mem.reserve(c, &c->ig_part, &c->ig_part_cap, (size_t)jsplit * nr * G * (c->Dp + 1) * sizeof(double)));
         for (int b0 = 0; b0 < S; b0 += G) {
             const int sg = std::min(G, S - b0);
-            const double* rec = c->ft_rec + (int64_t)(b0 / INPUT_GRAD_REC_SP) * F * rl;
-            CGLB_DISPATCH_DP(c->Dp, CGLB_TRY((feature_grad_group<DP>(c, X + i0 * c->D, nr, rec, b0 % INPUT_GRAD_REC_SP, F, jsplit, jchunk, (unsigned)bx))));
+            const double* rec = c->ft_rec + (int64_t)(b0 / FEATURE_SP) * F * rl;
+            CGLB_DISPATCH_DP(c->Dp, CGLB_TRY((feature_grad_group<DP>(c, X + i0 * c->D, nr, rec, b0 % FEATURE_SP, F, jsplit, jchunk, (unsigned)bx))));
             CGLB_TRY(input_grad_finish(c, jsplit, nr, G, sg, amp, gs, out ? out + i0 * ldo + b0 : nullptr, ldo, gout + (i0 * S + b0) * c->D, S));
         }
     }

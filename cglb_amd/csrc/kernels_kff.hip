@@ -9,10 +9,11 @@
 //     SGPRs and fed straight into v_fma_f64 as the scalar source: no VGPRs, no LDS traffic, no bank
 //     conflicts for the streamed side;
 //   * pair value by the Gram form (DP fma + 1 add), table-driven 2^x (devmath.h);
-//   * columns are split over blockIdx.y; partial row sums go to a [jsplit][nrows] slab and are
-//     combined in fixed order (bitwise reproducible, no atomics).
+//   * columns are split over blockIdx.y (row_slab_pair_split); partial row sums go to a [jsplit][nrows]
+//     slab and are combined in fixed order (bitwise reproducible, no atomics).
 #include "devmath.h"
 #include "dispatch.h"
+#include "row_slab.h"  // the column split (host)
 
 template <typename T, int KIND, int DP, int R, bool CLAMP, int PREC>
 __global__ __launch_bounds__(256) void kff_matvec_kernel(const T* __restrict__ XsRow, const T* __restrict__ xaRow,
@@ -226,13 +227,8 @@ static int kff_pairs_range(cglb_ctx* c, const T* XsRow, const T* xaRow, int64_t 
     const int R = rows_per_thread(c);
     const int64_t ncols = col1 - col0;
     const int64_t bx = (nrows + 256 * R - 1) / (256 * R);
-    int64_t jsplit = c->kff_jsplit > 0 ? c->kff_jsplit : (8192 + bx - 1) / bx;
-    if (jsplit > max_slots) jsplit = max_slots;
-    if (jsplit > (ncols + 63) / 64) jsplit = (ncols + 63) / 64;
-    if (jsplit < 1) jsplit = 1;
-    int64_t jchunk = (ncols + jsplit - 1) / jsplit;
-    jchunk = (jchunk + 1) & ~(int64_t)1;
-    jsplit = (ncols + jchunk - 1) / jchunk;
+    int64_t jsplit = 0, jchunk = 0;
+    row_slab_pair_split(c->kff_jsplit, bx, ncols, max_slots, true, &jsplit, &jchunk);
     *nslots = jsplit;
     dim3 grid((unsigned)bx, (unsigned)jsplit);
 #define KFF_LAUNCH(RR)                                                                                               \

@@ -5,28 +5,24 @@
 // shares (q of the CGLB mean, alpha of the exact GP); Wt[m][i] is new point i's OWN weight of point m (C^T of the variance), which the shared-column
 // product of kernels_input_grad.hip can only express with one column per new point.  One evaluation of a pair serves both sums.
 //
-// The decomposition is that of cross_grad_kernel: a lane owns R new points (coordinates and R x NW x (DP + 1) accumulators in VGPRs for the whole
-// launch, NW = 2 or 1 by the template flags); point p_m and u[m] are wave-uniform scalar loads; Wt[m][.] has the new-point index fastest (ldw >=
-// n_new, the layout of the predictive panels), so a wave reads 64 consecutive doubles per point, and the next point's weight is requested before the
-// current pair's profile.  Rows past n_new read the last row's weight (never the padding columns [n_new, ldw)) and write nothing.  The point range
-// is split over blockIdx.y by the kff_jsplit rule; partial sums go to a slab [jsplit][nrows][NW][DP + 1] that exactly one workgroup writes, and ONE
-// finish kernel adds the slabs in fixed order and applies f, -f / (l_k hot scale) and the caller's factor of the Wt gradient (-2 for g_var): no
-// atomics, bitwise repeatable.  The split never depends on NW, and the u sums of the two-weight instance are the operations of the one-weight
+// A row-slab product (row_slab.h) of cross_grad_kernel's pairs: a lane keeps the coordinates and R x NW x (DP + 1) accumulators, NW = 2 or 1 by the
+// template flags; point p_m and u[m] are wave-uniform scalar loads; Wt[m][.] has the new-point index fastest (ldw >= n_new, the layout of the
+// predictive panels), so a wave reads 64 consecutive doubles per point, and the next point's weight is requested before the current pair's
+// profile.  Rows past n_new read the last row's weight (never the padding columns [n_new, ldw)) and write nothing.  The point range is split by the
+// kff_jsplit rule; slab [jsplit][nrows][NW][DP + 1]; ONE finish kernel applies f, -f / (l_k hot scale) and the caller's factor of the Wt gradient
+// (-2 for g_var).  The split never depends on NW, and the u sums of the two-weight instance are the operations of the one-weight
 // instance, so every output is bitwise the same whichever of the others are requested.
 // Pair: DIRECT differences in hot units and kappa_hfac_hot_from_d2 (always the range-clamped 2^x), as cross_grad_kernel and for its reason; a
 // coincident pair has delta = 0 exactly and adds exactly zero to the gradient.  fp64, Dp <= 32.  Register use of every instance: DESIGN.md 4i.
 #include "pair_common.h"
+#include "row_slab.h"
 #include <cstring>
 
-#define PREDICT_GRAD_SLOTS 256        // most point chunks of one launch
 #define PREDICT_GRAD_ROWS 4096        // new points per launch
-#define PREDICT_GRAD_SLAB (1 << 24)   // doubles of the slab of one launch (128 MiB): caps the chunk count
 
 // rows per lane by padded width, chosen so that R (DP + 2 (DP + 1) + 2) + DP row-resident doubles (coordinates, both accumulator sets, the current and the
 // next weight, the differences of the pair in flight) stay near 100: 4 up to width 4 (64 + 4), 2 up to 8 (56 + 8), 1 beyond (100 + 32 at 32)
 static constexpr int predict_grad_rows_per_lane(int dp) { return dp <= 4 ? 4 : (dp <= 8 ? 2 : 1); }
-
-struct PredictGradScale { double g[CGLB_MAX_D_NARROW]; };  // constant of gradient component k
 
 // grid (row blocks of 256 R new points, chunks of jchunk points)
 template <int KIND, int DP, int R, bool HAS_U, bool HAS_W, int PREC>
@@ -44,14 +40,10 @@ __global__ __launch_bounds__(256) void weighted_grad_kernel(const double* __rest
     const int64_t j1 = (j0 + jchunk < npts) ? j0 + jchunk : npts;
 #pragma unroll
     for (int k = 0; k < R; ++k) {
-        const int64_t row = rbase + (int64_t)k * 256;
-        rowc[k] = row < nrows ? row : nrows - 1;
+        rowc[k] = row_slab_clamped(rbase, k, nrows);
 #pragma unroll
         for (int d = 0; d < DP; ++d) xi[k][d] = XhRow[rowc[k] * DP + d];
-#pragma unroll
-        for (int b = 0; b < NW; ++b)
-#pragma unroll
-            for (int d = 0; d <= DP; ++d) acc[k][b][d] = 0.0;
+        row_slab_zero(acc[k]);
         wn[k] = (HAS_W && j0 < j1) ? Wt[j0 * ldw + rowc[k]] : 0.0;
     }
     for (int64_t j = j0; j < j1; ++j) {
@@ -67,6 +59,9 @@ __global__ __launch_bounds__(256) void weighted_grad_kernel(const double* __rest
         }
 #pragma unroll
         for (int k = 0; k < R; ++k) {
+            // Written out, not row_slab_grad_acc / row_slab_store (row_slab.h): with the two calls the register allocation of 270 of the 351 instances
+            // moves (167 with the accumulate alone, 27 with the store alone).  The difference loop as a function of its own moves 189 (and all 81 of
+            // cross_grad_kernel, which keeps it written out too).
             double df[DP];
             double d2 = 0.0;
 #pragma unroll
@@ -107,7 +102,7 @@ __global__ __launch_bounds__(256) void weighted_grad_kernel(const double* __rest
 // gscale[b] multiplies the gradient constant, add_u adds the u gradient to what gout[0] holds (the K_*f v term of cglb_predict_grad)
 struct PredictGradOut { double* out[2]; double* gout[2]; double gscale[2]; };
 __global__ __launch_bounds__(256) void weighted_grad_finish_kernel(const double* __restrict__ part, int jsplit, int64_t nrows, int nw, int dp, int d, double vscale,
-                                                                   PredictGradScale gs, PredictGradOut o, int add_u) {
+                                                                   RowSlabGradScale gs, PredictGradOut o, int add_u) {
     const int64_t per = (int64_t)nw * (dp + 1);
     const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= nrows * per) return;
@@ -172,9 +167,7 @@ int launch_weighted_grad(cglb_ctx* c, const double* ls, double var, const double
     if ((!u && !Wt) || npts < 1 || (Wt && ldw < nrows) || (!u && (out_u || gout_u)) || (!Wt && (out_w || gout_w)))
         return cglb_fail(c, CGLB_ERR_BAD_ARG, "bad weights, leading dimension or outputs of the row-weighted gradient product");
     if (nrows == 0) return CGLB_OK;
-    PredictGradScale gs;
-    const double ks = cglb_kscale(c) * cglb_hot_scale(c);  // delta_hot = ks (x*_k - p_k) / l_k
-    for (int k = 0; k < CGLB_MAX_D_NARROW; ++k) gs.g[k] = k < c->D ? -var / (ls[k] * ks) : 0.0;
+    const RowSlabGradScale gs = row_slab_cross_grad_scale(c, ls, var);
     const int nw = (u ? 1 : 0) + (Wt ? 1 : 0);
     const int R = predict_grad_rows_per_lane(c->Dp);
     for (int k = 0; k < 2; ++k)
@@ -184,13 +177,10 @@ int launch_weighted_grad(cglb_ctx* c, const double* ls, double var, const double
     for (int64_t i0 = 0; i0 < nrows; i0 += PREDICT_GRAD_ROWS) {
         const int64_t nr = std::min<int64_t>(PREDICT_GRAD_ROWS, nrows - i0);
         const int64_t bx = (nr + 256 * R - 1) / (256 * R);
-        // the column split of the plain kernel (kernels_kff.hip: kff_pairs_range), capped by the slab of the two-weight instance whatever nw is
-        int64_t jsplit = c->kff_jsplit > 0 ? c->kff_jsplit : (8192 + bx - 1) / bx;
-        jsplit = std::min<int64_t>(jsplit, std::max<int64_t>(1, std::min<int64_t>(PREDICT_GRAD_SLOTS, (int64_t)PREDICT_GRAD_SLAB / (nr * 2 * (c->Dp + 1)))));
-        if (jsplit > (npts + 63) / 64) jsplit = (npts + 63) / 64;
-        if (jsplit < 1) jsplit = 1;
-        const int64_t jchunk = (npts + jsplit - 1) / jsplit;
-        jsplit = (npts + jchunk - 1) / jchunk;
+        // capped by the slab of the two-weight instance whatever nw is.  even = false: this product never rounded its chunk to an even length as the
+        // other pair kernels do; no reason is on record, kept as measured and tested
+        int64_t jsplit = 0, jchunk = 0;
+        row_slab_pair_split(c->kff_jsplit, bx, npts, row_slab_slot_cap(nr, 2 * (c->Dp + 1)), false, &jsplit, &jchunk);
         CGLB_TRY(c->mem.reserve(c, &c->ig_part, &c->ig_part_cap, (size_t)jsplit * nr * nw * (c->Dp + 1) * sizeof(double)));
         const double* xh = XhRow + i0 * c->Dp;
         const double* wt = Wt ? Wt + i0 : nullptr;

@@ -22,6 +22,7 @@ import scipy.linalg
 import gpr_ref
 import love_ref
 import sample_ref as sr
+import slab_rules
 
 LD = np.longdouble
 U = 2.0 ** -53
@@ -180,7 +181,7 @@ def paths(kind, X, y, hypers, xnew, omega, b, W, eps, U=None):
 
 
 # ---- launch geometry (csrc/kernels_input_grad.hip) ---------------------------------------------------------------------------------------------
-SLOTS, ROWS, SLAB = 256, 4096, 1 << 24
+ROWS = 4096
 pad_dim = sr.pad_dim
 
 
@@ -198,25 +199,18 @@ def rows_per_block(d: int) -> int:
 
 
 def _slot_cap(n_rows: int, d: int) -> int:
-    return max(1, min(SLOTS, SLAB // (n_rows * group_width(d) * (pad_dim(d) + 1))))
+    return slab_rules.slot_cap(n_rows, group_width(d) * (pad_dim(d) + 1))
 
 
 def cross_split(n_rows: int, N: int, d: int, forced: int = 0):
     """(chunks, chunk length) of one launch of the cross product (n_rows <= ROWS): the kff_jsplit rule, capped by the slab."""
     bx = (n_rows + rows_per_block(d) - 1) // rows_per_block(d)
-    js = forced if forced > 0 else (8192 + bx - 1) // bx
-    js = max(1, min(js, _slot_cap(n_rows, d), (N + 63) // 64))
-    chunk = (N + js - 1) // js
-    chunk = (chunk + 1) & ~1
-    return (N + chunk - 1) // chunk, chunk
+    return slab_rules.pair_split(forced, bx, N, _slot_cap(n_rows, d), even=True)
 
 
 def feature_split(n_rows: int, F: int, d: int):
-    """(chunks, chunk length) of one launch of the feature product (n_rows <= ROWS): sample_ref.feature_split at this kernel's rows per block."""
-    bx = (n_rows + rows_per_block(d) - 1) // rows_per_block(d)
-    js = max(1, min((sr.TARGET_WG + bx - 1) // bx, _slot_cap(n_rows, d), (F + sr.MIN_CHUNK - 1) // sr.MIN_CHUNK))
-    chunk = (F + js - 1) // js
-    return (F + chunk - 1) // chunk, chunk
+    """(chunks, chunk length) of one launch of the feature product (n_rows <= ROWS): the feature rule at this kernel's rows per block, capped by the slab."""
+    return slab_rules.feature_split(rows_per_block(d), n_rows, F, _slot_cap(n_rows, d))
 
 
 # ---- tolerances ---------------------------------------------------------------------------------------------------------------------------

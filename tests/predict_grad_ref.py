@@ -30,6 +30,7 @@ import torch
 
 import input_grad_ref as ig
 import predict_ref as pr
+import slab_rules
 
 LD = np.longdouble
 TOL_PREDICT = 1e-8
@@ -63,7 +64,7 @@ def _rows(n):
 
 
 # ---- launch geometry (csrc/kernels_predict_grad.hip) ----------------------------------------------------------------------------------------------
-SLOTS, ROWS, SLAB = 256, 4096, 1 << 24
+ROWS = 4096
 
 
 def rows_per_lane(d: int) -> int:
@@ -76,12 +77,10 @@ def rows_per_block(d: int) -> int:
 
 
 def weighted_split(n_rows: int, n_pts: int, d: int, forced: int = 0):
-    """(chunks, chunk length) of one launch (n_rows <= ROWS): the kff_jsplit rule, capped by the slab of the two-weight instance."""
+    """(chunks, chunk length) of one launch (n_rows <= ROWS): the kff_jsplit rule without the even rounding, capped by the slab of the two-weight
+    instance."""
     bx = (n_rows + rows_per_block(d) - 1) // rows_per_block(d)
-    js = forced if forced > 0 else (8192 + bx - 1) // bx
-    js = max(1, min(js, SLOTS, max(1, SLAB // (n_rows * 2 * (ig.pad_dim(d) + 1))), (n_pts + 63) // 64))
-    chunk = (n_pts + js - 1) // js
-    return (n_pts + chunk - 1) // chunk, chunk
+    return slab_rules.pair_split(forced, bx, n_pts, slab_rules.slot_cap(n_rows, 2 * (ig.pad_dim(d) + 1)), even=False)
 
 
 # ---- the product ------------------------------------------------------------------------------------------------------------------------------

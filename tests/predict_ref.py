@@ -56,6 +56,7 @@ import scipy.linalg as sla
 import fp32_error_model as em
 import geometry_cases as gc
 import gpr_ref
+import slab_rules
 from oracle import cglb_oracle as orc
 
 FAR = 1e3
@@ -89,12 +90,8 @@ def rows_per_thread(D: int, kff_rows: int = 4) -> int:
 
 def cross_slabs(n_new: int, N: int, R: int, jsplit_opt: int = 0) -> Tuple[int, int]:
     """(jchunk, slab count) of kff_pairs_range for n_new rows against N columns."""
-    bx = (n_new + 256 * R - 1) // (256 * R)
-    jsplit = jsplit_opt if jsplit_opt > 0 else (8192 + bx - 1) // bx
-    jsplit = max(1, min(jsplit, 512, (N + 63) // 64))
-    jchunk = (N + jsplit - 1) // jsplit
-    jchunk = (jchunk + 1) & ~1
-    return jchunk, (N + jchunk - 1) // jchunk
+    count, jchunk = slab_rules.pair_split(jsplit_opt, (n_new + 256 * R - 1) // (256 * R), N, 512, even=True)   # 512: the slots of kff_generic
+    return jchunk, count
 
 
 @dataclass(frozen=True)

@@ -16,6 +16,8 @@ import math
 import numpy as np
 import scipy.linalg
 
+import slab_rules
+
 U = 2.0 ** -53
 #: the absolute error bound cglb_amd/csrc/devmath.h states for cos_turns (CGLB_COS_TURNS_ERR)
 COS_TURNS_ERR = 3e-16
@@ -130,7 +132,7 @@ def features_from_draws(kind, z, chi2, u):
 
 # ---- launch geometry (cglb_amd/csrc/kernels_feature_multi.hip, cglb_internal.h) ---------------------------------------------------------
 PAD = (1, 2, 3, 4, 6, 8, 10, 12, 16, 20, 24, 28, 32)
-SLOTS, MIN_CHUNK, TARGET_WG, SP = 256, 64, 2048, 8
+SP = 8
 
 
 def pad_dim(d: int) -> int:
@@ -152,13 +154,8 @@ def rows_per_block(d: int) -> int:
 
 
 def feature_split(n_rows: int, F: int, d: int):
-    """(chunks, chunk length) of one launch: feature_split of the library."""
-    rb = rows_per_block(d)
-    bx = max((n_rows + rb - 1) // rb, 1)
-    js = min((TARGET_WG + bx - 1) // bx, SLOTS, (F + MIN_CHUNK - 1) // MIN_CHUNK)
-    js = max(js, 1)
-    chunk = (F + js - 1) // js
-    return (F + chunk - 1) // chunk, chunk
+    """(chunks, chunk length) of one launch: the feature rule at this kernel's rows per block."""
+    return slab_rules.feature_split(rows_per_block(d), n_rows, F)
 
 
 def feature_tolerance(x, c, ls, variance, omega, b, W):
