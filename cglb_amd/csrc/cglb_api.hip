@@ -1102,6 +1102,7 @@ int cglb_set_option(cglb_ctx* c, const char* name, int64_t value) {
     else if (!strcmp(name, "final_matvec")) c->final_matvec = (int)value;
     else if (!strcmp(name, "wide_grad_sym")) c->wide_grad_sym = (int)value;
     else if (!strcmp(name, "wide_reg")) { c->wide_reg = (int)value; c->pwh_src = nullptr; }
+    else if (!strcmp(name, "grad_multi_mid")) c->grad_multi_mid = (int)value;
     else if (!strcmp(name, "chol_mode")) c->chol_mode = (int)value;
     else if (!strcmp(name, "grad_trsm")) c->grad_trsm = (int)value;
     else if (!strcmp(name, "precond_mode")) {
@@ -1918,6 +1919,7 @@ int cglb_get_stat(cglb_ctx* c, const char* name, double* value) {
         if (rc != -1) return rc;
     }
     if (!strcmp(name, "matmat_native")) { *value = (c->have_data && kff_multi_native(c)) ? 1.0 : 0.0; return CGLB_OK; }  // shared-kernel instance or single mat-vecs
+    if (!strcmp(name, "grad_multi_native")) { *value = (c->have_data && grad_multi_native(c)) ? 1.0 : 0.0; return CGLB_OK; }  // multi-pair gradient instance or single passes
     if (!strcmp(name, "exp_clamp") || !strcmp(name, "m32_bias")) {  // the exponent-range regime of the last cglb_set_hypers
         if (!c->have_hypers) return cglb_fail(c, CGLB_ERR_STATE, "set_hypers must precede this statistic");
         *value = !strcmp(name, "exp_clamp") ? (c->exp_clamp ? 1.0 : 0.0) : c->m32_bias;

@@ -74,6 +74,7 @@ struct cglb_ctx {
     int Dh = 0;        // 32 < D <= 96, fp64: padded width (48, 64, 80, 96) of the hot operand set Xh kept for the register-resident mat-vec
     int wide_grad_sym = 1;  // option "wide_grad_sym": 0 evaluates every tile of the tiled K_ff gradient pass (A/B)
     int wide_reg = 1;  // option "wide_reg": 0 sends that mat-vec through the Gram tiles of kernels_wide.hip as well (A/B, fallback)
+    int grad_multi_mid = 1;  // option "grad_multi_mid": 0 sends the multi-pair gradient pass of a mid-width context through single passes (A/B, fallback)
     size_t esz = 8;
     hipStream_t stream = nullptr;
     rocblas_handle blas = nullptr;
@@ -429,6 +430,8 @@ int launch_cross_matvec(cglb_ctx* c, const void* Xs_new, const void* xa_new, int
 // One evaluation of every kernel value for up to 8 pairs where grad_multi_native(c), S single passes elsewhere.
 bool grad_multi_native(const cglb_ctx* c);
 int launch_grad_kff_multi(cglb_ctx* c, const void* U, const void* V, int S, double* out);
+// kernels_grad_multi_mid.hip: out (+)= the same sums of one group of 2 .. grad_multi_mid_group(Dh) pairs of a context with mid_reg(c), both exponent ranges
+int launch_grad_kff_multi_mid(cglb_ctx* c, const double* U, const double* V, int sg, double* out, int accumulate);
 // The row-slab products (decomposition, chunk rules, layout constants and the shared value finish kernel: row_slab.h), one file each:
 // kernels_cross_multi.hip: out[i * ldo + s] = var * sum_j kappa(row_i, x_j) Vi[j * ldv + s], s < S; Vi dev [N][ldv] row-major (ldv a multiple of 8, zero
 // padded), rows hot-scaled; every kernel value evaluated once per group of 8 columns.  fp64, Dp <= 32.  Bitwise repeatable.

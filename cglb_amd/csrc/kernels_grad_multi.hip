@@ -13,8 +13,9 @@
 // Partial sums go to slabs, part[(blockIdx.y * gridDim.x + blockIdx.x) * (DP + 1) + d], written by exactly one workgroup each and summed in
 // fixed order by the finalize kernel: no atomics, bitwise reproducible.  S > 8 runs in groups of 8 whose sums are added in group order.
 // The exponent runs through the range-clamped 2^x like the single direct-difference pass, so the clamped exponent range is native too.
-// Native scope: fp64, Dp <= 32, one rank, one shard covering all rows.  Elsewhere: S single launch_grad_kff passes and the kappa sums from
-// one product (launch_grad_kff_multi below).
+// Native scope: fp64, one rank, one shard covering all rows, at Dp <= 32 (the kernel of this file) and at 32 < D <= 96 with the register-resident
+// operand set (mid_reg; kernels_grad_multi_mid.hip, option "grad_multi_mid").  Elsewhere - fp32, D > 96, "wide_reg" 0, N ranks - S single
+// launch_grad_kff passes and the kappa sums from one product (launch_grad_kff_multi below).
 #include "pair_common.h"
 
 // rows per lane: 2 up to padded width 8 and 1 beyond, as the single pass.  The row-resident doubles are R (2 DP + 2 S_pad): at most 64 (DP = 8,
@@ -182,8 +183,9 @@ static int grad_multi_group(cglb_ctx* c, const double* U, const double* V, int s
     return CGLB_OK;
 }
 
+static bool grad_multi_mid_native(const cglb_ctx* c) { return mid_reg(c) && c->grad_multi_mid != 0 && grad_multi_mid_group(c->Dh) >= 2; }
 bool grad_multi_native(const cglb_ctx* c) {
-    return c->dtype == CGLB_F64 && !is_wide(c) && c->par_world == 1 && !c->comm && c->r0 == 0 && c->r1 == c->N;
+    return c->dtype == CGLB_F64 && (!is_wide(c) || grad_multi_mid_native(c)) && c->par_world == 1 && !c->comm && c->r0 == 0 && c->r1 == c->N;
 }
 
 // fall-back pieces: out[d] += g[d], d < D;  out[D] += sum_i u_i (w_i - noise v_i) / var with w = (K_ff + noise I) v  (one block, fixed order)
@@ -201,31 +203,48 @@ __global__ __launch_bounds__(256) void grad_multi_fallback_kernel(const double* 
     }
 }
 
+// S single passes added to out (overwritten first unless `accumulate`), and the kappa sums from one product:
+// u_b^T kappa v_b = u_b^T ((K_ff + noise I) v_b - noise v_b) / variance
+static int grad_multi_single_passes(cglb_ctx* c, const void* U, const void* V, int S, double* out, int accumulate) {
+    const size_t stride = (size_t)c->N * c->esz;
+    void* W = nullptr;
+    double* g = nullptr;
+    DevTemps tmp;
+    CGLB_TRY(tmp.alloc(c, &W, (size_t)S * stride));
+    CGLB_TRY(tmp.alloc(c, (void**)&g, sizeof(double) * c->D));
+    auto body = [&]() -> int {
+        CGLB_TRY(launch_kff_matmat(c, V, S, W));
+        for (int b = 0; b < S; ++b) {
+            CGLB_TRY(launch_grad_kff(c, (const char*)V + b * stride, (const char*)U + b * stride, g));
+            CGLB_DISPATCH_T(c->dtype, hipLaunchKernelGGL((grad_multi_fallback_kernel<T>), dim3(1), dim3(256), 0, c->stream, (const double*)g, c->D,
+                                                         (const T*)((const char*)U + b * stride), (const T*)((const char*)V + b * stride),
+                                                         (const T*)((const char*)W + b * stride), c->N, c->noise, c->var, out, (accumulate || b > 0) ? 1 : 0));
+            CGLB_LAUNCH_CHECK(c);
+        }
+        return CGLB_OK;
+    };
+    const int rc = body();
+    (void)hipStreamSynchronize(c->stream);  // before `tmp` releases the buffers the kernels use
+    return rc;
+}
+
 // out (device double[D + 1], overwritten): sum_b u_b^T (dK_ff/dl_d) v_b, d < D, and sum_b u_b^T kappa v_b.  U, V: device [S][N], pair b contiguous.
 int launch_grad_kff_multi(cglb_ctx* c, const void* U, const void* V, int S, double* out) {
-    if (!grad_multi_native(c)) {
-        // S single passes, and the kappa sums from one product: u_b^T kappa v_b = u_b^T ((K_ff + noise I) v_b - noise v_b) / variance
+    if (!grad_multi_native(c) || (is_wide(c) && S == 1)) {  // a single pair of a mid-width context: the single pass, bitwise what it was
         if (c->r0 != 0 || c->r1 != c->N) return cglb_fail(c, CGLB_ERR_BAD_ARG, "the multi-pair gradient pass needs a single shard covering all rows");
-        const size_t stride = (size_t)c->N * c->esz;
-        void* W = nullptr;
-        double* g = nullptr;
-        DevTemps tmp;
-        CGLB_TRY(tmp.alloc(c, &W, (size_t)S * stride));
-        CGLB_TRY(tmp.alloc(c, (void**)&g, sizeof(double) * c->D));
-        auto body = [&]() -> int {
-            CGLB_TRY(launch_kff_matmat(c, V, S, W));
-            for (int b = 0; b < S; ++b) {
-                CGLB_TRY(launch_grad_kff(c, (const char*)V + b * stride, (const char*)U + b * stride, g));
-                CGLB_DISPATCH_T(c->dtype, hipLaunchKernelGGL((grad_multi_fallback_kernel<T>), dim3(1), dim3(256), 0, c->stream, (const double*)g, c->D,
-                                                             (const T*)((const char*)U + b * stride), (const T*)((const char*)V + b * stride),
-                                                             (const T*)((const char*)W + b * stride), c->N, c->noise, c->var, out, b > 0 ? 1 : 0));
-                CGLB_LAUNCH_CHECK(c);
-            }
-            return CGLB_OK;
-        };
-        const int rc = body();
-        (void)hipStreamSynchronize(c->stream);  // before `tmp` releases the buffers the kernels use
-        return rc;
+        return grad_multi_single_passes(c, U, V, S, out, 0);
+    }
+    if (is_wide(c)) {  // mid widths: groups by the rule of pair_worklist.h (grad_multi_mid_group), added in group order; a single left-over pair last
+        const int group = grad_multi_mid_group(c->Dh);
+        for (int b0 = 0; b0 < S;) {
+            const int sg = multi_next_group(S - b0, group);
+            const double* Ug = (const double*)U + (size_t)b0 * c->N;
+            const double* Vg = (const double*)V + (size_t)b0 * c->N;
+            if (sg == 1) CGLB_TRY(grad_multi_single_passes(c, Ug, Vg, 1, out, b0 > 0 ? 1 : 0));
+            else CGLB_TRY(launch_grad_kff_multi_mid(c, Ug, Vg, sg, out, b0 > 0 ? 1 : 0));
+            b0 += sg;
+        }
+        return CGLB_OK;
     }
     for (int b0 = 0; b0 < S; b0 += 8) {
         const int sg = std::min(8, S - b0);

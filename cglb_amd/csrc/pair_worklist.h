@@ -78,3 +78,10 @@ static constexpr int multi_mid_partials(int dh, int sp) {
 static constexpr int multi_group_pad(int sg) { return sg <= 2 ? 2 : (sg <= 4 ? 4 : 8); }  // S_pad of a group of sg columns
 // columns of the next group when `left` columns remain and groups hold at most `group` (>= 2): 1 = the single left-over column
 static constexpr int multi_next_group(int left, int group) { return left < group ? left : group; }
+
+// Group rule of the mid-width multi-pair gradient pass (kernels_grad_multi_mid.hip): S pairs are cut into groups of at most `group` pairs in
+// order (multi_next_group), each group of two or more padded to S_pad = 4 or 8 (the column operands of a group fill half a 16-lane row; the
+// padding pairs cost S_pad - sg of the ~DP + 30 lane-instructions of a pair), and a single left-over pair goes through the single pass.  Every hot
+// width holds 8 inside the 256 VGPRs of two waves per SIMD (DESIGN.md section 4d has the registers of every instance); 0 = no instance.
+static constexpr int grad_multi_mid_group(int dh) { return (dh == 48 || dh == 64 || dh == 80 || dh == 96) ? 8 : 0; }
+static constexpr int grad_multi_mid_pad(int sg) { return sg <= 4 ? 4 : 8; }

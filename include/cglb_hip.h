@@ -450,8 +450,10 @@ int cglb_itergp_paths_eval(cglb_ctx* ctx, const void* xnew, int64_t n_new, const
                            int S, void* f_out, void* g_out);
 /* The gradient pass of the class on its own (tests, timing): out host double[d + 1], out[k] = sum_b u_b^T (dK_ff / dl_k) v_b for k < d and
  * out[d] = sum_b u_b^T kappa v_b (kappa = K_ff / variance), b < S.  U, V: dev [S, n_total], pair b contiguous.  Every kernel value is evaluated
- * once per unordered pair for up to 8 pairs of vectors (fp64, d <= 32: csrc/kernels_grad_multi.hip; wider inputs run S single passes); S > 8
- * runs in groups of 8 added in group order.  Bitwise reproducible.  The scope of cglb_matmat, fp64 only. */
+ * once per unordered pair for up to 8 pairs of vectors (fp64, d <= 32: csrc/kernels_grad_multi.hip; 33 ... 96 dimensions with "wide_reg" and
+ * "grad_multi_mid" 1: csrc/kernels_grad_multi_mid.hip, where a single left-over pair takes the single pass; everything else runs S single passes -
+ * cglb_get_stat "grad_multi_native" tells which); S > 8 runs in groups of 8 added in group order.  Bitwise reproducible.  The scope of
+ * cglb_matmat, fp64 only. */
 int cglb_grad_kff_multi(cglb_ctx* ctx, const void* U, const void* V, int S, double* out);
 /* average duration (ms) of `reps` back-to-back passes with S pairs (operand prep, pair kernel and fixed-order sum of every group, on the context
  * stream, no read-back), in the style of cglb_time_kernel(which = 2), which times one single pass */
@@ -484,6 +486,10 @@ int cglb_time_kernel(cglb_ctx* ctx, int which, int reps, double* ms_avg);
  * symmetric form visits each unordered pair once) - the unit count of the roofline; "kpart_bytes": size of the partial-sum slabs;
  * "matmat_native": 1 if a product of two or more columns (cglb_matmat, the batched solves) on this context in its current state - data, dtype,
  * hyper-parameters, "wide_reg", "kff_variant", ranks - runs through a shared-kernel instance, 0 if it falls back to single mat-vecs;
+ * "grad_multi_native": 1 if a group of two or more vector pairs of the multi-pair gradient pass (cglb_grad_kff_multi, the gradient of
+ * cglb_itergp_objective_and_grad) on this context in its current state - dtype, width, "wide_reg", "grad_multi_mid", ranks, shard - runs in ONE
+ * pass over the kernel values (fp64 on one rank and one shard covering all rows, up to 32 dimensions and, register-resident, 33 ... 96), 0 if
+ * it runs one single pass per pair and takes the kappa sums from one product;
  * "exp_clamp" | "m32_bias": the exponent-range regime the last cglb_set_hypers chose from the data's per-column range and the lengthscales
  * (CGLB_ERR_STATE before one) - 1 if the pair kernels run their range-clamped instances (kernel values below 2^-1000 come out as that floor,
  * not 0), 0 for the unclamped ones | the positivity bias of the Matern squared distance in hot units^2 (0 for RBF; above 2e-8 the clamped
@@ -529,6 +535,9 @@ int cglb_get_stat(cglb_ctx* ctx, const char* name, double* value);
  * "wide_grad_sym" (tiled K_ff gradient pass of wide inputs: 1, default - tiles on and right of the diagonal only; 0 - every tile) |
  * "wide_reg" (inputs of 33 ... 96 dimensions, fp64: 1, default - the symmetric K_ff mat-vec and the K_ff gradient pass stay register-resident,
  *  column operands handed out by v_fmac_f64 row_newbcast; 0 - both go through the Gram tiles like every other product of a wide input) |
+ * "grad_multi_mid" (inputs of 33 ... 96 dimensions, fp64, "wide_reg" 1: 1, default - the multi-pair gradient pass evaluates every kernel value
+ *  once per group of up to 8 vector pairs; 0 - one single pass per pair and one product for the kappa sums, what every other wide context runs;
+ *  for A/B timing and tests; a single pair takes the single pass either way) |
  * "drop_weighted_operand" (any value: forget the pre-weighted copy cglb_vec_update_p_seg made of its p - for callers that modify p before the next mat-vec) |
  * "logdet_bound" (the log-det term of the bound; cglb_logdet, cglb_objective_and_grad and its gradient follow it.  e = y - mu, s = noise,
  *  f = variance, A = L^-1 K_uf / sqrt(s), B = I + A A^T = LB LB^T, C = LB^-1 A, t = N f / s - tr A A^T:

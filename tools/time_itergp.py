@@ -8,7 +8,15 @@ a warm-up round).  Then
 one evaluation of cglb_itergp_objective_and_grad (t = 10 probes, rank-100 preconditioner, cold start) split by the library's three phase
 statistics.  The instruction model (18 + 4 Dp + 2 S_pad per group of 8) / (S (17 + 2 Dp)) is printed next to every measured ratio.
 
-    python tools/time_itergp.py [--n 20000 100000] [--d 8] [--reps 5] [--rounds 5] [--pairs 1 2 4 8 11] [--out profiles/itergp_timing.json]"""
+    python tools/time_itergp.py [--n 20000 100000] [--d 8] [--reps 5] [--rounds 5] [--pairs 1 2 4 8 11] [--out profiles/itergp_timing.json]
+
+--ab-grad-multi-mid: inputs of 33 - 96 dimensions (profiles/grad_multi_mid_timing.json).  Per `--dims` D and kind, on ONE context with lengthscales
+~ sqrt(D) (unclamped exponent range), cglb_time_grad_kff_multi for every S of `--pairs` with the option "grad_multi_mid" 1 (the shared-weight pass
+of kernels_grad_multi_mid.hip) and 0 (S single passes and one product), in alternating rounds after a warm-up round of each, so that a drift of
+the clocks hits both.  The instruction model next to every ratio: a pass of a group costs (2 Dh + 38) / 2 + S_pad + 5 lane-instructions per pair
+and lane at two lanes per row, a single pass (2 Dh + 38) / 2.
+
+    python tools/time_itergp.py --ab-grad-multi-mid [--n 50000] [--dims 40 64 77 90] --pairs 1 2 3 4 8 11 [--out profiles/grad_multi_mid_timing.json]"""
 import argparse
 import json
 import os
@@ -17,6 +25,7 @@ import sys
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
+import numpy as np
 import torch
 
 from cglb_amd.data import synthetic_problem, trained_like_hypers
@@ -40,17 +49,83 @@ def model_ratio(S, dp):
     return cost / (S * (15.0 + 2 * dp + 2))
 
 
+def alternating(fa, fb, rounds):
+    """Two timed calls in alternating rounds, after one warm-up round of each."""
+    fa(), fb()
+    ta, tb = [], []
+    for _ in range(rounds):
+        ta.append(fa())
+        tb.append(fb())
+    return [dict(median=statistics.median(t), min=min(t), max=max(t)) for t in (ta, tb)]
+
+
+def mid_model_ratio(S, dh):
+    """Lane-instructions per pair of the grouped mid-width pass (groups of up to 8 padded to 4 or 8, a single left-over pair through the single
+    pass) over those of S single passes."""
+    single, cost, rest = (2 * dh + 38) / 2.0, 0.0, S
+    while rest > 0:
+        g = min(8, rest)
+        cost += single if g == 1 else single + (4 if g <= 4 else 8) + 5
+        rest -= g
+    return cost / (S * single)
+
+
+def ab_grad_multi_mid(a):
+    out = dict(N=a.n[0], dtype="fp64", reps=a.reps, rounds=a.rounds, device=torch.cuda.get_device_name(0), option="grad_multi_mid", shapes=[])
+    n = a.n[0]
+    for D in a.dims:
+        X, y, Z = synthetic_problem(n, D, a.prec_size, seed=0)
+        ls = np.random.default_rng(D).uniform(0.8, 1.6, size=D) * np.sqrt(D)
+        for kind in ("rbf", "matern32"):
+            ctx = HipContext(X, y, a.prec_size, kind)
+            ctx.set_hypers(ls, 1.0, 0.05, 0.0, Z)
+            Dh = mid_width(D)
+            rec = dict(D=D, Dh=Dh, kind=kind, exp_clamp=ctx.get_stat("exp_clamp"), grad_multi_native=ctx.get_stat("grad_multi_native"),
+                       matmat_native=ctx.get_stat("matmat_native"), pairs={})
+
+            def timed(opt, S):
+                ctx.set_option("grad_multi_mid", opt)
+                return ctx.time_grad_kff_multi(S, a.reps)
+
+            for S in a.pairs:
+                on, off = alternating(lambda: timed(1, S), lambda: timed(0, S), a.rounds)
+                ratio = on["median"] / off["median"]
+                rec["pairs"][str(S)] = dict(native_ms=on, fallback_ms=off, ratio=ratio, model=mid_model_ratio(S, Dh))
+                print(f"D={D} {kind} S={S}: native {on['median']:.3f} ms ({on['min']:.3f}..{on['max']:.3f}), single passes {off['median']:.3f} ms "
+                      f"({off['min']:.3f}..{off['max']:.3f}), ratio {ratio:.3f} (model of the pair kernels alone {rec['pairs'][str(S)]['model']:.3f})", flush=True)
+            ctx.set_option("grad_multi_mid", 1)
+            out["shapes"].append(rec)
+            ctx.close()
+    path = a.out or os.path.join("profiles", "grad_multi_mid_timing.json")
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    with open(path, "w") as f:
+        json.dump(out, f, indent=1)
+    print("wrote", path)
+
+
+def mid_width(D):
+    """Padded width of the hot operand set of a mid-width fp64 context (0: none)."""
+    return 0 if D <= 32 or D > 96 else 48 if D <= 48 else 64 if D <= 64 else 80 if D <= 80 else 96
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--n", type=int, nargs="+", default=[20000, 100000])
+    ap.add_argument("--ab-grad-multi-mid", action="store_true", help="time every S with the option grad_multi_mid 1 and 0 on one context (module docstring)")
+    ap.add_argument("--dims", type=int, nargs="+", default=[40, 64, 77, 90], help="--ab-grad-multi-mid: input dimensions")
+    ap.add_argument("--n", type=int, nargs="+", default=None, help="default 20000 100000, with --ab-grad-multi-mid 50000")
     ap.add_argument("--d", type=int, default=8)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--pairs", type=int, nargs="+", default=[1, 2, 4, 8, 11])
     ap.add_argument("--probes", type=int, default=10)
     ap.add_argument("--prec-size", type=int, default=100)
-    ap.add_argument("--out", default=os.path.join("profiles", "itergp_timing.json"))
+    ap.add_argument("--out", default=None, help="default profiles/itergp_timing.json, with --ab-grad-multi-mid profiles/grad_multi_mid_timing.json")
     a = ap.parse_args()
+    if a.ab_grad_multi_mid:
+        a.n = a.n or [50000]
+        return ab_grad_multi_mid(a)
+    a.n = a.n or [20000, 100000]
+    a.out = a.out or os.path.join("profiles", "itergp_timing.json")
     hyp = trained_like_hypers(a.d)
     out = dict(D=a.d, dtype="fp64", reps=a.reps, rounds=a.rounds, device=torch.cuda.get_device_name(0), sizes={})
     for n in a.n:
@@ -60,7 +135,8 @@ def main():
             ctx = HipContext(X, y, a.prec_size, kind)
             ctx.set_hypers(hyp["lengthscales"], hyp["variance"], hyp["noise"], hyp["mean"], Z)
             ctx.setup()   # cglb_time_kernel(which=2) asks for the common terms
-            rec = dict(single_ms=rounds_of(lambda: ctx.time_kernel(2, a.reps), a.rounds), multi_ms={}, ratio_to_S_singles={}, model={})
+            rec = dict(Dh=mid_width(a.d), grad_multi_native=ctx.get_stat("grad_multi_native"), matmat_native=ctx.get_stat("matmat_native"),
+                       single_ms=rounds_of(lambda: ctx.time_kernel(2, a.reps), a.rounds), multi_ms={}, ratio_to_S_singles={}, model={})
             t1 = rec["single_ms"]["median"]
             gen = torch.Generator(device="cpu").manual_seed(0)
             for S in a.pairs:
