@@ -7,8 +7,8 @@
 //   dk/dl_d = var * h * delta_d^2 / l_d,  dk/dx1_d = -var * h * delta_d / l_d,
 //   delta_d = (x1_d - x2_d)/l_d,  h = kappa (RBF) | 3 exp(-sqrt3 r) (Matern-3/2) | 5/3 (1 + sqrt5 r) exp(-sqrt5 r) (Matern-5/2).
 // Operands are the scaled ones of K1 (xs = (x-c)/l*kscale); the 1/(l_d kscale^2) factors are applied
-// in the finalize kernels.
-#include "pair_common.h"
+// in the finish kernels (grad_pass.h: grad_finish_kernel; grad_panel_finalize_kernel below).  Column split, slabs and finish of the N^2 pass: grad_pass.h.
+#include "grad_pass.h"
 
 // ---- N^2 pass ---------------------------------------------------------------------------------------
 // Thread owns R rows; the column operand (xs_j, v_j, u_j) is wave-uniform (scalar loads).
@@ -187,10 +187,8 @@ __global__ __launch_bounds__(256, (DP == CGLB_GRAM_W3_DP ? 3 : 1)) void grad_kff
         ui[k] = row < n ? hscale * u[row0 + rr] : T(0);
         vi[k] = row < n ? hscale * v[row0 + rr] : T(0);
     }
-    int64_t j0 = (int64_t)blockIdx.y * jchunk;
-    const int64_t j1 = (j0 + jchunk < n) ? j0 + jchunk : n;
-    const int64_t sym_from = rblock + 256 * R;
-    if (j0 < rblock) j0 = rblock;
+    int64_t j0, j1, sym_from;
+    grad_pass_chunk(jchunk, n, rblock, 256 * R, j0, j1, sym_from);
     for (int64_t jb = j0; jb < j1; jb += 8) {
         T t[8];  // per column of the batch: the sum of this lane's R pair weights
 #pragma unroll
@@ -285,21 +283,6 @@ int launch_hot_squares(cglb_ctx* c) {
     return CGLB_OK;
 }
 
-// out[d] += scale[d] * sum_b part[b*DP + d]   (one block per d)
-__global__ __launch_bounds__(256) void grad_dl_finalize_kernel(const double* __restrict__ part, int64_t nblk, int DP, int D,
-                                                               ScaleParams sp, double var, double* __restrict__ out, int accumulate) {
-    __shared__ double smem[16];
-    const int d = blockIdx.x;
-    if (d >= D) return;
-    double s = 0.0;
-    for (int64_t b = threadIdx.x; b < nblk; b += blockDim.x) s += part[b * DP + d];
-    s = block_sum(s, smem);
-    if (threadIdx.x == 0) {
-        const double val = s * var * sp.scale[d];  // sp.scale holds 1/(l_d kscale^2) here
-        out[d] = accumulate ? out[d] + val : val;
-    }
-}
-
 // rows per lane of the Gram-form kernel when D <= 8 (4 rows - 204 VGPRs, 2 waves per SIMD - measured 6.28 ms against 5.55 ms)
 #ifndef CGLB_GRAM_R2_MAX_DP
 #define CGLB_GRAM_R2_MAX_DP 12  // widest padded row with CGLB_GRAM_ROWS rows per lane in the Gram-form kernel (DP = 12: 8.4 -> 7.2 ms at N = 100k against 1 row)
@@ -339,12 +322,6 @@ int grad_fold_operands(cglb_ctx* c, const void* v_full, const void* u, int64_t o
 int launch_grad_kff(cglb_ctx* c, const void* v_full, const void* u_local, double* out_dl) {
     if (is_wide(c) && mid_reg(c) && c->nloc == c->N) return launch_grad_kff_mid(c, v_full, u_local, 1, 0, out_dl);
     if (is_wide(c)) return wide_grad_kff(c, v_full, u_local, c->r0, c->nloc, 1, 0, out_dl);
-    ScaleParams sp;
-    const double ks = kscale_of(c) * cglb_hot_scale(c);  // the N^2 pass runs on the hot operand set
-    for (int d = 0; d < CGLB_MAX_D_NARROW; ++d) {
-        sp.center[d] = 0;
-        sp.scale[d] = d < c->D ? 1.0 / (c->ls[d] * ks * ks) : 0.0;
-    }
     if (c->nloc == 0) {
         HIP_CHECK(c, hipMemsetAsync(out_dl, 0, sizeof(double) * c->D, c->stream));
         return CGLB_OK;
@@ -364,13 +341,7 @@ int launch_grad_kff(cglb_ctx* c, const void* v_full, const void* u_local, double
         if (r.ncols <= 0) continue;
         const int rr = (r.sym && use_gram) ? Rg : R;
         const int64_t bx = (c->nloc + 256 * rr - 1) / (256 * rr);
-        int64_t js = (8192 + bx - 1) / bx;
-        if (r.sym) js *= 2;  // about half of the (row block, chunk) cells of the square are left of the diagonal and exit at once
-        if (js > 1024) js = 1024;
-        if (js > (r.ncols + 63) / 64) js = (r.ncols + 63) / 64;
-        if (js < 1) js = 1;
-        r.jchunk = (r.ncols + js - 1) / js;
-        r.jsplit = (r.ncols + r.jchunk - 1) / r.jchunk;
+        grad_pass_split(bx, r.ncols, r.sym, &r.jsplit, &r.jchunk);
         nblk += bx * r.jsplit;
     }
     CGLB_TRY(c->mem.reserve(c, &c->gpart, &c->gpart_cap, (size_t)nblk * c->Dp * sizeof(double)));
@@ -401,10 +372,7 @@ int launch_grad_kff(cglb_ctx* c, const void* v_full, const void* u_local, double
         CGLB_LAUNCH_CHECK(c);
         blk0 += bx * r.jsplit;
     }
-    hipLaunchKernelGGL(grad_dl_finalize_kernel, dim3(c->D), dim3(256), 0, c->stream, (const double*)c->gpart, nblk, c->Dp, c->D, sp,
-                       c->var, out_dl, 0);
-    CGLB_LAUNCH_CHECK(c);
-    return CGLB_OK;
+    return grad_finish(c, nblk, c->Dp, 0, grad_scale_params(c), c->var, 1.0, out_dl, 0);  // (s var) scale_d
 }
 
 // Cyclic form for the multi-GPU path: the whole N x N form in its symmetric version, row blocks rb == par_rank (mod par_world).
@@ -412,28 +380,18 @@ int launch_grad_kff(cglb_ctx* c, const void* v_full, const void* u_local, double
 int launch_grad_kff_cyclic(cglb_ctx* c, const void* v_full, const void* u_full, double* out_dl) {
     if (is_wide(c) && mid_reg(c)) return launch_grad_kff_mid(c, v_full, u_full, c->par_world, c->par_rank, out_dl);
     if (is_wide(c)) return wide_grad_kff(c, v_full, u_full, 0, c->N, c->par_world, c->par_rank, out_dl);
-    ScaleParams sp;
-    const double ks = kscale_of(c) * cglb_hot_scale(c);
-    for (int d = 0; d < CGLB_MAX_D_NARROW; ++d) {
-        sp.center[d] = 0;
-        sp.scale[d] = d < c->D ? 1.0 / (c->ls[d] * ks * ks) : 0.0;
-    }
     const bool use_gram = c->grad_gram && c->dtype == CGLB_F64;
     bool fold = false;
     if (use_gram) CGLB_TRY(grad_fold_operands(c, v_full, u_full, 0, c->N, &fold));
     const int R = use_gram ? CGLB_GRAM_ROWS_OF(c->Dp) : ((c->Dp <= 8 || (c->dtype == CGLB_F32 && c->Dp <= 16)) ? 2 : 1);
     const int64_t nb = (c->N + 256 * R - 1) / (256 * R);
-    const int64_t bx = c->par_rank < nb ? (nb - c->par_rank + c->par_world - 1) / c->par_world : 0;
+    const int64_t bx = grad_pass_dealt_blocks(nb, c->par_world, c->par_rank);
     if (bx == 0) {
         HIP_CHECK(c, hipMemsetAsync(out_dl, 0, sizeof(double) * c->D, c->stream));
         return CGLB_OK;
     }
-    int64_t js = 2 * ((8192 + bx - 1) / bx);
-    if (js > 1024) js = 1024;
-    if (js > (c->N + 63) / 64) js = (c->N + 63) / 64;
-    if (js < 1) js = 1;
-    const int64_t jchunk = (c->N + js - 1) / js;
-    const int64_t jsplit = (c->N + jchunk - 1) / jchunk;
+    int64_t jsplit, jchunk;
+    grad_pass_split(bx, c->N, true, &jsplit, &jchunk);
     const int64_t nblk = bx * jsplit;
     CGLB_TRY(c->mem.reserve(c, &c->gpart, &c->gpart_cap, (size_t)nblk * c->Dp * sizeof(double)));
     dim3 grid((unsigned)bx, (unsigned)jsplit);
@@ -453,10 +411,7 @@ int launch_grad_kff_cyclic(cglb_ctx* c, const void* v_full, const void* u_full, 
 #undef GGC_LAUNCH1
 #undef GKC_LAUNCH
     CGLB_LAUNCH_CHECK(c);
-    hipLaunchKernelGGL(grad_dl_finalize_kernel, dim3(c->D), dim3(256), 0, c->stream, (const double*)c->gpart, nblk, c->Dp, c->D, sp,
-                       c->var, out_dl, 0);
-    CGLB_LAUNCH_CHECK(c);
-    return CGLB_OK;
+    return grad_finish(c, nblk, c->Dp, 0, grad_scale_params(c), c->var, 1.0, out_dl, 0);  // (s var) scale_d
 }
 
 // ---- M x ncols pass over an adjoint panel --------------------------------------------------------------

@@ -1,6 +1,6 @@
 // K5, mid widths (32 < D <= 96, fp64): the symmetric Gram-form N^2 pass of kernels_grad.hip with a matrix row shared by two (four) lanes
 // and the column operands broadcast across lanes.  A translation unit of its own: its instances build in parallel with the narrow ones.
-#include "pair_common.h"
+#include "grad_pass.h"
 
 // Mid-width form of the symmetric Gram-form pass (32 < D <= 96, fp64; cglb_internal.h: mid_dim).  A row's operand and its first moments
 // no longer fit one lane (4 DP registers), so a matrix row is shared by SPLIT lanes (lane l of each half of the wave, SPLIT = 2; of each
@@ -18,8 +18,8 @@ __global__ __launch_bounds__(256, 2) void grad_kff_mid_kernel(const double* __re
                                                               int64_t n, int64_t jchunk, int rb_stride, int rb_offset, double* __restrict__ part,
                                                               const double* __restrict__ exp_tab, double bias) {
     using T = double;
-    constexpr int HD = DP / SPLIT, CH = 8, NCH = HD / CH, NQ = (DP + 7) / 8, WROWS = 64 / SPLIT;
-    static_assert((SPLIT == 2 || SPLIT == 4) && HD % CH == 0, "part width must be a multiple of 8");
+    using G = GradMidDims<DP, SPLIT>;
+    constexpr int HD = G::HD, CH = G::CH, NCH = G::NCH, NQ = G::NQ, WROWS = G::WROWS;
     constexpr bool FOLD = pair_fold<KIND, CLAMP>(), BIASED = pair_biased<T, KIND, CLAMP, PREC>();
     __shared__ double smem[16];
     __shared__ double tab[CGLB_TAB_SIZE];
@@ -36,11 +36,7 @@ __global__ __launch_bounds__(256, 2) void grad_kff_mid_kernel(const double* __re
     const int64_t row = rblock + (threadIdx.x >> 6) * WROWS + (lane & (WROWS - 1));
     const int64_t rr = row < n ? row : n - 1;
     T xi[HD], S1[HD], G2[G2LDS ? 1 : NQ];
-#pragma unroll
-    for (int d = 0; d < HD; ++d) {
-        xi[d] = Xh[rr * DP + prt * HD + d];
-        S1[d] = 0;
-    }
+    grad_mid_row_load<DP>(Xh, rr, prt, xi, S1);
 #pragma unroll
     for (int q = 0; q < NQ; ++q) {
         if constexpr (G2LDS) g2[q * 64] = 0;
@@ -48,15 +44,14 @@ __global__ __launch_bounds__(256, 2) void grad_kff_mid_kernel(const double* __re
     }
     T S0 = 0;
     const T a = ah[rr];
-    // pair_row_seed of pair_common.h, written out (calling it here reschedules every instance); the seed enters the sum of the parts once
+    // pair_row_seed of pair_common.h, written out (calling it here reschedules every instance); the seed enters the sum of the parts once.  The
+    // chains, the moments, the second-moment step and the final sums below are written out for the same reason (grad_pass.h lists what was tried)
     const T aseed = prt ? T(0) : ((KIND == CGLB_RBF) ? a : (BIASED ? T(-0.5) * (a + bias) : T(-0.5) * a));
     const T hscale = hfac_scale<T, KIND>();
     const T ui = row < n ? hscale * u[rr] : T(0);
     const T vi = row < n ? hscale * v[rr] : T(0);
-    int64_t j0 = (int64_t)blockIdx.y * jchunk;
-    const int64_t j1 = (j0 + jchunk < n) ? j0 + jchunk : n;
-    const int64_t sym_from = rblock + 4 * WROWS;
-    if (j0 < rblock) j0 = rblock;
+    int64_t j0, j1, sym_from;
+    grad_pass_chunk(jchunk, n, rblock, 4 * WROWS, j0, j1, sym_from);
     const T* __restrict__ xcol = Xh + prt * HD + l8;   // + j * DP + 8 s: this lane's element of slice s of column j
     T xsl[NCH];
     if (j0 < j1) {
@@ -120,53 +115,24 @@ __global__ __launch_bounds__(256, 2) void grad_kff_mid_kernel(const double* __re
     }
 }
 
-// out[d] = var * scale_d / hot^2 * sum_b part[b * DP + d], scale_d = 1 / (l_d kscale^2) from the device copy (kernels_wide.hip: upload_scales)
-__global__ __launch_bounds__(256) void grad_dl_finalize_mid_kernel(const double* __restrict__ part, int64_t nblk, int DP, int D, const double* __restrict__ scale,
-                                                                   double inv_hot2, double var, double* __restrict__ out) {
-    __shared__ double smem[16];
-    const int d = blockIdx.x;
-    if (d >= D) return;
-    double s = 0.0;
-    for (int64_t b = threadIdx.x; b < nblk; b += blockDim.x) s += part[b * DP + d];
-    s = block_sum(s, smem);
-    if (threadIdx.x == 0) out[d] = s * var * scale[d] * inv_hot2;
-}
-
-
-// Lanes sharing a matrix row at padded width 96: 2 with the second moments in LDS (16.8 ms at N = 50k; 24.7 with 4).  The Matern-3/2
-// instance of the exact level (two-step square root) does not fit 256 registers that way (101 spilled: 41 ms) and keeps 4 (25.5 ms); the
-// Matern-5/2 instance has the same root and one more live constant, so the rule is "any Matern kind".
-static inline int grad_mid_split(const cglb_ctx* c) {
-    if (c->Dh != 96) return 2;
-    return (c->kind != CGLB_RBF && c->precision == CGLB_PREC_EXACT) ? 4 : 2;
-}
 // Mid-width contexts: the whole symmetric form register-resident (rb_stride / rb_offset: the cyclic deal of the 128-row blocks)
 int launch_grad_kff_mid(cglb_ctx* c, const void* v_full, const void* u_full, int world, int rank, double* out_dl) {
     bool fold = false;
     CGLB_TRY(grad_fold_operands(c, v_full, u_full, 0, c->N, &fold));
     const int split = grad_mid_split(c);
-    const int brows = 256 / split;   // rows of a workgroup
-    const int64_t nb = (c->N + brows - 1) / brows;
-    const int64_t bx = rank < nb ? (nb - rank + world - 1) / world : 0;
-    if (bx == 0) {
+    GradMidGeom gm;
+    CGLB_TRY(grad_mid_geometry(c, split, world, rank, c->Dh, &gm));
+    if (gm.bx == 0) {
         HIP_CHECK(c, hipMemsetAsync(out_dl, 0, sizeof(double) * c->D, c->stream));
         return CGLB_OK;
     }
-    int64_t js = 2 * ((8192 + bx - 1) / bx);
-    if (js > 1024) js = 1024;
-    if (js > (c->N + 63) / 64) js = (c->N + 63) / 64;
-    if (js < 1) js = 1;
-    const int64_t jchunk = (c->N + js - 1) / js;
-    const int64_t jsplit = (c->N + jchunk - 1) / jchunk;
-    const int64_t nblk = bx * jsplit;
-    CGLB_TRY(c->mem.reserve(c, &c->gpart, &c->gpart_cap, (size_t)nblk * c->Dh * sizeof(double)));
-    dim3 grid((unsigned)bx, (unsigned)jsplit);
+    dim3 grid((unsigned)gm.bx, (unsigned)gm.jsplit);
     const bool lowprec = c->precision != CGLB_PREC_EXACT;   // level 2 runs as level 1 here
 #define GM_LAUNCH1(DPV, PR, CL) do { if (DPV == 96 && split == 4) { GM_LAUNCH0(DPV, PR, CL, (DPV == 96 ? 4 : 2)); } else { GM_LAUNCH0(DPV, PR, CL, 2); } } while (0)
 #define GM_LAUNCH0(DPV, PR, CL, SP)                                                                                                                    \
     hipLaunchKernelGGL((grad_kff_mid_kernel<KIND, DPV, PR, CL, SP>), grid, dim3(256), 0, c->stream, (const double*)c->Xh, (const double*)c->xah,         \
                        (const double*)u_full, (const double*)v_full, (CL || !fold) ? (const double*)u_full : (const double*)c->uwh,                    \
-                       (CL || !fold) ? (const double*)v_full : (const double*)c->pwh, c->N, jchunk, world, rank, c->gpart, (const double*)c->exp_tab, \
+                       (CL || !fold) ? (const double*)v_full : (const double*)c->pwh, c->N, gm.jchunk, world, rank, c->gpart, (const double*)c->exp_tab, \
                        c->m32_bias)
 #define GM_LAUNCH(DPV) do { if (c->exp_clamp) { if (lowprec) GM_LAUNCH1(DPV, CGLB_PREC_FAST, true); else GM_LAUNCH1(DPV, CGLB_PREC_EXACT, true); }     \
                             else { if (lowprec) GM_LAUNCH1(DPV, CGLB_PREC_FAST, false); else GM_LAUNCH1(DPV, CGLB_PREC_EXACT, false); } } while (0)
@@ -184,9 +150,6 @@ int launch_grad_kff_mid(cglb_ctx* c, const void* v_full, const void* u_full, int
 #undef GM_LAUNCH0
     CGLB_LAUNCH_CHECK(c);
     const double hot = cglb_hot_scale(c);
-    hipLaunchKernelGGL(grad_dl_finalize_mid_kernel, dim3(c->D), dim3(256), 0, c->stream, (const double*)c->gpart, nblk, c->Dh, c->D, (const double*)c->wsmall,
-                       1.0 / (hot * hot), c->var, out_dl);
-    CGLB_LAUNCH_CHECK(c);
-    return CGLB_OK;
+    // ((s var) scale_d) / hot^2, scale_d from the device copy
+    return grad_finish(c, gm.nblk, c->Dh, 0, (const double*)c->wsmall, c->var, 1.0 / (hot * hot), out_dl, 0);
 }
-

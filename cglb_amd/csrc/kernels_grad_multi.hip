@@ -5,34 +5,23 @@
 // The decomposition and the direct differences are those of grad_kff_kernel<..., SYM = true> (kernels_grad.hip): a lane owns R rows (x_i, the
 // row-side values u_bi, v_bi and the R x (DP + 1) accumulators live in VGPRs) and streams the columns at or right of its row block; x_j and
 // the column-side values are wave-uniform scalar loads.  The column side is interleaved to UVi[N][2 S_pad] = (u_0j .. u_{S_pad-1,j}, v_0j ..)
-// by a prep kernel (zero padded), so the operands of a column are ONE contiguous scalar load, as multi_operand_kernel does for the product.
+// by a prep kernel (grad_pass.h: grad_multi_operand_kernel, zero padded), so the operands of a column are ONE contiguous scalar load.
 //   diagonal block, columns [rblock, rblock + 256 R): visited in full, w_ij = sum_b u_bi v_bj                      (S_pad fmas)
 //   to its right:                                   visited once,  w_ij = sum_b (u_bi v_bj + u_bj v_bi)            (2 S_pad fmas)
 // then hv = h_ij w_ij, acc_d += hv (x_id - x_jd)^2 and the kappa sum, as in the single pass: about 18 + 4 DP + 2 S_pad vector-fp64
 // instructions per pair against S (18 + 4 DP + 2) for S single passes.
 // Partial sums go to slabs, part[(blockIdx.y * gridDim.x + blockIdx.x) * (DP + 1) + d], written by exactly one workgroup each and summed in
-// fixed order by the finalize kernel: no atomics, bitwise reproducible.  S > 8 runs in groups of 8 whose sums are added in group order.
+// fixed order by the finish kernel (grad_pass.h): no atomics, bitwise reproducible.  S > 8 runs in groups of 8 whose sums are added in group order.
 // The exponent runs through the range-clamped 2^x like the single direct-difference pass, so the clamped exponent range is native too.
 // Native scope: fp64, one rank, one shard covering all rows, at Dp <= 32 (the kernel of this file) and at 32 < D <= 96 with the register-resident
 // operand set (mid_reg; kernels_grad_multi_mid.hip, option "grad_multi_mid").  Elsewhere - fp32, D > 96, "wide_reg" 0, N ranks - S single
 // launch_grad_kff passes and the kappa sums from one product (launch_grad_kff_multi below).
-#include "pair_common.h"
+#include "grad_pass.h"
 
 // rows per lane: 2 up to padded width 8 and 1 beyond, as the single pass.  The row-resident doubles are R (2 DP + 2 S_pad): at most 64 (DP = 8,
 // S_pad = 8: 202 VGPRs, two waves per SIMD) with two rows and 80 (DP = 32, S_pad = 8: 256 VGPRs) with one; no instance spills.  Register use of
 // every instance: DESIGN.md section 4d.
 static constexpr int grad_multi_rows_per_lane(int dp) { return dp <= 8 ? 2 : 1; }
-
-// UVi[j][b] = U[b][j], UVi[j][sp + b] = V[b][j], zero for the padding pairs b >= s
-__global__ __launch_bounds__(256) void grad_multi_operand_kernel(const double* __restrict__ U, const double* __restrict__ V, int s, int sp, int64_t n,
-                                                                 double* __restrict__ UVi) {
-    const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= n * 2 * sp) return;
-    const int64_t j = idx / (2 * sp);
-    const int q = (int)(idx - j * 2 * sp);
-    const int b = q < sp ? q : q - sp;
-    UVi[idx] = b < s ? (q < sp ? U : V)[(int64_t)b * n + j] : 0.0;
-}
 
 // Columns [j0, j1) against the R rows of a lane.  FULL: both orientations of the pair weight (columns right of the diagonal block).
 template <int KIND, int DP, int R, int SP, int PREC, bool FULL>
@@ -115,6 +104,7 @@ __global__ __launch_bounds__(256) void grad_kff_multi_kernel(const double* __res
         }
         acck[k] = 0.0;
     }
+    // grad_pass_chunk of grad_pass.h, written out (calling it here moves two instructions of every instance)
     int64_t j0 = (int64_t)blockIdx.y * jchunk;
     const int64_t j1 = (j0 + jchunk < n) ? j0 + jchunk : n;
     const int64_t sym_from = rblock + 256 * R;
@@ -134,53 +124,21 @@ __global__ __launch_bounds__(256) void grad_kff_multi_kernel(const double* __res
     }
 }
 
-// out[d] (+)= scale_d * sum_blk part[blk][d], d < D the lengthscale entries, out[D] (+)= sum_blk part[blk][DP]; one block per entry
-__global__ __launch_bounds__(256) void grad_multi_finalize_kernel(const double* __restrict__ part, int64_t nblk, int DP, int D, ScaleParams sp, double var,
-                                                                  double* __restrict__ out, int accumulate) {
-    __shared__ double smem[16];
-    const int d = blockIdx.x;
-    if (d > D) return;
-    const int col = d < D ? d : DP;
-    double s = 0.0;
-    for (int64_t b = threadIdx.x; b < nblk; b += blockDim.x) s += part[b * (DP + 1) + col];
-    s = block_sum(s, smem);
-    if (threadIdx.x == 0) {
-        const double val = d < D ? s * var * sp.scale[d] : s;  // sp.scale holds 1 / (l_d kscale^2)
-        out[d] = accumulate ? out[d] + val : val;
-    }
-}
-
 template <int KIND, int DP, int SP>
 static int grad_multi_group(cglb_ctx* c, const double* U, const double* V, int s, double* out, int accumulate) {
     constexpr int R = grad_multi_rows_per_lane(DP);
     const int64_t n = c->N;
-    ScaleParams sp;
-    const double ks = cglb_kscale(c) * cglb_hot_scale(c);  // the pass runs on the hot operand set
-    for (int d = 0; d < CGLB_MAX_D_NARROW; ++d) {
-        sp.center[d] = 0;
-        sp.scale[d] = d < c->D ? 1.0 / (c->ls[d] * ks * ks) : 0.0;
-    }
-    // the grid rule of the single symmetric pass (launch_grad_kff)
     const int64_t bx = (n + 256 * R - 1) / (256 * R);
-    int64_t js = 2 * ((8192 + bx - 1) / bx);
-    if (js > 1024) js = 1024;
-    if (js > (n + 63) / 64) js = (n + 63) / 64;
-    if (js < 1) js = 1;
-    const int64_t jchunk = (n + js - 1) / js;
-    const int64_t jsplit = (n + jchunk - 1) / jchunk;
+    int64_t jsplit, jchunk;
+    grad_pass_split(bx, n, true, &jsplit, &jchunk);
     const int64_t nblk = bx * jsplit;
     CGLB_TRY(c->mem.reserve(c, &c->gpart, &c->gpart_cap, (size_t)nblk * (DP + 1) * sizeof(double)));
-    CGLB_TRY(c->mem.reserve(c, &c->gm_uv, &c->gm_uv_cap, (size_t)n * 16 * sizeof(double)));
-    hipLaunchKernelGGL(grad_multi_operand_kernel, dim3((unsigned)((n * 2 * SP + 255) / 256)), dim3(256), 0, c->stream, U, V, s, SP, n, (double*)c->gm_uv);
-    CGLB_LAUNCH_CHECK(c);
+    CGLB_TRY(grad_multi_operands(c, U, V, s, SP, nullptr));
     using T = double;
     CGLB_DISPATCH_PREC(c, hipLaunchKernelGGL((grad_kff_multi_kernel<KIND, DP, R, SP, PREC>), dim3((unsigned)bx, (unsigned)jsplit), dim3(256), 0, c->stream,
                                              (const double*)c->Xh, U, V, s, (const double*)c->gm_uv, n, jchunk, c->gpart, (const double*)c->exp_tab));
     CGLB_LAUNCH_CHECK(c);
-    hipLaunchKernelGGL(grad_multi_finalize_kernel, dim3(c->D + 1), dim3(256), 0, c->stream, (const double*)c->gpart, nblk, DP, c->D, sp, c->var, out,
-                       accumulate);
-    CGLB_LAUNCH_CHECK(c);
-    return CGLB_OK;
+    return grad_finish(c, nblk, DP, 1, grad_scale_params(c), c->var, 1.0, out, accumulate);  // (s var) scale_d
 }
 
 static bool grad_multi_mid_native(const cglb_ctx* c) { return mid_reg(c) && c->grad_multi_mid != 0 && grad_multi_mid_group(c->Dh) >= 2; }

@@ -10,24 +10,12 @@
 // dropped inside the diagonal block) - the operand path of the Gram chain.  sum_halves adds the two: SP + 5 lane-instructions per pair
 // against the 2 a single pass spends, and SP + 1 registers for the operands of both sides.  The folded column weight 2^(a_j / T) (RBF,
 // unclamped range) rides in UVi, as grad_fold_operands puts it into the column-side copies of the single pass; the constant of the gradient
-// profile (hfac_scale) is applied by the finalize kernel, so that the kappa sum needs no division.
+// profile (hfac_scale) is applied by the finish kernel, so that the kappa sum needs no division.
 // kappa: RBF kappa = h, the entry is the sum of S0 over the rows; the Matern kinds take P(r) from the root that is the exponent argument
 // (kappa = P(r) e, h = hscale L(r) e, e = 2^(-r / T)) and keep one more accumulator.
-// Slabs part[(by * gridDim.x + bx) * (DP + 1) + d], entry DP the kappa sum, one workgroup each, summed in fixed order by the finalize
+// Slabs part[(by * gridDim.x + bx) * (DP + 1) + d], entry DP the kappa sum, one workgroup each, summed in fixed order by the finish
 // kernel; groups are added in group order: no atomics, bitwise repeatable.  Registers of every instance: DESIGN.md section 4d.
-#include "pair_common.h"
-
-// UVi[j][b] = U[b][j] w_j, UVi[j][sp + b] = V[b][j] w_j (w = 1 without `wh`), zero for the padding pairs b >= s
-static __global__ __launch_bounds__(256) void grad_multi_mid_operand_kernel(const double* __restrict__ U, const double* __restrict__ V, int s, int sp, int64_t n,
-                                                                     const double* __restrict__ wh, double* __restrict__ UVi) {
-    const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= n * 2 * sp) return;
-    const int64_t j = idx / (2 * sp);
-    const int q = (int)(idx - j * 2 * sp);
-    const int b = q < sp ? q : q - sp;
-    const double x = b < s ? (q < sp ? U : V)[(int64_t)b * n + j] : 0.0;
-    UVi[idx] = wh ? x * wh[j] : x;
-}
+#include "grad_pass.h"
 
 template <int KIND, int DP, int PREC, bool CLAMP, int SPLIT, int SP>
 __global__ __launch_bounds__(256, 2) void grad_kff_multi_mid_kernel(const double* __restrict__ Xh, const double* __restrict__ ah, const double* __restrict__ U,
@@ -35,8 +23,8 @@ __global__ __launch_bounds__(256, 2) void grad_kff_multi_mid_kernel(const double
                                                                     int64_t jchunk, double* __restrict__ part, const double* __restrict__ exp_tab,
                                                                     double bias) {
     using T = double;
-    constexpr int HD = DP / SPLIT, CH = 8, NCH = HD / CH, NQ = (DP + 7) / 8, WROWS = 64 / SPLIT;
-    static_assert((SPLIT == 2 || SPLIT == 4) && HD % CH == 0, "part width must be a multiple of 8");
+    using G = GradMidDims<DP, SPLIT>;
+    constexpr int HD = G::HD, CH = G::CH, NCH = G::NCH, NQ = G::NQ, WROWS = G::WROWS;
     static_assert(SP == 2 || SP == 4 || SP == 8, "the column operands of a group fill at most half of a 16-lane row");
     constexpr bool FOLD = pair_fold<KIND, CLAMP>(), BIASED = pair_biased<T, KIND, CLAMP, PREC>(), MATERN = cglb_kind_matern<KIND>();
     __shared__ double smem[16];
@@ -55,11 +43,7 @@ __global__ __launch_bounds__(256, 2) void grad_kff_multi_mid_kernel(const double
     const int64_t row = rblock + (threadIdx.x >> 6) * WROWS + (lane & (WROWS - 1));
     const int64_t rr = row < n ? row : n - 1;
     T xi[HD], S1[HD], G2[G2LDS ? 1 : NQ], rw[SP];
-#pragma unroll
-    for (int d = 0; d < HD; ++d) {
-        xi[d] = Xh[rr * DP + prt * HD + d];
-        S1[d] = 0;
-    }
+    grad_mid_row_load<DP>(Xh, rr, prt, xi, S1);
 #pragma unroll
     for (int q = 0; q < NQ; ++q) {
         if constexpr (G2LDS) g2[q * 64] = 0;
@@ -69,11 +53,11 @@ __global__ __launch_bounds__(256, 2) void grad_kff_multi_mid_kernel(const double
     for (int b = 0; b < SP; ++b) rw[b] = (row < n && b < s) ? (role ? V : U)[(int64_t)b * n + rr] : T(0);  // padded rows and pairs carry zero weight
     T S0 = 0, acck = 0;
     const T a = ah[rr];
+    // from here on the text of grad_kff_mid_kernel but for the pair weight and the kappa sum, written out: as functions the shared steps move
+    // instances of this kernel (grad_pass.h lists what was tried)
     const T aseed = prt ? T(0) : ((KIND == CGLB_RBF) ? a : (BIASED ? T(-0.5) * (a + bias) : T(-0.5) * a));
-    int64_t j0 = (int64_t)blockIdx.y * jchunk;
-    const int64_t j1 = (j0 + jchunk < n) ? j0 + jchunk : n;
-    const int64_t sym_from = rblock + 4 * WROWS;
-    if (j0 < rblock) j0 = rblock;
+    int64_t j0, j1, sym_from;
+    grad_pass_chunk(jchunk, n, rblock, 4 * WROWS, j0, j1, sym_from);
     const T* __restrict__ xcol = Xh + prt * HD + l8;   // + j * DP + 8 s: this lane's element of slice s of column j
     const T* __restrict__ wcol = UVi + (role ? 0 : SP) + (lane & (SP - 1));   // + j * 2 SP: this lane's column-side value of column j
     T xsl[NCH], uvj = 0;
@@ -146,60 +130,28 @@ __global__ __launch_bounds__(256, 2) void grad_kff_multi_mid_kernel(const double
     if (threadIdx.x == 0) out[DP] = ks;
 }
 
-// out[d] (+)= hscale var scale_d / hot^2 sum_blk part[blk][d], d < D, out[D] (+)= sum_blk part[blk][DP]; scale_d = 1 / (l_d kscale^2) from the device copy
-static __global__ __launch_bounds__(256) void grad_multi_mid_finalize_kernel(const double* __restrict__ part, int64_t nblk, int DP, int D, const double* __restrict__ scale,
-                                                                      double fac, double* __restrict__ out, int accumulate) {
-    __shared__ double smem[16];
-    const int d = blockIdx.x;
-    if (d > D) return;
-    const int col = d < D ? d : DP;
-    double s = 0.0;
-    for (int64_t b = threadIdx.x; b < nblk; b += blockDim.x) s += part[b * (DP + 1) + col];
-    s = block_sum(s, smem);
-    if (threadIdx.x == 0) {
-        const double val = d < D ? s * fac * scale[d] : s;
-        out[d] = accumulate ? out[d] + val : val;
-    }
-}
-
 template <int KIND, int DP, int SP>
 static int grad_multi_mid_generic(cglb_ctx* c, const double* U, const double* V, int s, double* out, int accumulate) {
     static_assert(SP <= grad_multi_mid_group(DP), "an instance the register budget of this width does not hold");
     const int64_t n = c->N;
-    // Lanes sharing a matrix row: 2, and 4 at width 96, where every instance with 2 needs scratch (15 - 50 registers beyond 256 with the second
-    // moments in LDS); the single pass makes the same choice for its Matern instances of the exact level (kernels_grad_mid.hip: grad_mid_split)
-    constexpr int SPLIT = DP == 96 ? 4 : 2;
-    const int brows = 256 / SPLIT;
-    // the grid rule of the single pass (launch_grad_kff_mid), one rank
-    const int64_t bx = (n + brows - 1) / brows;
-    int64_t js = 2 * ((8192 + bx - 1) / bx);
-    if (js > 1024) js = 1024;
-    if (js > (n + 63) / 64) js = (n + 63) / 64;
-    if (js < 1) js = 1;
-    const int64_t jchunk = (n + js - 1) / js;
-    const int64_t jsplit = (n + jchunk - 1) / jchunk;
-    const int64_t nblk = bx * jsplit;
-    CGLB_TRY(c->mem.reserve(c, &c->gpart, &c->gpart_cap, (size_t)nblk * (DP + 1) * sizeof(double)));
-    CGLB_TRY(c->mem.reserve(c, &c->gm_uv, &c->gm_uv_cap, (size_t)n * 16 * sizeof(double)));
+    constexpr int SPLIT = grad_multi_mid_split(DP);
+    GradMidGeom gm;   // one rank: every row block
+    CGLB_TRY(grad_mid_geometry(c, SPLIT, 1, 0, DP + 1, &gm));
     const bool fold = KIND == CGLB_RBF && !c->exp_clamp;
-    hipLaunchKernelGGL(grad_multi_mid_operand_kernel, dim3((unsigned)((n * 2 * SP + 255) / 256)), dim3(256), 0, c->stream, U, V, s, SP, n,
-                       fold ? (const double*)c->wh : (const double*)nullptr, (double*)c->gm_uv);
-    CGLB_LAUNCH_CHECK(c);
-    dim3 grid((unsigned)bx, (unsigned)jsplit);
+    CGLB_TRY(grad_multi_operands(c, U, V, s, SP, fold ? (const double*)c->wh : (const double*)nullptr));
+    dim3 grid((unsigned)gm.bx, (unsigned)gm.jsplit);
     const bool lowprec = c->precision != CGLB_PREC_EXACT;   // level 2 runs as level 1 here, as in the single pass
 #define GMM_LAUNCH1(PR, CL)                                                                                                                              \
     hipLaunchKernelGGL((grad_kff_multi_mid_kernel<KIND, DP, PR, CL, SPLIT, SP>), grid, dim3(256), 0, c->stream, (const double*)c->Xh, (const double*)c->xah, U, V, \
-                       s, (const double*)c->gm_uv, n, jchunk, c->gpart, (const double*)c->exp_tab, c->m32_bias)
+                       s, (const double*)c->gm_uv, n, gm.jchunk, c->gpart, (const double*)c->exp_tab, c->m32_bias)
     if (c->exp_clamp) { if (lowprec) GMM_LAUNCH1(CGLB_PREC_FAST, true); else GMM_LAUNCH1(CGLB_PREC_EXACT, true); }
     else { if (lowprec) GMM_LAUNCH1(CGLB_PREC_FAST, false); else GMM_LAUNCH1(CGLB_PREC_EXACT, false); }
 #undef GMM_LAUNCH1
     CGLB_LAUNCH_CHECK(c);
     const double hot = cglb_hot_scale(c);
     const double hscale = KIND == CGLB_RBF ? 1.0 : (KIND == CGLB_MATERN32 ? 3.0 : 5.0 / 3.0);  // devmath.h: hfac_scale
-    hipLaunchKernelGGL(grad_multi_mid_finalize_kernel, dim3(c->D + 1), dim3(256), 0, c->stream, (const double*)c->gpart, nblk, DP, c->D, (const double*)c->wsmall,
-                       hscale * c->var / (hot * hot), out, accumulate);
-    CGLB_LAUNCH_CHECK(c);
-    return CGLB_OK;
+    // (s (hscale var / hot^2)) scale_d, scale_d from the device copy
+    return grad_finish(c, gm.nblk, DP, 1, (const double*)c->wsmall, hscale * c->var / (hot * hot), 1.0, out, accumulate);
 }
 
 // one group of 2 <= sg <= grad_multi_mid_group(Dh) pairs of a context with mid_reg(c)
