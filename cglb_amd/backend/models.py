@@ -772,13 +772,17 @@ class PredictGradIterGPR(nn.Module):
     """`PredictGradIterGPR(model)(xnew)` -> (mean [n, 1], dmean [n, d], var [n, 1], dvar [n, d]): predict_f of the iterative model and its
     gradients with respect to the new points (cglb_itergp_predict_grad).  The variances come from the Lanczos variance cache of rank `var_rank`
     (None: the model's `pred_var_rank`), built on demand as PredictIterGPR builds it; `dvar` is the exact gradient of that cache's variance
-    (an upper bound of the exact variance), not of the exact variance.  Rank 0: `var` and `dvar` are None."""
+    (an upper bound of the exact variance), not of the exact variance.  Rank 0: `var` and `dvar` are None.
+    Up to 32 input dimensions; `wide=True` sets the option "input_grad_mid" on the model's context, which opens 33 to 96 dimensions (fp64, the
+    register-resident mid-width path) - without it such a model is refused."""
 
-    def __init__(self, model: IterGPR, max_error: float = 1e-3, var_rank: Optional[int] = None):
+    def __init__(self, model: IterGPR, max_error: float = 1e-3, var_rank: Optional[int] = None, wide: bool = False):
         if not isinstance(model, IterGPR):
             raise ValueError(f"IterGPR model expected in the constructor of the {self.__class__}")
         super().__init__()
         object.__setattr__(self, "model", model)
+        if wide:
+            model.hip.set_option("input_grad_mid", 1)
         self.max_error = float(max_error)
         self.var_rank = int(model.pred_var_rank if var_rank is None else var_rank)
 
@@ -914,13 +918,16 @@ class PathsIterGPR(nn.Module):
     `paths.value_and_grad(x)` -> ([S, n, 1], [S, n, d]) with the gradients with respect to x.  When `x.requires_grad`, `paths(x)` is
     differentiable by autograd.  Frequencies, phases, weights and noise are drawn from `model.generator` in the order of
     SampleIterGPR.forward (fixed_features False): with the same seed the paths are the samples that class returns.  The paths belong to the
-    hyper-parameters and targets they were solved at: evaluating after either changed raises RuntimeError."""
+    hyper-parameters and targets they were solved at: evaluating after either changed raises RuntimeError.  Up to 32 input dimensions;
+    `wide=True` sets the option "input_grad_mid" on the model's context before the solve, which opens 33 to 96 dimensions (fp64)."""
 
-    def __init__(self, model: IterGPR, num_samples: int, num_features: int = 1024, max_error: float = 1e-3):
+    def __init__(self, model: IterGPR, num_samples: int, num_features: int = 1024, max_error: float = 1e-3, wide: bool = False):
         if not isinstance(model, IterGPR):
             raise ValueError(f"IterGPR model expected in the constructor of the {self.__class__}")
         super().__init__()
         object.__setattr__(self, "model", model)
+        if wide:
+            model.hip.set_option("input_grad_mid", 1)
         self.num_samples, self.num_features, self.max_error = int(num_samples), int(num_features), float(max_error)
         S = self.num_samples
         with torch.no_grad():

@@ -303,10 +303,35 @@ int sample_eval(cglb_ctx* c, const void* xnew, int64_t n_new, StagedPoints& pts,
     return CGLB_OK;
 }
 
-// the scope of the input-gradient entries: the class's own, up to 32 input dimensions
-int require_input_grad_ok(cglb_ctx* c) {
+// the width part of the scope of every input-gradient entry: up to 32 input dimensions, or a mid-width context (33 .. 96, wide_reg on) with the option
+// "input_grad_mid"
+static int require_input_grad_width(cglb_ctx* c) {
+    if (is_wide(c) && !input_grad_mid_on(c))
+        return cglb_fail(c, CGLB_ERR_BAD_ARG, "the input-gradient products have no wide path yet: they are available up to 32 input dimensions, and at 33 to 96 with the "
+                                              "option input_grad_mid 1 (fp64, wide_reg on)");
+    return CGLB_OK;
+}
+// cglb_cross_grad_matmat, its timer, cglb_itergp_predict_grad: the class's own scope and the cross product's width (kernels_input_grad.hip,
+// kernels_input_grad_mid.hip)
+int require_cross_grad_ok(cglb_ctx* c) {
     CGLB_TRY(require_itergp_ok(c));
-    if (is_wide(c)) return cglb_fail(c, CGLB_ERR_BAD_ARG, "the input-gradient products have no wide path yet: they are available up to 32 input dimensions");
+    return require_input_grad_width(c);
+}
+// cglb_feature_grad_matmat, its timer, cglb_itergp_paths_solve / _eval: the class's own scope (the value kernels of cglb_itergp_sample run at any width)
+// and the width of the two gradient products
+int require_feature_grad_ok(cglb_ctx* c) {
+    CGLB_TRY(require_itergp_ok(c));
+    return require_input_grad_width(c);
+}
+// the rows launch_cross_grad takes (input_grad_row_stride(c) doubles each): the hot-scaled set as staged; on a mid-width context under "input_grad_mid" the hot
+// set at width Dh, formed here from the staged raw rows (StagedPoints stages the plain scaled set alone on wide contexts)
+int input_grad_rows(cglb_ctx* c, StagedPoints& pts, const void** rows) {
+    if (input_grad_mid_on(c)) {
+        CGLB_TRY(pts.stage_hot_mid());
+        *rows = pts.xh;
+    } else {
+        *rows = pts.xs;
+    }
     return CGLB_OK;
 }
 
@@ -693,16 +718,18 @@ int cglb_itergp_sample(cglb_ctx* c, const void* xnew, int64_t n_new, const void*
 int cglb_cross_grad_matmat(cglb_ctx* c, const void* xnew, int64_t n_new, const void* V, int S, void* out, void* gout) {
     if (c) c->obj_valid = false;
     if (!c || !xnew || !V || !gout || n_new < 0 || S < 1) return c ? cglb_fail(c, CGLB_ERR_BAD_ARG, "bad argument") : CGLB_ERR_BAD_ARG;
-    CGLB_TRY(require_input_grad_ok(c));
-    return cross_product(c, xnew, n_new, V, S, [&](const StagedPoints& pts, int64_t ldv) {
-        return launch_cross_grad(c, pts.xs, n_new, (const double*)c->cm_vi, ldv, S, (double*)out, S, (double*)gout);
+    CGLB_TRY(require_cross_grad_ok(c));
+    return cross_product(c, xnew, n_new, V, S, [&](StagedPoints& pts, int64_t ldv) {
+        const void* rows = nullptr;
+        CGLB_TRY(input_grad_rows(c, pts, &rows));
+        return launch_cross_grad(c, rows, n_new, (const double*)c->cm_vi, ldv, S, (double*)out, S, (double*)gout);
     });
 }
 
 int cglb_time_cross_grad_matmat(cglb_ctx* c, int64_t n_new, int S, int reps, double* ms_avg) {
     if (c) c->obj_valid = false;
     if (!c || !ms_avg || reps <= 0 || S < 1 || n_new < 1) return c ? cglb_fail(c, CGLB_ERR_BAD_ARG, "bad argument") : CGLB_ERR_BAD_ARG;
-    CGLB_TRY(require_input_grad_ok(c));
+    CGLB_TRY(require_cross_grad_ok(c));
     if (n_new > c->N) return cglb_fail(c, CGLB_ERR_BAD_ARG, "the timed product takes its new points from the training rows: n_new <= n_total");
     HIP_CHECK(c, hipSetDevice(c->device));
     multi_work w;
@@ -726,7 +753,7 @@ int cglb_feature_grad_matmat(cglb_ctx* c, const void* x, int64_t n_rows, const v
                              void* gout) {
     if (c) c->obj_valid = false;
     if (!c || !omega || !phase || !W || !gout || n_rows < 0 || F < 1 || S < 1) return c ? cglb_fail(c, CGLB_ERR_BAD_ARG, "bad argument") : CGLB_ERR_BAD_ARG;
-    CGLB_TRY(require_input_grad_ok(c));
+    CGLB_TRY(require_feature_grad_ok(c));
     return feature_rows_product(c, x, n_rows, omega, phase, W, F, S,
                                 [&](const double* rows) { return launch_feature_grad(c, rows, n_rows, F, S, (double*)out, S, (double*)gout); });
 }
@@ -734,7 +761,7 @@ int cglb_feature_grad_matmat(cglb_ctx* c, const void* x, int64_t n_rows, const v
 int cglb_time_feature_grad_matmat(cglb_ctx* c, int64_t n_rows, int64_t F, int S, int reps, double* ms_avg) {
     if (c) c->obj_valid = false;
     if (!c || !ms_avg || reps <= 0 || S < 1 || F < 1 || n_rows < 1) return c ? cglb_fail(c, CGLB_ERR_BAD_ARG, "bad argument") : CGLB_ERR_BAD_ARG;
-    CGLB_TRY(require_input_grad_ok(c));
+    CGLB_TRY(require_feature_grad_ok(c));
     if (n_rows > c->N) return cglb_fail(c, CGLB_ERR_BAD_ARG, "the timed product takes its rows from the training rows: n_rows <= n_total");
     HIP_CHECK(c, hipSetDevice(c->device));
     void *om = nullptr, *ph = nullptr, *W = nullptr, *out = nullptr, *gout = nullptr;
@@ -755,7 +782,7 @@ int cglb_itergp_predict_grad(cglb_ctx* c, const void* xnew, int64_t n_new, doubl
     if (c) c->obj_valid = false;
     if (!c || !xnew || !f_mean || !g_mean || (!f_var) != (!g_var) || n_new < 0 || max_cg_iter < 0)
         return c ? cglb_fail(c, CGLB_ERR_BAD_ARG, "bad argument") : CGLB_ERR_BAD_ARG;
-    CGLB_TRY(require_input_grad_ok(c));
+    CGLB_TRY(require_cross_grad_ok(c));
     if (f_var && c->it_cache_rank < 1)
         return cglb_fail(c, CGLB_ERR_STATE, "cglb_itergp_var_cache must precede cglb_itergp_predict_cached at the current data and hyper-parameters");
     if (n_new == 0) return CGLB_OK;
@@ -773,15 +800,17 @@ int cglb_itergp_predict_grad(cglb_ctx* c, const void* xnew, int64_t n_new, doubl
     CGLB_TRY(pts.alloc(n_new, sizeof(double)));
     CGLB_TRY(itergp_predict_mean(c, xnew, n_new, pts, f_mean));  // the mean of both predictives, bitwise
     // g_mean = grad (K_*f alpha): the stored alpha as the single column of the gradient product
+    const void* rows = nullptr;
+    CGLB_TRY(input_grad_rows(c, pts, &rows));
     int64_t ldv = 0;
     CGLB_TRY(launch_cross_multi_operand(c, c->it_alpha, 1, &ldv));
-    CGLB_TRY(launch_cross_grad(c, pts.xs, n_new, (const double*)c->cm_vi, ldv, 1, nullptr, 1, (double*)g_mean));
+    CGLB_TRY(launch_cross_grad(c, rows, n_new, (const double*)c->cm_vi, ldv, 1, nullptr, 1, (double*)g_mean));
     if (!f_var) return CGLB_OK;
     // f_var as cglb_itergp_predict_cached forms it (B = K_*f R through the value kernel, bitwise), then g_var = -2 sum_s B G
     CGLB_TRY(itergp_cached_var(c, pts, n_new, r_pad, f_var));
     for (int64_t i0 = 0; i0 < n_new; i0 += rows_blk) {
         const int64_t nr = std::min(rows_blk, n_new - i0);
-        CGLB_TRY(launch_cross_grad(c, (const double*)pts.xs + i0 * c->Dp, nr, c->it_cache, c->it_cache_ld, r_pad, nullptr, r_pad, c->ig_gk));
+        CGLB_TRY(launch_cross_grad(c, (const double*)rows + i0 * input_grad_row_stride(c), nr, c->it_cache, c->it_cache_ld, r_pad, nullptr, r_pad, c->ig_gk));
         CGLB_TRY(launch_input_grad_var(c, c->it_blk + i0 * r_pad, r_pad, c->ig_gk, nr, r_pad, (double*)g_var + i0 * c->D));
     }
     return CGLB_OK;
@@ -792,7 +821,7 @@ int cglb_itergp_paths_solve(cglb_ctx* c, const void* omega, const void* phase, c
     if (c) c->obj_valid = false;
     if (!c || !omega || !phase || !W || !eps || !U_out || F < 1 || S < 1 || max_cg_iter < 0)
         return c ? cglb_fail(c, CGLB_ERR_BAD_ARG, "bad argument") : CGLB_ERR_BAD_ARG;
-    CGLB_TRY(require_input_grad_ok(c));
+    CGLB_TRY(require_feature_grad_ok(c));
     HIP_CHECK(c, hipSetDevice(c->device));
     multi_work w;
     CGLB_TRY(sample_reserve(c, S, 0, &w));
@@ -810,7 +839,7 @@ int cglb_itergp_paths_eval(cglb_ctx* c, const void* xnew, int64_t n_new, const v
     if (c) c->obj_valid = false;
     if (!c || !xnew || !omega || !phase || !W || !U || !f_out || n_new < 0 || F < 1 || S < 1)
         return c ? cglb_fail(c, CGLB_ERR_BAD_ARG, "bad argument") : CGLB_ERR_BAD_ARG;
-    CGLB_TRY(require_input_grad_ok(c));
+    CGLB_TRY(require_feature_grad_ok(c));
     if (n_new == 0) return CGLB_OK;
     HIP_CHECK(c, hipSetDevice(c->device));
     CGLB_TRY(c->mem.reserve(c, &c->ft_G, &c->ft_G_cap, (size_t)n_new * S * sizeof(double)));
@@ -828,7 +857,9 @@ int cglb_itergp_paths_eval(cglb_ctx* c, const void* xnew, int64_t n_new, const v
     CGLB_TRY(launch_feature_grad(c, (const double*)pts.xr, n_new, F, S, c->ft_G, S, c->ig_gf));
     int64_t ldv = 0;
     CGLB_TRY(launch_cross_multi_operand(c, U, S, &ldv));
-    CGLB_TRY(launch_cross_grad(c, pts.xs, n_new, (const double*)c->cm_vi, ldv, S, c->ft_KU, S, c->ig_gk));
+    const void* rows = nullptr;
+    CGLB_TRY(input_grad_rows(c, pts, &rows));
+    CGLB_TRY(launch_cross_grad(c, rows, n_new, (const double*)c->cm_vi, ldv, S, c->ft_KU, S, c->ig_gk));
     return launch_input_grad_paths(c, c->ft_G, c->ft_KU, c->ig_gf, c->ig_gk, n_new, S, (double*)f_out, (double*)g_out);
 }
 

@@ -215,6 +215,12 @@ int StagedPoints::stage(const void* xnew, bool hot) {
     return xs ? scale(hot) : CGLB_OK;
 }
 int StagedPoints::scale(bool hot) { return launch_prep_scaled(c, xr, n, xs, xa, hot); }
+int StagedPoints::stage_hot_mid() {
+    void* xah = nullptr;  // |xh|^2 term of the Gram form: written by the kernel, not read by the direct-difference product
+    if (!xh) CGLB_TRY(tmp.alloc(c, &xh, (size_t)n * c->Dh * esz));
+    CGLB_TRY(tmp.alloc(c, &xah, (size_t)n * esz));
+    return wide_prep_hot_rows(c, xr, n, xh, xah);
+}
 
 int read_scalars(cglb_ctx* c, const double* dev, double* host, int n) {
     HIP_CHECK(c, hipMemcpyAsync(host, dev, sizeof(double) * n, hipMemcpyDeviceToHost, c->stream));
@@ -1103,6 +1109,7 @@ int cglb_set_option(cglb_ctx* c, const char* name, int64_t value) {
     else if (!strcmp(name, "wide_grad_sym")) c->wide_grad_sym = (int)value;
     else if (!strcmp(name, "wide_reg")) { c->wide_reg = (int)value; c->pwh_src = nullptr; }
     else if (!strcmp(name, "grad_multi_mid")) c->grad_multi_mid = (int)value;
+    else if (!strcmp(name, "input_grad_mid")) c->input_grad_mid = value != 0;
     else if (!strcmp(name, "chol_mode")) c->chol_mode = (int)value;
     else if (!strcmp(name, "grad_trsm")) c->grad_trsm = (int)value;
     else if (!strcmp(name, "precond_mode")) {
@@ -1920,6 +1927,10 @@ int cglb_get_stat(cglb_ctx* c, const char* name, double* value) {
     }
     if (!strcmp(name, "matmat_native")) { *value = (c->have_data && kff_multi_native(c)) ? 1.0 : 0.0; return CGLB_OK; }  // shared-kernel instance or single mat-vecs
     if (!strcmp(name, "grad_multi_native")) { *value = (c->have_data && grad_multi_native(c)) ? 1.0 : 0.0; return CGLB_OK; }  // multi-pair gradient instance or single passes
+    if (!strcmp(name, "input_grad_native")) {  // the next input-gradient cross product runs a register-resident instance (narrow, or mid under "input_grad_mid") or is refused
+        *value = (c->dtype == CGLB_F64 && (!is_wide(c) || input_grad_mid_on(c))) ? 1.0 : 0.0;
+        return CGLB_OK;
+    }
     if (!strcmp(name, "exp_clamp") || !strcmp(name, "m32_bias")) {  // the exponent-range regime of the last cglb_set_hypers
         if (!c->have_hypers) return cglb_fail(c, CGLB_ERR_STATE, "set_hypers must precede this statistic");
         *value = !strcmp(name, "exp_clamp") ? (c->exp_clamp ? 1.0 : 0.0) : c->m32_bias;

@@ -74,6 +74,7 @@ struct cglb_ctx {
     int Dh = 0;        // 32 < D <= 96, fp64: padded width (48, 64, 80, 96) of the hot operand set Xh kept for the register-resident mat-vec
     int wide_grad_sym = 1;  // option "wide_grad_sym": 0 evaluates every tile of the tiled K_ff gradient pass (A/B)
     int wide_reg = 1;  // option "wide_reg": 0 sends that mat-vec through the Gram tiles of kernels_wide.hip as well (A/B, fallback)
+    int input_grad_mid = 0;  // option "input_grad_mid": 1 opens the value-and-gradient cross product of a mid-width context (kernels_input_grad_mid.hip); 0: refused
     int grad_multi_mid = 1;  // option "grad_multi_mid": 0 sends the multi-pair gradient pass of a mid-width context through single passes (A/B, fallback)
     size_t esz = 8;
     hipStream_t stream = nullptr;
@@ -333,6 +334,7 @@ struct StagedPoints {
     int64_t n = 0;
     size_t esz = 0;
     void *xr = nullptr, *xs = nullptr, *xa = nullptr;
+    void* xh = nullptr;  // mid-width contexts, after stage_hot_mid: the points in hot units at width Dh (xs is the plain scaled set there)
     DevTemps tmp;  // the further temporaries of the call
     explicit StagedPoints(cglb_ctx* cc) : c(cc) {}
     StagedPoints(const StagedPoints&) = delete;
@@ -340,6 +342,7 @@ struct StagedPoints {
     int alloc(int64_t n_points, size_t elem, bool scaled = true);  // n points of element size elem; not scaled: xr alone
     int stage(const void* xnew, bool hot = true);                  // xr <- xnew (host or device), then (xs, xa) in hot or plain units where allocated
     int scale(bool hot);                                           // (xs, xa) from xr once more, in the units asked for
+    int stage_hot_mid();                                           // xh [n][Dh] from the staged xr (wide_prep_hot_rows), allocated on first use
 };
 
 static inline int pad_dim(int d) {
@@ -357,12 +360,14 @@ static inline int mid_dim(int d, int dtype) {
     return d <= 48 ? 48 : d <= 64 ? 64 : d <= 80 ? 80 : 96;  // (a 128-wide row operand alone would fill the 256 VGPRs VALU instructions can address)
 }
 static inline bool mid_reg(const cglb_ctx* c) { return c->Dh > 0 && c->wide_reg != 0; }
+static inline bool input_grad_mid_on(const cglb_ctx* c) { return c->input_grad_mid != 0 && mid_reg(c); }  // the input-gradient cross product runs at this mid width
 
 // kernels_wide.hip: D > 32.  The Gram part of the pair value is a contraction with k = D and goes through rocBLAS in tiles; same
 // contracts as the launchers below they stand in for.
 int wide_prep_scaled(cglb_ctx* c, const void* Xraw, int64_t n, void* Xs_out, void* xa_out, void* Xsq_out);
 int wide_after_hypers(cglb_ctx* c);
 int wide_prep_hot(cglb_ctx* c);   // Xh (N x Dh, zero padded), xah in hot units for the register-resident mat-vec of a mid-width context
+int wide_prep_hot_rows(cglb_ctx* c, const void* Xraw, int64_t n, void* Xh_out, void* xah_out);  // the same for any n raw rows: Xh_out [n][Dh], xah_out [n]
 int wide_kuf(cglb_ctx* c);
 int wide_kuu(cglb_ctx* c);
 int wide_kpanel(cglb_ctx* c, const void* Zs, int M, const void* XsNew, int64_t n_new, int64_t ld, void* out);  // out[m * ld + n] = var K(z_m, xnew_n), any two scaled sets
@@ -451,6 +456,12 @@ int feature_rows_per_block(const cglb_ctx* c);      // rows per workgroup at the
 // fp64, Dp <= 32.  Bitwise repeatable.
 int launch_cross_grad(cglb_ctx* c, const void* XhRow, int64_t nrows, const double* Vi, int64_t ldv, int S, double* out, int64_t ldo, double* gout);
 int launch_feature_grad(cglb_ctx* c, const double* X, int64_t nrows, int64_t F, int S, double* out, int64_t ldo, double* gout);
+// kernels_input_grad_mid.hip: launch_cross_grad's and launch_feature_grad's contracts on a context with input_grad_mid_on(c) (fp64, 32 < D <= 96), where launch_cross_grad sends it:
+// XhRow [nrows][Dh] from wide_prep_hot_rows.  Bitwise repeatable.
+int launch_cross_grad_mid(cglb_ctx* c, const void* XhRow, int64_t nrows, const double* Vi, int64_t ldv, int S, double* out, int64_t ldo, double* gout);
+int launch_feature_grad_mid(cglb_ctx* c, const double* X, int64_t nrows, int64_t F, int S, double* out, int64_t ldo, double* gout);  // launch_feature_grad's contract there
+int input_grad_mid_rows_per_block(const cglb_ctx* c);   // new points per workgroup (64)
+int input_grad_mid_width(const cglb_ctx* c);            // columns per group at the context's hot width (4 or 2)
 int launch_input_grad_var(cglb_ctx* c, const double* B, int64_t ldb, const double* G, int64_t nrows, int sp, double* g_var);  // g_var[i][k] = -2 sum_s B[i][s] G[i][s][k]
 int launch_input_grad_paths(cglb_ctx* c, const double* Gf, const double* KU, const double* gf, const double* gk, int64_t n, int S, double* f, double* g);
 // kernels_predict_grad.hip: row-weighted value and input gradient of a cross product between two explicit hot-unit point sets (lengthscales ls, host):
@@ -463,6 +474,7 @@ int predict_grad_rows_per_block(const cglb_ctx* c);  // new points per workgroup
 int predict_grad_stat(cglb_ctx* c, const char* name, double* value);  // "predict_grad_kernel_ms"; -1: not this name
 int input_grad_rows_per_block(const cglb_ctx* c);   // new points per workgroup at the context's width
 int input_grad_width(const cglb_ctx* c);            // columns per group at the context's width (8, 4 or 2)
+static inline int64_t input_grad_row_stride(const cglb_ctx* c) { return input_grad_mid_on(c) ? c->Dh : c->Dp; }  // doubles per new point of launch_cross_grad's XhRow
 // kernels_vec.hip
 // dot, update_v_r, update_p: s columns of length n ([s][n], one launch each; per-column device scalars [s]); s = 1 is the one-column form.
 // A zero denominator gives a zero factor.

@@ -364,6 +364,13 @@ template <int K0, int N> struct BcastAxpy {    // acc[k] += bc[lane k] * x for k
         if constexpr (K0 + 1 < N) BcastAxpy<K0 + 1, N>::run(acc, bc, x);
     }
 };
+template <int K0, int N> struct BcastDiff {    // df[k] = x[k] - bc[lane k] for k < N: v_add_f64 has no DPP form, so x[k] + bc[lane k] * m1 with m1 = -1.0, rounded once like the subtraction
+    static __device__ __forceinline__ void run(double* df, double bc, const double* x, double m1) {
+        df[K0] = x[K0];
+        fmac_bcast<K0>(df[K0], bc, m1);
+        if constexpr (K0 + 1 < N) BcastDiff<K0 + 1, N>::run(df, bc, x, m1);
+    }
+};
 // sum of a value over the two 32-lane halves of the wave, returned to both (v_permlane32_swap, gfx950): with old == src the first result is
 // the lower half's value in every lane, the second the upper half's
 __device__ __forceinline__ double sum_halves(double g) {

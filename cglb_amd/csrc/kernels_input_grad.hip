@@ -21,10 +21,7 @@
 
 #define INPUT_GRAD_ROWS 4096            // new points per launch
 
-// rows per lane and columns per group by padded width, chosen so that R (DP + G (DP + 1)) + DP row-resident doubles stay near 100 (200 of the 256
-// VGPRs of two waves per SIMD): 2 x 8 up to width 4 (88 + 4), 1 x 8 up to 8 (80 + 8), 1 x 4 up to 16 (84 + 16), 1 x 2 beyond (98 + 32)
-static constexpr int input_grad_rows_per_lane(int dp) { return dp <= 4 ? 2 : 1; }
-static constexpr int input_grad_group_width(int dp) { return dp <= 8 ? 8 : (dp <= 16 ? 4 : 2); }
+// rows per lane and columns per group by padded width: input_grad_rows_per_lane, input_grad_group_width (row_slab.h)
 
 // grid (row blocks of 256 R new points, column chunks of jchunk training points); Vi points at the first column of the group
 template <int KIND, int DP, int R, int G, int PREC>
@@ -183,7 +180,9 @@ static int cross_grad_group(cglb_ctx* c, const double* XhRow, int64_t nrows, con
 
 // out[i * ldo + s] (out may be NULL) and gout[(i * S + s) * D + k], s < S <= ldv, from Vi: dev [N][ldv] row-major, ldv a multiple of 8, the columns
 // S .. ldv - 1 readable.  XhRow: hot-scaled new points.  Rows in blocks of INPUT_GRAD_ROWS, columns in groups of input_grad_group_width.
+// A mid-width context with the option "input_grad_mid" goes to kernels_input_grad_mid.hip; XhRow then has input_grad_row_stride(c) = Dh doubles per point.
 int launch_cross_grad(cglb_ctx* c, const void* XhRow, int64_t nrows, const double* Vi, int64_t ldv, int S, double* out, int64_t ldo, double* gout) {
+    if (input_grad_mid_on(c)) return launch_cross_grad_mid(c, XhRow, nrows, Vi, ldv, S, out, ldo, gout);
     if (c->dtype != CGLB_F64 || is_wide(c)) return cglb_fail(c, CGLB_ERR_BAD_ARG, "the input-gradient cross product needs an fp64 context of at most 32 input dimensions");
     if (S < 1 || ldv < S || (ldv % CROSS_MULTI_SP) || !gout || (out && ldo < S))
         return cglb_fail(c, CGLB_ERR_BAD_ARG, "bad column count, leading dimension or output of the input-gradient cross product");
@@ -213,6 +212,7 @@ static int feature_grad_group(cglb_ctx* c, const double* X, int64_t nrows, const
 // out[i * ldo + s] (out may be NULL) and gout[(i * S + s) * D + k] from the records launch_feature_operand left.  X: dev [nrows][D] raw rows.  The feature
 // rule (row_slab_feature_split) at this kernel's rows per block, capped by the slab
 int launch_feature_grad(cglb_ctx* c, const double* X, int64_t nrows, int64_t F, int S, double* out, int64_t ldo, double* gout) {
+    if (input_grad_mid_on(c)) return launch_feature_grad_mid(c, X, nrows, F, S, out, ldo, gout);
     if (c->dtype != CGLB_F64 || is_wide(c)) return cglb_fail(c, CGLB_ERR_BAD_ARG, "the input-gradient feature product needs an fp64 context of at most 32 input dimensions");
     if (S < 1 || F < 1 || !gout || (out && ldo < S)) return cglb_fail(c, CGLB_ERR_BAD_ARG, "bad feature count, column count or output of the input-gradient feature product");
     const int G = input_grad_group_width(c->Dp);

@@ -413,14 +413,18 @@ int wide_after_hypers(cglb_ctx* c) {
     return CGLB_OK;
 }
 
-int wide_prep_hot(cglb_ctx* c) {   // after wide_after_hypers: the device copies of centre and scale are current
-    if (c->Dh == 0 || c->N == 0) return CGLB_OK;
-    CGLB_DISPATCH_T(c->dtype, CGLB_DISPATCH_KIND(c->kind, hipLaunchKernelGGL((wide_prep_hot_kernel<T, KIND>), dim3((unsigned)((c->N + 3) / 4)), dim3(256), 0, c->stream,
-                                                                             (const T*)c->X, c->N, c->D, c->Dh, (const double*)c->wcenter, (const double*)c->wscale,
-                                                                             cglb_hot_scale(c), (T*)c->Xh, (T*)c->xah)));
+// any n raw rows of a mid-width context in hot units (the training rows: wide_prep_hot; new points of the input-gradient product), after
+// wide_after_hypers: the device copies of centre and scale are current
+int wide_prep_hot_rows(cglb_ctx* c, const void* Xraw, int64_t n, void* Xh_out, void* xah_out) {
+    if (c->Dh == 0 || n == 0) return CGLB_OK;
+    CGLB_DISPATCH_T(c->dtype, CGLB_DISPATCH_KIND(c->kind, hipLaunchKernelGGL((wide_prep_hot_kernel<T, KIND>), dim3((unsigned)((n + 3) / 4)), dim3(256), 0, c->stream,
+                                                                             (const T*)Xraw, n, c->D, c->Dh, (const double*)c->wcenter, (const double*)c->wscale,
+                                                                             cglb_hot_scale(c), (T*)Xh_out, (T*)xah_out)));
     CGLB_LAUNCH_CHECK(c);
     return CGLB_OK;
 }
+
+int wide_prep_hot(cglb_ctx* c) { return wide_prep_hot_rows(c, c->X, c->N, c->Xh, c->xah); }
 
 // At (nloc x M column-major, ld = lda) <- var * K(x_n, z_m) for the local rows
 int wide_kuf(cglb_ctx* c) {

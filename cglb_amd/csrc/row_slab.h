@@ -28,6 +28,16 @@
 #define ROW_SLAB_SLOTS 256        // most chunks of one launch of the multi-column, feature and gradient products
 #define ROW_SLAB_GRAD_DOUBLES (1 << 24)  // doubles of the slab of one gradient launch (128 MiB): caps the chunk count
 
+// ---- geometry of the value-and-gradient products by padded width (mirrored by tests/input_grad_ref.py and tests/input_grad_mid_ref.py) ----
+// Narrow (kernels_input_grad.hip): rows per lane and columns per group, chosen so that R (DP + G (DP + 1)) + DP row-resident doubles stay near 100
+// (200 of the 256 VGPRs of two waves per SIMD): 2 x 8 up to width 4 (88 + 4), 1 x 8 up to 8 (80 + 8), 1 x 4 up to 16 (84 + 16), 1 x 2 beyond (98 + 32)
+static constexpr int input_grad_rows_per_lane(int dp) { return dp <= 4 ? 2 : 1; }
+static constexpr int input_grad_group_width(int dp) { return dp <= 8 ? 8 : (dp <= 16 ? 4 : 2); }
+// Mid widths (kernels_input_grad_mid.hip, hot width dh in 48, 64, 80, 96): a new point is shared by SPLIT lanes of HD = dh / SPLIT coordinates each;
+// (2 + G) HD + G row-resident doubles per lane (coordinates, differences, G x HD gradient sums, G values): 76, 100, 82, 98.  256 / SPLIT rows per workgroup
+static constexpr int input_grad_mid_split(int dh) { return dh > 0 ? 4 : 0; }
+static constexpr int input_grad_mid_group(int dh) { return dh <= 64 ? 4 : 2; }
+
 // ---- device pieces ----
 // row k of the lane whose first row is rbase; rows past the end read the last row (and store nothing: row_slab_store)
 __device__ __forceinline__ int64_t row_slab_clamped(int64_t rbase, int k, int64_t nrows) {

@@ -454,7 +454,8 @@ class HipContext:
         return IterGPSamples(f, steps.value, half.value, U)
 
     # -- input gradients of predictive and sample paths (cglb_*_grad_matmat, cglb_itergp_predict_grad, cglb_itergp_paths_*): with respect to the
-    #    raw coordinates of the new points; the scope of itergp_predict, up to 32 input dimensions ----
+    #    raw coordinates of the new points; the scope of itergp_predict, up to 32 input dimensions.  set_option("input_grad_mid", 1) opens
+    #    every one of them at 33 to 96 dimensions (fp64, wide_reg on; get_stat("input_grad_native") tells) ----
     def _out(self, out, shape, what):
         if out is None:
             return torch.empty(shape, dtype=self.dtype, device=self.device)

@@ -368,10 +368,14 @@ int cglb_time_feature_matmat(cglb_ctx* ctx, int64_t n_rows, int64_t F, int S, in
  * bitwise equal samples.  The stored alpha and the variance cache are left as they are.  Scope of cglb_itergp_predict. */
 int cglb_itergp_sample(cglb_ctx* ctx, const void* xnew, int64_t n_new, const void* omega, const void* phase, const void* W, const void* eps, int64_t F,
                        int S, double max_error, int max_cg_iter, void* f_out, void* U_out, int* steps, double* half_rz);
-/* ---- input gradients of predictive and sample paths (csrc/kernels_input_grad.hip) ----
+/* ---- input gradients of predictive and sample paths (csrc/kernels_input_grad.hip, csrc/kernels_input_grad_mid.hip) ----
  * All gradients below are with respect to the RAW coordinates of the new point (not centred, not scaled).  Scope of every entry: that of
- * cglb_itergp_predict (fp64, one rank, one target column, the default bound) and d <= 32 - the gradient products have no wide path yet; else
- * CGLB_ERR_BAD_ARG with a message.  Not covered: fp32, N ranks, wide inputs.  The gpr / cglb / sgpr predictors have their own entries further down (cglb_predict_grad, cglb_gpr_predict_grad).
+ * cglb_itergp_predict (fp64, one rank, one target column, the default bound) and d <= 32; else CGLB_ERR_BAD_ARG with a message ("... no wide path
+ * yet ...").  OPT-IN beyond: cglb_set_option(ctx, "input_grad_mid", 1) opens every entry below at 33 <= d <= 96 on a context whose option
+ * "wide_reg" is on (the default): the same contracts, a new point shared by four lanes, 4 columns per group up to d = 64 and 2 beyond, 64 new points
+ * per workgroup.  The option defaults to 0, where behaviour, messages and results are unchanged; on a narrow context it changes nothing.  The
+ * statistic "input_grad_native" is 1 where the next call would run a register-resident instance (narrow or mid), 0 where it would be refused.
+ * Not covered: fp32, N ranks, d > 96, "wide_reg" 0.  The gpr / cglb / sgpr predictors have their own entries further down (cglb_predict_grad, cglb_gpr_predict_grad).
  *
  * Value and input gradient of K_*f V in one pass over the pairs:
  *   out [i, s]    =  variance sum_j kappa(x*_i, x_j) V[s, j]
@@ -490,6 +494,8 @@ int cglb_time_kernel(cglb_ctx* ctx, int which, int reps, double* ms_avg);
  * cglb_itergp_objective_and_grad) on this context in its current state - dtype, width, "wide_reg", "grad_multi_mid", ranks, shard - runs in ONE
  * pass over the kernel values (fp64 on one rank and one shard covering all rows, up to 32 dimensions and, register-resident, 33 ... 96), 0 if
  * it runs one single pass per pair and takes the kappa sums from one product;
+ * "input_grad_native": 1 if the next input-gradient call on this context in its current state - dtype, width, "wide_reg", "input_grad_mid" - runs a
+ * register-resident instance (fp64 up to 32 dimensions; 33 ... 96 under "input_grad_mid"), 0 if it is refused;
  * "exp_clamp" | "m32_bias": the exponent-range regime the last cglb_set_hypers chose from the data's per-column range and the lengthscales
  * (CGLB_ERR_STATE before one) - 1 if the pair kernels run their range-clamped instances (kernel values below 2^-1000 come out as that floor,
  * not 0), 0 for the unclamped ones | the positivity bias of the Matern squared distance in hot units^2 (0 for RBF; above 2e-8 the clamped
@@ -538,6 +544,8 @@ int cglb_get_stat(cglb_ctx* ctx, const char* name, double* value);
  * "grad_multi_mid" (inputs of 33 ... 96 dimensions, fp64, "wide_reg" 1: 1, default - the multi-pair gradient pass evaluates every kernel value
  *  once per group of up to 8 vector pairs; 0 - one single pass per pair and one product for the kappa sums, what every other wide context runs;
  *  for A/B timing and tests; a single pair takes the single pass either way) |
+ * "input_grad_mid" (inputs of 33 ... 96 dimensions, fp64, "wide_reg" 1: 0, default - the input-gradient entries refuse the context ("no wide path
+ *  yet"); 1 - they run through csrc/kernels_input_grad_mid.hip; no effect on any other width or entry) |
  * "drop_weighted_operand" (any value: forget the pre-weighted copy cglb_vec_update_p_seg made of its p - for callers that modify p before the next mat-vec) |
  * "logdet_bound" (the log-det term of the bound; cglb_logdet, cglb_objective_and_grad and its gradient follow it.  e = y - mu, s = noise,
  *  f = variance, A = L^-1 K_uf / sqrt(s), B = I + A A^T = LB LB^T, C = LB^-1 A, t = N f / s - tr A A^T:
