@@ -819,7 +819,14 @@ class _PredictGrad:
     """What the gradient predictors of the cglb / sgpr / gpr classes share: `forward(xnew)` -> (mean [n, 1], dmean [n, d], var [n, 1], dvar [n, d]),
     the gradients with respect to the new points; `mean_and_variance(xnew)` -> (mean, var), differentiable by autograd when `xnew.requires_grad`
     (one torch.autograd.Function whose backward contracts the incoming gradients with dmean and dvar), so any torch acquisition function
-    differentiates through the library."""
+    differentiates through the library.
+    Up to 32 input dimensions; `wide=True` sets the option "input_grad_mid" on the model's context, exactly as PredictGradIterGPR does, which opens
+    33 to 96 dimensions (fp64, wide_reg on: the register-resident mid-width kernels) - without it such a model is refused as before."""
+
+    @staticmethod
+    def _open_wide(model, wide):
+        if wide:
+            model.hip.set_option("input_grad_mid", 1)
 
     @staticmethod
     def _refuse(model):
@@ -846,13 +853,15 @@ class _PredictGrad:
 
 class PredictGradCG(_PredictGrad, PredictCG):
     """`PredictGradCG(model)(xnew)`: PredictCG (its solve for v, cached until `clear_cache`) with the input gradients of mean and variance
-    (cglb_predict_grad).  Takes CGLB, CGLBN2M and CGLBNM2; fp64, one rank, one target column, up to 32 input dimensions."""
+    (cglb_predict_grad).  Takes CGLB, CGLBN2M and CGLBNM2; fp64, one rank, one target column, up to 32 input dimensions, 33 to 96 with
+    `wide=True`."""
 
-    def __init__(self, model: CGLB, cg_opt: Optional[ConjugateGradient] = None):
+    def __init__(self, model: CGLB, cg_opt: Optional[ConjugateGradient] = None, wide: bool = False):
         if not isinstance(model, CGLB):
             raise ValueError(f"CGLB model expected in the constructor of the {self.__class__}")
         self._refuse(model)
         PredictCG.__init__(self, model, cg_opt)
+        self._open_wide(model, wide)
 
     def value_and_grad(self, xnew):
         self._solve()
@@ -861,14 +870,15 @@ class PredictGradCG(_PredictGrad, PredictCG):
 
 class PredictGradSGPR(_PredictGrad, nn.Module):
     """`PredictGradSGPR(model)(xnew)`: Titsias' predictive (PredictSGPR: v = 0, no solve) with the input gradients of mean and variance.  Takes
-    SGPR and SGPRN2M."""
+    SGPR and SGPRN2M; 33 to 96 input dimensions with `wide=True`."""
 
-    def __init__(self, model: SGPR):
+    def __init__(self, model: SGPR, wide: bool = False):
         if not isinstance(model, SGPR) or isinstance(model, CGLB):
             raise ValueError(f"SGPR model expected in the constructor of the {self.__class__}")
         self._refuse(model)
         nn.Module.__init__(self)
         object.__setattr__(self, "model", model)
+        self._open_wide(model, wide)
         self.cached = False
 
     def value_and_grad(self, xnew):
@@ -882,14 +892,15 @@ class PredictGradSGPR(_PredictGrad, nn.Module):
 
 class PredictGradGPR(_PredictGrad, nn.Module):
     """`PredictGradGPR(model)(xnew)`: predict_f of the exact model (PredictGPR) with the input gradients of mean and variance
-    (cglb_gpr_predict_grad); this class's variance, and so its gradient, is exact."""
+    (cglb_gpr_predict_grad); this class's variance, and so its gradient, is exact.  33 to 96 input dimensions with `wide=True`."""
 
-    def __init__(self, model: ExactGPR):
+    def __init__(self, model: ExactGPR, wide: bool = False):
         if not isinstance(model, ExactGPR):
             raise ValueError(f"ExactGPR model expected in the constructor of the {self.__class__}")
         self._refuse(model)
         nn.Module.__init__(self)
         object.__setattr__(self, "model", model)
+        self._open_wide(model, wide)
 
     def value_and_grad(self, xnew):
         self.model.push_hypers()

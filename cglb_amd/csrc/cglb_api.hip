@@ -1180,6 +1180,7 @@ int cglb_set_data(cglb_ctx* c, const void* X, const void* y) {
     c->it_valid = false;
     c->it_cache_rank = c->it_cache_request = 0;
     c->p = 1;  // one target column again (cglb_set_targets)
+    c->Zhm_valid = false;  // the centre of the hot units follows the data
     c->have_local = c->have_terms = false;
     return CGLB_OK;
 }
@@ -1199,6 +1200,7 @@ int cglb_set_hypers(cglb_ctx* c, const double* lengthscales, double variance, do
     c->it_valid = false;
     c->it_cache_rank = c->it_cache_request = 0;  // the variance cache belongs to the old hyper-parameters
     c->pwh_src = nullptr;  // the column weights change with the hypers
+    c->Zhm_valid = false;  // rebuilt by the first row-weighted gradient product that needs it
     {   // |a_i + a_j + xs_i.xs_j| <= 2 max|xs|^2 (scaled units: octaves for RBF, octaves^2 for Matern).  The unclamped 2^x of
         // the hot loops needs the exponent inside [-1000, 0] octaves (exp2_tab_scale) and its hot-unit integer below 2^30.
         const double ks = cglb_kscale(c);
@@ -1585,10 +1587,17 @@ static int predict_rows(cglb_ctx* c, const void* v_full, const void* u, const vo
     if (c->quad_term == 1) HIP_CHECK(c, hipMemsetAsync(f_mean, 0, (size_t)n_new * c->esz, c->stream));  // cg_mean = 0 at v = 0
     else CGLB_TRY(launch_cross_matvec(c, pts.xs, pts.xa, n_new, v_full, f_mean));         // cg_mean = ksf @ v   (models.py:334)
     void *xh = nullptr, *qv = nullptr;
+    const bool mid = g_mean && input_grad_mid_on(c);  // mid width: the hot set [n_new][Dh] of its own (pts.xs is the plain scaled set on a wide context)
     if (g_mean) {  // grad (K_*f v) while the new points are in hot units, which the row-weighted kernel below reads from a copy
-        CGLB_TRY(pts.tmp.alloc(c, &xh, (size_t)n_new * c->Dp * sizeof(double)));
         CGLB_TRY(pts.tmp.alloc(c, &qv, (size_t)M * sizeof(double)));
-        HIP_CHECK(c, hipMemcpyAsync(xh, pts.xs, (size_t)n_new * c->Dp * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+        if (mid) {
+            CGLB_TRY(pts.stage_hot_mid());
+            CGLB_TRY(predict_grad_mid_inducing(c));
+            xh = pts.xh;
+        } else {
+            CGLB_TRY(pts.tmp.alloc(c, &xh, (size_t)n_new * c->Dp * sizeof(double)));
+            HIP_CHECK(c, hipMemcpyAsync(xh, pts.xs, (size_t)n_new * c->Dp * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+        }
         if (c->quad_term != 1) {
             int64_t ldv = 0;
             CGLB_TRY(launch_cross_multi_operand(c, v_full, 1, &ldv));
@@ -1630,8 +1639,9 @@ static int predict_rows(cglb_ctx* c, const void* v_full, const void* u, const vo
         BLAS_CHECK(c, rocblas_dtrsm(c->blas, rocblas_side_right, rocblas_fill_lower, rocblas_operation_none, rocblas_diagonal_non_unit, (int)n_new, M, &one,
                                     (const double*)c->Lc, M, (double*)t2, (int)ld));
     }
-    return launch_weighted_grad(c, c->ls, c->var, (const double*)xh, n_new, (const double*)c->Zh, M, (const double*)qv, g_var ? (const double*)t2 : nullptr, ld,
-                                nullptr, (double*)g_mean, c->quad_term != 1, nullptr, (double*)g_var, -2.0);
+    return launch_weighted_grad(c, c->ls, c->var, (const double*)xh, n_new, (const double*)(mid ? c->Zhm : c->Zh), M, (const double*)qv,
+                                g_var ? (const double*)t2 : nullptr, ld, nullptr, (double*)g_mean, c->quad_term != 1, nullptr, (double*)g_var, -2.0,
+                                mid ? (const double*)c->wscale : nullptr);
 }
 
 int cglb_predict(cglb_ctx* c, const void* v_full, const void* xnew, int64_t n_new, void* f_mean, void* f_var) {
@@ -1648,13 +1658,16 @@ int cglb_predict(cglb_ctx* c, const void* v_full, const void* xnew, int64_t n_ne
     return predict_rows(c, v_full, c->w_u, xnew, n_new, f_mean, f_var);
 }
 
-// the scope of the input-gradient entries of the sparse predictors: fp64, one rank, one target column, at most 32 input dimensions
+// the scope of the input-gradient entries of the sparse predictors: fp64, one rank, one target column; at most 32 input dimensions, or a mid-width context
+// (33 .. 96, wide_reg on) with the option "input_grad_mid"
 static int require_predict_grad_ok(cglb_ctx* c) {
     if (c->dtype != CGLB_F64)
         return cglb_fail(c, CGLB_ERR_BAD_ARG, "the input gradients of the predictive need an fp64 context (-t fp64): the gradient kernels have no fp32 instances");
     if (c->par_world > 1 || c->comm) return cglb_fail(c, CGLB_ERR_BAD_ARG, "the input gradients of the predictive are not available on more than one rank");
     if (c->p != 1) return cglb_fail(c, CGLB_ERR_BAD_ARG, "the input gradients of the predictive take one target column");
-    if (is_wide(c)) return cglb_fail(c, CGLB_ERR_BAD_ARG, "the input-gradient products have no wide path yet: they are available up to 32 input dimensions");
+    if (is_wide(c) && !input_grad_mid_on(c))
+        return cglb_fail(c, CGLB_ERR_BAD_ARG, "the input-gradient products have no wide path yet: they are available up to 32 input dimensions, and at 33 to 96 with the "
+                                              "option input_grad_mid 1 (fp64, wide_reg on)");
     return CGLB_OK;
 }
 
@@ -1692,8 +1705,15 @@ int cglb_cross_grad_weighted(cglb_ctx* c, int set, const void* xnew, int64_t n_n
     StagedPoints pts(c);
     CGLB_TRY(pts.alloc(n_new, sizeof(double)));
     CGLB_TRY(pts.stage(xnew, true));
-    return launch_weighted_grad(c, c->ls, c->var, (const double*)pts.xs, n_new, set == 0 ? (const double*)c->Xh : (const double*)c->Zh, set == 0 ? c->N : (int64_t)c->M,
-                                (const double*)u, (const double*)Wt, ldw, (double*)out_u, (double*)gout_u, false, (double*)out_w, (double*)gout_w, 1.0);
+    const bool mid = input_grad_mid_on(c);  // both sets at width Dh: the new points from the staged raw rows, Z from the buffer of its own
+    if (mid) {
+        CGLB_TRY(pts.stage_hot_mid());
+        if (set == 1) CGLB_TRY(predict_grad_mid_inducing(c));
+    }
+    const void* ph = set == 0 ? c->Xh : (mid ? c->Zhm : c->Zh);
+    return launch_weighted_grad(c, c->ls, c->var, (const double*)(mid ? pts.xh : pts.xs), n_new, (const double*)ph, set == 0 ? c->N : (int64_t)c->M,
+                                (const double*)u, (const double*)Wt, ldw, (double*)out_u, (double*)gout_u, false, (double*)out_w, (double*)gout_w, 1.0,
+                                mid ? (const double*)c->wscale : nullptr);
 }
 
 int cglb_time_predict_grad(cglb_ctx* c, int64_t n_new, int with_grad, int reps, double* ms_avg) {
@@ -1927,6 +1947,10 @@ int cglb_get_stat(cglb_ctx* c, const char* name, double* value) {
     }
     if (!strcmp(name, "matmat_native")) { *value = (c->have_data && kff_multi_native(c)) ? 1.0 : 0.0; return CGLB_OK; }  // shared-kernel instance or single mat-vecs
     if (!strcmp(name, "grad_multi_native")) { *value = (c->have_data && grad_multi_native(c)) ? 1.0 : 0.0; return CGLB_OK; }  // multi-pair gradient instance or single passes
+    if (!strcmp(name, "predict_grad_native")) {  // the next cglb_predict_grad runs (fp64, one rank, one target column; narrow, or mid under "input_grad_mid") or is refused
+        *value = (c->dtype == CGLB_F64 && c->par_world == 1 && !c->comm && c->p == 1 && (!is_wide(c) || input_grad_mid_on(c))) ? 1.0 : 0.0;
+        return CGLB_OK;
+    }
     if (!strcmp(name, "input_grad_native")) {  // the next input-gradient cross product runs a register-resident instance (narrow, or mid under "input_grad_mid") or is refused
         *value = (c->dtype == CGLB_F64 && (!is_wide(c) || input_grad_mid_on(c))) ? 1.0 : 0.0;
         return CGLB_OK;

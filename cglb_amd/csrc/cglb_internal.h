@@ -74,7 +74,7 @@ struct cglb_ctx {
     int Dh = 0;        // 32 < D <= 96, fp64: padded width (48, 64, 80, 96) of the hot operand set Xh kept for the register-resident mat-vec
     int wide_grad_sym = 1;  // option "wide_grad_sym": 0 evaluates every tile of the tiled K_ff gradient pass (A/B)
     int wide_reg = 1;  // option "wide_reg": 0 sends that mat-vec through the Gram tiles of kernels_wide.hip as well (A/B, fallback)
-    int input_grad_mid = 0;  // option "input_grad_mid": 1 opens the value-and-gradient cross product of a mid-width context (kernels_input_grad_mid.hip); 0: refused
+    int input_grad_mid = 0;  // option "input_grad_mid": 1 opens every input-gradient product of a mid-width context (kernels_input_grad_mid.hip, kernels_predict_grad_mid.hip); 0: refused
     int grad_multi_mid = 1;  // option "grad_multi_mid": 0 sends the multi-pair gradient pass of a mid-width context through single passes (A/B, fallback)
     size_t esz = 8;
     hipStream_t stream = nullptr;
@@ -93,6 +93,8 @@ struct cglb_ctx {
     // scaled operands of the streaming kernels (T): xs = (x-c)/l*kscale padded to Dp, xa = per-row norm term
     void *Xs = nullptr, *xa = nullptr, *Zs = nullptr, *za = nullptr;
     void *Zh = nullptr, *zah = nullptr;  // hot-scaled inducing points (implicit preconditioner)
+    void* Zhm = nullptr;                 // [M][Dh] inducing points in hot units at width Dh: the row-weighted gradient product of a mid-width context (first use)
+    bool Zhm_valid = false;              // Zhm belongs to the current data and hyper-parameters (predict_grad_mid_inducing)
     void *Linv = nullptr, *LinvT = nullptr;  // L^-1 (column-major lower) and its transpose (implicit preconditioner)
     void* w_q = nullptr;                 // [M] scratch
     void* ppart = nullptr;               // partial slab of launch_pairs_rect
@@ -224,6 +226,7 @@ struct cglb_ctx {
     double *gpr_Xh = nullptr, *gpr_xh = nullptr, *gpr_Ct = nullptr;  // input gradients: X and the batch in hot units at gpr_ls, C = K^-1 K_f* as [N][ld]
     size_t gpr_xh_cap = 0, gpr_Ct_cap = 0;
     bool gpr_hot_valid = false;                         // gpr_Xh holds X at the current data and lengthscales
+    double* gpr_cs = nullptr;                           // mid widths: device [centre (D) | ks / gpr_ls (D)], scales of gpr_Xh / gpr_xh and of their gradient constants
     size_t gpr_bytes = 0;                               // device bytes the pool holds (cglb_get_stat "gpr_bytes")
     hipEvent_t gpr_ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};  // start | fill | factor | solves | inverse | gradient of the last evaluation
     int gpr_ev_last = 0;                                // index of the last event that evaluation recorded (2: no solve reached, 3: value only, 5: with gradient)
@@ -360,7 +363,7 @@ static inline int mid_dim(int d, int dtype) {
     return d <= 48 ? 48 : d <= 64 ? 64 : d <= 80 ? 80 : 96;  // (a 128-wide row operand alone would fill the 256 VGPRs VALU instructions can address)
 }
 static inline bool mid_reg(const cglb_ctx* c) { return c->Dh > 0 && c->wide_reg != 0; }
-static inline bool input_grad_mid_on(const cglb_ctx* c) { return c->input_grad_mid != 0 && mid_reg(c); }  // the input-gradient cross product runs at this mid width
+static inline bool input_grad_mid_on(const cglb_ctx* c) { return c->input_grad_mid != 0 && mid_reg(c); }  // every input-gradient product runs at this mid width
 
 // kernels_wide.hip: D > 32.  The Gram part of the pair value is a contraction with k = D and goes through rocBLAS in tiles; same
 // contracts as the launchers below they stand in for.
@@ -460,15 +463,32 @@ int launch_feature_grad(cglb_ctx* c, const double* X, int64_t nrows, int64_t F, 
 // XhRow [nrows][Dh] from wide_prep_hot_rows.  Bitwise repeatable.
 int launch_cross_grad_mid(cglb_ctx* c, const void* XhRow, int64_t nrows, const double* Vi, int64_t ldv, int S, double* out, int64_t ldo, double* gout);
 int launch_feature_grad_mid(cglb_ctx* c, const double* X, int64_t nrows, int64_t F, int S, double* out, int64_t ldo, double* gout);  // launch_feature_grad's contract there
+// the finish kernel of every mid-width input-gradient product: the slabs part[js][i][b < g][Dh + 1] in fixed order, then per slot b
+//   out[b][i * ldo] = vscale * sum (out[b] NULL: no value), gout[b][i * ldg + k] = (gfac[b] scale[k]) * sum, k < D (gout[b] NULL: slot not stored);
+// scale: the device copy of ks / l_k (NULL: 1, the feature product); add0: slot 0 adds to what gout[0] holds
+#define INPUT_GRAD_MID_SLOTS 4
+struct InputGradMidOut { double* out[INPUT_GRAD_MID_SLOTS]; double* gout[INPUT_GRAD_MID_SLOTS]; double gfac[INPUT_GRAD_MID_SLOTS]; int64_t ldo, ldg; int add0; };
+int launch_input_grad_mid_finish(cglb_ctx* c, const double* part, int64_t jsplit, int64_t nrows, int g, double vscale, const double* scale, const InputGradMidOut& o);
 int input_grad_mid_rows_per_block(const cglb_ctx* c);   // new points per workgroup (64)
 int input_grad_mid_width(const cglb_ctx* c);            // columns per group at the context's hot width (4 or 2)
 int launch_input_grad_var(cglb_ctx* c, const double* B, int64_t ldb, const double* G, int64_t nrows, int sp, double* g_var);  // g_var[i][k] = -2 sum_s B[i][s] G[i][s][k]
 int launch_input_grad_paths(cglb_ctx* c, const double* Gf, const double* KU, const double* gf, const double* gk, int64_t n, int S, double* f, double* g);
 // kernels_predict_grad.hip: row-weighted value and input gradient of a cross product between two explicit hot-unit point sets (lengthscales ls, host):
-// out_u / gout_u with the shared weight u [npts], out_w / gout_w with new point i's own weights Wt[m * ldw + i]; gout_w times wscale, gout_u added to if add_u
+// out_u / gout_u with the shared weight u [npts], out_w / gout_w with new point i's own weights Wt[m * ldw + i]; gout_w times wscale, gout_u added to if add_u.
+// Both sets have predict_grad_row_stride(c) doubles per point; a context with input_grad_mid_on(c) takes the gradient constants from scale_dev, the device
+// copy of ks / l_k at ls, in place of ls
 int launch_weighted_grad(cglb_ctx* c, const double* ls, double var, const double* XhRow, int64_t nrows, const double* Ph, int64_t npts, const double* u,
-                         const double* Wt, int64_t ldw, double* out_u, double* gout_u, bool add_u, double* out_w, double* gout_w, double wscale);
+                         const double* Wt, int64_t ldw, double* out_u, double* gout_u, bool add_u, double* out_w, double* gout_w, double wscale,
+                         const double* scale_dev = nullptr);
 int launch_hot_points(cglb_ctx* c, const double* ls, const double* x, int64_t n, double* out);  // out [n][Dp] <- x [n][D] in hot units at ls
+// kernels_predict_grad_mid.hip: the same product on a context with input_grad_mid_on(c) (fp64, 32 < D <= 96), where launch_weighted_grad sends each of its
+// row blocks: both point sets [.][Dh]; scale: the device copy of ks / l_k both were staged with (c->wscale, or the second half of gpr_cs)
+int launch_weighted_grad_mid(cglb_ctx* c, const double* scale, double var, const double* XhRow, int64_t nrows, const double* Ph, int64_t npts, const double* u,
+                             const double* Wt, int64_t ldw, double* out_u, double* gout_u, bool add_u, double* out_w, double* gout_w, double wscale);
+int launch_hot_points_mid(cglb_ctx* c, const double* cs, const double* x, int64_t n, double* out);  // out [n][Dh] <- x [n][D] in hot units, zero padded; cs dev [centre | ks / l]
+int predict_grad_mid_inducing(cglb_ctx* c);               // c->Zhm [M][Dh] at the current hyper-parameters, built where it is not valid
+int predict_grad_mid_rows_per_block(const cglb_ctx* c);   // new points per workgroup of the mid-width row-weighted kernel (64)
+static inline int64_t predict_grad_row_stride(const cglb_ctx* c) { return input_grad_mid_on(c) ? c->Dh : c->Dp; }  // doubles per point of both sets of launch_weighted_grad
 int launch_transpose(cglb_ctx* c, const double* src, int64_t lds, int64_t rows, int64_t cols, double* dst, int64_t ldd);  // dst[j * ldd + i] = src[i * lds + j]
 int predict_grad_rows_per_block(const cglb_ctx* c);  // new points per workgroup of the row-weighted kernel at the context's width
 int predict_grad_stat(cglb_ctx* c, const char* name, double* value);  // "predict_grad_kernel_ms"; -1: not this name

@@ -386,9 +386,11 @@ int gpr_predict_batches(cglb_ctx* c, const void* xnew, int64_t n_new, double* me
     const int64_t bmax = std::min(GPR_PREDICT_BATCH, n_new);
     if (bmax == 0) return CGLB_OK;
     const int64_t ldc = (bmax + 7) & ~(int64_t)7;
+    const bool mid = g_mean && input_grad_mid_on(c);             // mid width: hot sets [.][Dh] by launch_hot_points_mid, scales from the device copy gpr_cs
+    const size_t hw = (size_t)predict_grad_row_stride(c);        // doubles per point of gpr_Xh / gpr_xh
     if (g_mean) {  // X and the batch in the pair kernel's units, C as [N][ldc]: checked against the free memory like the factor
         size_t need = 0;
-        if (!c->gpr_Xh) need += (size_t)N * c->Dp * sizeof(double);
+        if (!c->gpr_Xh) need += (size_t)N * hw * sizeof(double);
         if (c->gpr_Ks_cap < (size_t)N * bmax * sizeof(double)) need += (size_t)N * bmax * sizeof(double);
         if (g_var && c->gpr_Ct_cap < (size_t)N * ldc * sizeof(double)) need += (size_t)N * ldc * sizeof(double);
         if (need > 0) {
@@ -398,11 +400,20 @@ int gpr_predict_batches(cglb_ctx* c, const void* xnew, int64_t n_new, double* me
                 return cglb_fail(c, CGLB_ERR_HIP, "the exact GPR input gradients at N = " + std::to_string(N) + " need " + std::to_string(need >> 20) +
                                                       " MiB for the panels of a batch but only " + std::to_string(free_b >> 20) + " MiB of device memory are free");
         }
-        CGLB_TRY(gpr_alloc(c, &c->gpr_Xh, (size_t)N * c->Dp));
-        CGLB_TRY(gpr_reserve(c, &c->gpr_xh, &c->gpr_xh_cap, (size_t)bmax * c->Dp));
+        CGLB_TRY(gpr_alloc(c, &c->gpr_Xh, (size_t)N * hw));
+        CGLB_TRY(gpr_reserve(c, &c->gpr_xh, &c->gpr_xh_cap, (size_t)bmax * hw));
         if (g_var) CGLB_TRY(gpr_reserve(c, &c->gpr_Ct, &c->gpr_Ct_cap, (size_t)N * ldc));
+        if (mid) CGLB_TRY(gpr_alloc(c, &c->gpr_cs, (size_t)2 * D));
         if (!c->gpr_hot_valid) {  // once per hyper-parameter set
-            CGLB_TRY(launch_hot_points(c, c->gpr_ls.data(), (const double*)c->X, N, c->gpr_Xh));
+            if (mid) {
+                std::vector<double> cs((size_t)2 * D);
+                for (int d = 0; d < D; ++d) { cs[d] = c->xmean[d]; cs[D + d] = cglb_kscale(c) / c->gpr_ls[d]; }
+                HIP_CHECK(c, hipMemcpyAsync(c->gpr_cs, cs.data(), cs.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
+                HIP_CHECK(c, hipStreamSynchronize(c->stream));  // `cs` is pageable host memory
+                CGLB_TRY(launch_hot_points_mid(c, c->gpr_cs, (const double*)c->X, N, c->gpr_Xh));
+            } else {
+                CGLB_TRY(launch_hot_points(c, c->gpr_ls.data(), (const double*)c->X, N, c->gpr_Xh));
+            }
             c->gpr_hot_valid = true;
         }
     }
@@ -433,14 +444,15 @@ int gpr_predict_batches(cglb_ctx* c, const void* xnew, int64_t n_new, double* me
         CGLB_LAUNCH_CHECK(c);
         if (!g_mean) return CGLB_OK;
         // C = L^-T (L^-1 K_f*) in place, transposed to [N][ldc] (a transpose pass); one launch against X with u = alpha, Wt = C
-        CGLB_TRY(launch_hot_points(c, c->gpr_ls.data(), raw, b, c->gpr_xh));
+        if (mid) CGLB_TRY(launch_hot_points_mid(c, c->gpr_cs, raw, b, c->gpr_xh));
+        else CGLB_TRY(launch_hot_points(c, c->gpr_ls.data(), raw, b, c->gpr_xh));
         if (g_var) {
             BLAS_CHECK(c, rocblas_dtrsm(c->blas, rocblas_side_left, rocblas_fill_lower, rocblas_operation_transpose, rocblas_diagonal_non_unit, (int)N, (int)b,
                                         &one, c->gpr_L, (int)N, c->gpr_Ks, (int)N));
             CGLB_TRY(launch_transpose(c, c->gpr_Ks, N, b, N, c->gpr_Ct, ldc));
         }
         return launch_weighted_grad(c, c->gpr_ls.data(), c->gpr_var, c->gpr_xh, b, c->gpr_Xh, N, c->gpr_alpha, g_var ? c->gpr_Ct : nullptr, ldc, nullptr,
-                                    g_mean + off * D, false, nullptr, g_var ? g_var + off * D : nullptr, -2.0);
+                                    g_mean + off * D, false, nullptr, g_var ? g_var + off * D : nullptr, -2.0, mid ? c->gpr_cs + D : nullptr);
     }();
     if (var_tmp) (void)hipStreamSynchronize(c->stream);  // before `tmp` frees
     return rc;
@@ -506,7 +518,9 @@ int cglb_gpr_predict(cglb_ctx* c, const void* xnew, int64_t n_new, void* f_mean,
 int cglb_gpr_predict_grad(cglb_ctx* c, const void* xnew, int64_t n_new, void* f_mean, void* g_mean, void* f_var, void* g_var) {
     if (!c || !xnew || !f_mean || !g_mean || (!f_var) != (!g_var) || n_new < 0) return c ? cglb_fail(c, CGLB_ERR_BAD_ARG, "bad argument") : CGLB_ERR_BAD_ARG;
     CGLB_TRY(gpr_require(c));
-    if (is_wide(c)) return cglb_fail(c, CGLB_ERR_BAD_ARG, "the input-gradient products have no wide path yet: they are available up to 32 input dimensions");
+    if (is_wide(c) && !input_grad_mid_on(c))
+        return cglb_fail(c, CGLB_ERR_BAD_ARG, "the input-gradient products have no wide path yet: they are available up to 32 input dimensions, and at 33 to 96 with the "
+                                              "option input_grad_mid 1 (fp64, wide_reg on)");
     return gpr_predict_batches(c, xnew, n_new, (double*)f_mean, (double*)g_mean, (double*)f_var, (double*)g_var);
 }
 

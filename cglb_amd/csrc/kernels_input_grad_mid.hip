@@ -166,22 +166,50 @@ __global__ __launch_bounds__(256, 2) void feature_grad_mid_kernel(const double* 
     }
 }
 
-// the slabs in fixed order, then the constants: gout[(i * S + b) * d + k] = (gfac scale[k]) sum_js part[js][i][b][k] (k < d), out[i * ldo + b] = vscale *
-// sum_js part[js][i][b][dp] (out may be NULL), b < sg.  scale: the device copy of kscale / l_k (NULL: 1, the feature product).  One thread per (i, b, k <= dp)
-__global__ __launch_bounds__(256) void input_grad_mid_finish_kernel(const double* __restrict__ part, int jsplit, int64_t nrows, int g, int sg, int dp, int d,
-                                                                    double vscale, double gfac, const double* __restrict__ scale, double* __restrict__ out,
-                                                                    int64_t ldo, double* __restrict__ gout, int64_t S) {
+// the slabs in fixed order, then the constants, per slot b < g (InputGradMidOut, cglb_internal.h): gout[b][i * ldg + k] = (gfac[b] scale[k]) sum_js
+// part[js][i][b][k] (k < d; added to what is there for slot 0 under add0), out[b][i * ldo] = vscale * sum_js part[js][i][b][dp]; a slot whose pointer is NULL
+// is not stored.  scale: the device copy of kscale / l_k (NULL: 1, the feature product).  One thread per (i, b, k <= dp).  The cross and feature products
+// (slot b = column b of the group: out + b, gout + b d, ldg = S d) and the row-weighted product (kernels_predict_grad_mid.hip: one array per slot) share it
+__global__ __launch_bounds__(256) void input_grad_mid_finish_kernel(const double* __restrict__ part, int jsplit, int64_t nrows, int g, int dp, int d, double vscale,
+                                                                    const double* __restrict__ scale, InputGradMidOut o) {
     const int64_t per = (int64_t)g * (dp + 1);
     const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= nrows * per) return;
     const int64_t i = idx / per;
     const int e = (int)(idx - i * per);
     const int b = e / (dp + 1), k = e - b * (dp + 1);
-    if (b >= sg || (k >= d && k < dp) || (k == dp && !out)) return;
+    double* __restrict__ dst = k == dp ? o.out[b] : o.gout[b];
+    if (!dst || (k >= d && k < dp)) return;
     double s = 0.0;
     for (int js = 0; js < jsplit; ++js) s += part[(int64_t)js * nrows * per + idx];
-    if (k == dp) out[i * ldo + b] = vscale * s;
-    else gout[(i * S + b) * d + k] = (scale ? gfac * scale[k] : gfac) * s;
+    if (k == dp) dst[i * o.ldo] = vscale * s;
+    else {
+        const double gv = (scale ? o.gfac[b] * scale[k] : o.gfac[b]) * s;
+        dst[i * o.ldg + k] = (o.add0 && b == 0) ? dst[i * o.ldg + k] + gv : gv;
+    }
+}
+
+int launch_input_grad_mid_finish(cglb_ctx* c, const double* part, int64_t jsplit, int64_t nrows, int g, double vscale, const double* scale, const InputGradMidOut& o) {
+    if (g < 1 || g > INPUT_GRAD_MID_SLOTS) return cglb_fail(c, CGLB_ERR_BAD_ARG, "slot count outside the mid-width input-gradient finish kernel's");
+    const int64_t total = nrows * g * (c->Dh + 1);
+    hipLaunchKernelGGL(input_grad_mid_finish_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, c->stream, part, (int)jsplit, nrows, g, c->Dh, c->D, vscale,
+                       scale, o);
+    CGLB_LAUNCH_CHECK(c);
+    return CGLB_OK;
+}
+
+// the slots of one group of sg <= g columns of a product with S columns: column b at out + b (row stride ldo; NULL: no values) and gout + b d (row stride S d)
+static InputGradMidOut input_grad_mid_columns(int sg, int d, double gfac, double* out, int64_t ldo, double* gout, int64_t S) {
+    InputGradMidOut o;
+    for (int b = 0; b < INPUT_GRAD_MID_SLOTS; ++b) {
+        o.out[b] = (b < sg && out) ? out + b : nullptr;
+        o.gout[b] = b < sg ? gout + (int64_t)b * d : nullptr;
+        o.gfac[b] = gfac;
+    }
+    o.ldo = ldo;
+    o.ldg = S * d;
+    o.add0 = 0;
+    return o;
 }
 
 int input_grad_mid_rows_per_block(const cglb_ctx* c) { return 256 / input_grad_mid_split(c->Dh); }
@@ -203,11 +231,8 @@ static int cross_grad_mid_group(cglb_ctx* c, const double* XhRow, int64_t nrows,
     CGLB_LAUNCH_CHECK(c);
     // delta_hot = ks hot (x*_k - x_jk) / l_k, so d kappa / d x*_k = -var h delta_hot / (l_k ks hot) = -var h delta_hot (ks / l_k) / (ks^2 hot)
     const double ks = cglb_kscale(c);
-    const int64_t total = nrows * G * (DP + 1);
-    hipLaunchKernelGGL(input_grad_mid_finish_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, c->stream, (const double*)c->ig_part, (int)jsplit, nrows, G,
-                       sg, DP, c->D, c->var, -c->var / (ks * ks * cglb_hot_scale(c)), (const double*)c->wscale, out, ldo, gout, S);
-    CGLB_LAUNCH_CHECK(c);
-    return CGLB_OK;
+    return launch_input_grad_mid_finish(c, c->ig_part, jsplit, nrows, G, c->var, (const double*)c->wscale,
+                                        input_grad_mid_columns(sg, c->D, -c->var / (ks * ks * cglb_hot_scale(c)), out, ldo, gout, S));
 }
 
 template <int KIND>
@@ -274,12 +299,10 @@ int launch_feature_grad_mid(cglb_ctx* c, const double* X, int64_t nrows, int64_t
                 case 96: CGLB_TRY(feature_grad_mid_group<96>(c, X + i0 * c->D, nr, rec, b0 % FEATURE_SP, F, jsplit, jchunk, (unsigned)bx)); break;
                 default: return cglb_fail(c, CGLB_ERR_BAD_ARG, "unsupported mid width");
             }
-            const int64_t total = nr * G * (Dh + 1);
             // the records hold omega / (2 pi l): the constant of every gradient component is -2 pi amp
-            hipLaunchKernelGGL(input_grad_mid_finish_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, c->stream, (const double*)c->ig_part, (int)jsplit, nr, G,
-                               sg, Dh, c->D, amp, -6.283185307179586476925286766559 * amp, (const double*)nullptr, out ? out + i0 * ldo + b0 : nullptr, ldo,
-                               gout + (i0 * S + b0) * c->D, (int64_t)S);
-            CGLB_LAUNCH_CHECK(c);
+            CGLB_TRY(launch_input_grad_mid_finish(c, c->ig_part, jsplit, nr, G, amp, nullptr,
+                                                  input_grad_mid_columns(sg, c->D, -6.283185307179586476925286766559 * amp, out ? out + i0 * ldo + b0 : nullptr, ldo,
+                                                                         gout + (i0 * S + b0) * c->D, (int64_t)S)));
         }
     }
     return CGLB_OK;

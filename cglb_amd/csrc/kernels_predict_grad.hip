@@ -14,6 +14,7 @@
 // instance, so every output is bitwise the same whichever of the others are requested.
 // Pair: DIRECT differences in hot units and kappa_hfac_hot_from_d2 (always the range-clamped 2^x), as cross_grad_kernel and for its reason; a
 // coincident pair has delta = 0 exactly and adds exactly zero to the gradient.  fp64, Dp <= 32.  Register use of every instance: DESIGN.md 4i.
+// Mid widths (33 .. 96 dimensions, option "input_grad_mid"): the same contract in kernels_predict_grad_mid.hip, where launch_weighted_grad sends each row block.
 #include "pair_common.h"
 #include "row_slab.h"
 #include <cstring>
@@ -145,7 +146,7 @@ __global__ __launch_bounds__(256) void transpose_kernel(const double* __restrict
     }
 }
 
-int predict_grad_rows_per_block(const cglb_ctx* c) { return 256 * predict_grad_rows_per_lane(c->Dp); }
+int predict_grad_rows_per_block(const cglb_ctx* c) { return input_grad_mid_on(c) ? predict_grad_mid_rows_per_block(c) : 256 * predict_grad_rows_per_lane(c->Dp); }
 
 template <int KIND, int DP, bool HAS_U, bool HAS_W>
 static int weighted_grad_pairs(cglb_ctx* c, const double* XhRow, int64_t nrows, const double* Ph, int64_t npts, const double* u, const double* Wt, int64_t ldw,
@@ -160,14 +161,16 @@ static int weighted_grad_pairs(cglb_ctx* c, const double* XhRow, int64_t nrows, 
 
 // XhRow [nrows][Dp] and Ph [npts][Dp]: the two point sets in hot units at the lengthscales ls (host, [D]); variance var.  u: dev [npts] or NULL,
 // Wt: dev [npts][ldw] or NULL (one at least).  out_* [nrows], gout_* [nrows][D]: any may be NULL.  gout_w carries the factor wscale; add_u: gout_u
-// is added to.  Rows in blocks of PREDICT_GRAD_ROWS.
+// is added to.  Rows in blocks of PREDICT_GRAD_ROWS.  On a mid-width context under "input_grad_mid" both sets are [.][Dh] and scale_dev, the device copy of
+// ks / l_k at ls, carries the gradient constants; every other wide context is refused.
 int launch_weighted_grad(cglb_ctx* c, const double* ls, double var, const double* XhRow, int64_t nrows, const double* Ph, int64_t npts, const double* u,
-                         const double* Wt, int64_t ldw, double* out_u, double* gout_u, bool add_u, double* out_w, double* gout_w, double wscale) {
-    if (c->dtype != CGLB_F64 || is_wide(c)) return cglb_fail(c, CGLB_ERR_BAD_ARG, "the row-weighted gradient product needs an fp64 context of at most 32 input dimensions");
-    if ((!u && !Wt) || npts < 1 || (Wt && ldw < nrows) || (!u && (out_u || gout_u)) || (!Wt && (out_w || gout_w)))
+                         const double* Wt, int64_t ldw, double* out_u, double* gout_u, bool add_u, double* out_w, double* gout_w, double wscale, const double* scale_dev) {
+    const bool mid = input_grad_mid_on(c);  // a mid-width context under "input_grad_mid": kernels_predict_grad_mid.hip, block by block
+    if (c->dtype != CGLB_F64 || (is_wide(c) && !mid)) return cglb_fail(c, CGLB_ERR_BAD_ARG, "the row-weighted gradient product needs an fp64 context of at most 32 input dimensions");
+    if ((!u && !Wt) || npts < 1 || (Wt && ldw < nrows) || (!u && (out_u || gout_u)) || (!Wt && (out_w || gout_w)) || (mid && !scale_dev))
         return cglb_fail(c, CGLB_ERR_BAD_ARG, "bad weights, leading dimension or outputs of the row-weighted gradient product");
     if (nrows == 0) return CGLB_OK;
-    const RowSlabGradScale gs = row_slab_cross_grad_scale(c, ls, var);
+    const RowSlabGradScale gs = mid ? RowSlabGradScale() : row_slab_cross_grad_scale(c, ls, var);
     const int nw = (u ? 1 : 0) + (Wt ? 1 : 0);
     const int R = predict_grad_rows_per_lane(c->Dp);
     for (int k = 0; k < 2; ++k)
@@ -176,6 +179,11 @@ int launch_weighted_grad(cglb_ctx* c, const double* ls, double var, const double
     HIP_CHECK(c, hipEventRecord(c->pg_ev[0], c->stream));
     for (int64_t i0 = 0; i0 < nrows; i0 += PREDICT_GRAD_ROWS) {
         const int64_t nr = std::min<int64_t>(PREDICT_GRAD_ROWS, nrows - i0);
+        if (mid) {
+            CGLB_TRY(launch_weighted_grad_mid(c, scale_dev, var, XhRow + i0 * c->Dh, nr, Ph, npts, u, Wt ? Wt + i0 : nullptr, ldw, out_u ? out_u + i0 : nullptr,
+                                              gout_u ? gout_u + i0 * c->D : nullptr, add_u, out_w ? out_w + i0 : nullptr, gout_w ? gout_w + i0 * c->D : nullptr, wscale));
+            continue;
+        }
         const int64_t bx = (nr + 256 * R - 1) / (256 * R);
         // capped by the slab of the two-weight instance whatever nw is.  even = false: this product never rounded its chunk to an even length as the
         // other pair kernels do; no reason is on record, kept as measured and tested

@@ -1,0 +1,3 @@
+// Matern-3/2 instances of the mid-width row-weighted gradient product: compiled in parallel with the other kinds
+#define CGLB_PREDICT_GRAD_MID_M32
+#include "kernels_predict_grad_mid.hip"

@@ -37,6 +37,9 @@ static constexpr int input_grad_group_width(int dp) { return dp <= 8 ? 8 : (dp <
 // (2 + G) HD + G row-resident doubles per lane (coordinates, differences, G x HD gradient sums, G values): 76, 100, 82, 98.  256 / SPLIT rows per workgroup
 static constexpr int input_grad_mid_split(int dh) { return dh > 0 ? 4 : 0; }
 static constexpr int input_grad_mid_group(int dh) { return dh <= 64 ? 4 : 2; }
+// The row-weighted product at mid widths (kernels_predict_grad_mid.hip; mirrored by tests/predict_grad_mid_ref.py): the same sharing of a new point, two
+// weight slots at every width: (2 + NW) HD + NW + 2 row-resident doubles per lane (the current and the next weight besides): 52, 68, 84, 100 at NW = 2
+static constexpr int predict_grad_mid_split(int dh) { return input_grad_mid_split(dh); }
 
 // ---- device pieces ----
 // row k of the lane whose first row is rbase; rows past the end read the last row (and store nothing: row_slab_store)

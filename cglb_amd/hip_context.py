@@ -510,7 +510,8 @@ class HipContext:
         _lib.check(rc, self._ctx)
         return mean, dmean, var, dvar
 
-    # -- input gradients of the CGLB / SGPR / exact-GP predictive (cglb_cross_grad_weighted, cglb_predict_grad, cglb_gpr_predict_grad) ----
+    # -- input gradients of the CGLB / SGPR / exact-GP predictive (cglb_cross_grad_weighted, cglb_predict_grad, cglb_gpr_predict_grad): up to 32 input
+    #    dimensions; set_option("input_grad_mid", 1) opens them at 33 to 96 (fp64, wide_reg on; get_stat("predict_grad_native") tells) ----
     def cross_grad_weighted(self, xnew, u=None, Wt=None, point_set="train", out_u=None, gout_u=None, out_w=None, gout_w=None,
                             with_value=True, with_grad=True):
         """Row-weighted value and input gradient of the cross product against the training inputs (point_set "train") or the inducing points

@@ -375,7 +375,8 @@ int cglb_itergp_sample(cglb_ctx* ctx, const void* xnew, int64_t n_new, const voi
  * "wide_reg" is on (the default): the same contracts, a new point shared by four lanes, 4 columns per group up to d = 64 and 2 beyond, 64 new points
  * per workgroup.  The option defaults to 0, where behaviour, messages and results are unchanged; on a narrow context it changes nothing.  The
  * statistic "input_grad_native" is 1 where the next call would run a register-resident instance (narrow or mid), 0 where it would be refused.
- * Not covered: fp32, N ranks, d > 96, "wide_reg" 0.  The gpr / cglb / sgpr predictors have their own entries further down (cglb_predict_grad, cglb_gpr_predict_grad).
+ * Not covered: fp32, N ranks, d > 96, "wide_reg" 0.  The gpr / cglb / sgpr predictors have their own entries further down (cglb_predict_grad, cglb_gpr_predict_grad),
+ * under the same option.
  *
  * Value and input gradient of K_*f V in one pass over the pairs:
  *   out [i, s]    =  variance sum_j kappa(x*_i, x_j) V[s, j]
@@ -407,9 +408,12 @@ int cglb_time_feature_grad_matmat(cglb_ctx* ctx, int64_t n_rows, int64_t F, int 
  * Galerkin upper bound f - |R^T k_*|^2), not of the exact variance.  The stored alpha and the variance cache stay valid. */
 int cglb_itergp_predict_grad(cglb_ctx* ctx, const void* xnew, int64_t n_new, double max_error, int max_cg_iter, void* f_mean, void* g_mean, void* f_var,
                              void* g_var);
-/* ---- input gradients of the CGLB, SGPR and exact-GP predictive (csrc/kernels_predict_grad.hip) ----
- * Gradients with respect to the RAW coordinates of the new point, as above.  Not covered: fp32, N ranks, wide inputs (d > 32), more than one
- * target column; CGLB_ERR_BAD_ARG with a message.
+/* ---- input gradients of the CGLB, SGPR and exact-GP predictive (csrc/kernels_predict_grad.hip, csrc/kernels_predict_grad_mid.hip) ----
+ * Gradients with respect to the RAW coordinates of the new point, as above.  d <= 32; OPT-IN beyond, as above: cglb_set_option(ctx,
+ * "input_grad_mid", 1) opens the four entries below at 33 <= d <= 96 on a context whose option "wide_reg" is on - the same contracts, the
+ * row-weighted kernel with a new point shared by four lanes, 64 new points per workgroup; without the option such a context is refused ("... no wide
+ * path yet ...").  "predict_grad_native" (cglb_get_stat) is 1 where the next cglb_predict_grad would run, 0 where it would be refused.
+ * Not covered: fp32, N ranks, d > 96, "wide_reg" 0, more than one target column; CGLB_ERR_BAD_ARG with a message.
  *
  * Row-weighted value and input gradient of a cross product, one pass over the pairs for up to two weights:
  *   out_u[i] =  variance sum_m u[m]     kappa(x*_i, p_m)     gout_u[i, k] = -variance sum_m u[m]     h(x*_i, p_m) (x*_ik - p_mk) / l_k^2
@@ -419,7 +423,8 @@ int cglb_itergp_predict_grad(cglb_ctx* ctx, const void* xnew, int64_t n_new, dou
  * columns [n_new, ldw) hold never reaches an output); at least one of the two.  out_*: dev [n_new]; gout_*: dev [n_new, d], k fastest; the outputs
  * of an absent weight must be NULL, any output of a present one may be.  Pairs from direct differences, always the range-clamped 2^x, as
  * cglb_cross_grad_matmat: a coincident pair adds exactly zero to the gradient.  No atomics: bitwise reproducible, and every output is bitwise the
- * same whichever of the others are requested.  Scope: a context with hyper-parameters set (cglb_set_hypers), fp64, one rank, d <= 32.
+ * same whichever of the others are requested.  Scope: a context with hyper-parameters set (cglb_set_hypers), fp64, one rank, d <= 32 (33 ... 96 under
+ * "input_grad_mid"; the inducing points in the kernel's units at that width are staged on the first call after cglb_set_hypers that needs them).
  * "predict_grad_kernel_ms" (cglb_get_stat): device time of the pair kernel and slab sums of the last product. */
 int cglb_cross_grad_weighted(cglb_ctx* ctx, int set, const void* xnew, int64_t n_new, const void* u, const void* Wt, int64_t ldw, void* out_u, void* gout_u,
                              void* out_w, void* gout_w);
@@ -430,12 +435,13 @@ int cglb_cross_grad_weighted(cglb_ctx* ctx, int set, const void* xnew, int64_t n
  *   g_var [i, k] = -2 sum_m C^T[m, i] dk(x*_i, z_m)/dx*_k,                 C^T = L^-T (tmp1 - LB^-T tmp2)   (f_var = variance - sum_m C^T[m, i] k(x*_i, z_m))
  * grad (K_*f v) is cglb_cross_grad_matmat's product with v as its single column (quad_term 1: skipped, v is not read); the sums over m are ONE launch
  * of the row-weighted kernel against Z.  Scope: that of cglb_predict (quad_term 0 and 1, every logdet_bound) in fp64, on one rank, with one
- * target column and d <= 32.  v, the common terms and every cached state are left as they are. */
+ * target column and d <= 32 (33 ... 96 under "input_grad_mid").  v, the common terms and every cached state are left as they are. */
 int cglb_predict_grad(cglb_ctx* ctx, const void* v_full, const void* xnew, int64_t n_new, void* f_mean, void* g_mean, void* f_var, void* g_var);
 /* cglb_gpr_predict with the input gradients of both outputs, in its batches.  f_mean, f_var are bitwise those of cglb_gpr_predict (the same gemv,
  * trsm and column-norm calls).  g_mean = sum_j alpha_j dk_ij, g_var = -2 sum_j C[j, i] dk_ij with C = K^-1 K_f* from one further trsm on the
  * panel, transposed to [n_total][ld]: one launch of the row-weighted kernel against X per batch.  X and each batch are staged in the kernel's units
- * at the class's own lengthscales.  The extra 8 n_total (batch + d_p) bytes are checked against the free device memory first.  d <= 32. */
+ * at the class's own lengthscales.  The extra 8 n_total (batch + d_p) bytes are checked against the free device memory first.  d <= 32 (33 ... 96
+ * under "input_grad_mid": d_p is the hot width 48, 64, 80 or 96 there). */
 int cglb_gpr_predict_grad(cglb_ctx* ctx, const void* xnew, int64_t n_new, void* f_mean, void* g_mean, void* f_var, void* g_var);
 /* average duration (ms) of `reps` back-to-back cglb_predict (with_grad 0) or cglb_predict_grad (with_grad 1) calls at the first n_new training rows
  * as new points (n_new <= n_total) and v = 0, HIP events on the context stream */
@@ -496,6 +502,8 @@ int cglb_time_kernel(cglb_ctx* ctx, int which, int reps, double* ms_avg);
  * it runs one single pass per pair and takes the kappa sums from one product;
  * "input_grad_native": 1 if the next input-gradient call on this context in its current state - dtype, width, "wide_reg", "input_grad_mid" - runs a
  * register-resident instance (fp64 up to 32 dimensions; 33 ... 96 under "input_grad_mid"), 0 if it is refused;
+ * "predict_grad_native": 1 if the next cglb_predict_grad on this context in its current state - dtype, ranks, target columns, width, "wide_reg",
+ * "input_grad_mid" - runs (fp64, one rank, one target column, up to 32 dimensions; 33 ... 96 under "input_grad_mid"), 0 if it is refused;
  * "exp_clamp" | "m32_bias": the exponent-range regime the last cglb_set_hypers chose from the data's per-column range and the lengthscales
  * (CGLB_ERR_STATE before one) - 1 if the pair kernels run their range-clamped instances (kernel values below 2^-1000 come out as that floor,
  * not 0), 0 for the unclamped ones | the positivity bias of the Matern squared distance in hot units^2 (0 for RBF; above 2e-8 the clamped
@@ -544,8 +552,10 @@ int cglb_get_stat(cglb_ctx* ctx, const char* name, double* value);
  * "grad_multi_mid" (inputs of 33 ... 96 dimensions, fp64, "wide_reg" 1: 1, default - the multi-pair gradient pass evaluates every kernel value
  *  once per group of up to 8 vector pairs; 0 - one single pass per pair and one product for the kappa sums, what every other wide context runs;
  *  for A/B timing and tests; a single pair takes the single pass either way) |
- * "input_grad_mid" (inputs of 33 ... 96 dimensions, fp64, "wide_reg" 1: 0, default - the input-gradient entries refuse the context ("no wide path
- *  yet"); 1 - they run through csrc/kernels_input_grad_mid.hip; no effect on any other width or entry) |
+ * "input_grad_mid" (inputs of 33 ... 96 dimensions, fp64, "wide_reg" 1: 0, default - every input-gradient entry refuses the context ("no wide path
+ *  yet"); 1 - every input-gradient product runs at that width: the iterative class's two through csrc/kernels_input_grad_mid.hip, the row-weighted
+ *  one of cglb_cross_grad_weighted, cglb_predict_grad and cglb_gpr_predict_grad through csrc/kernels_predict_grad_mid.hip; no effect on any other
+ *  width or entry) |
  * "drop_weighted_operand" (any value: forget the pre-weighted copy cglb_vec_update_p_seg made of its p - for callers that modify p before the next mat-vec) |
  * "logdet_bound" (the log-det term of the bound; cglb_logdet, cglb_objective_and_grad and its gradient follow it.  e = y - mu, s = noise,
  *  f = variance, A = L^-1 K_uf / sqrt(s), B = I + A A^T = LB LB^T, C = LB^-1 A, t = N f / s - tr A A^T:

@@ -9,7 +9,11 @@ value call, from the medians; `bar` = d + 1, the predictor calls that one-sided 
 `below_bar` = ratio < bar.  `kernel_ms`: device time of the row-weighted pair kernel and its slab sums inside one gradient call
 ("predict_grad_kernel_ms").
 
-    python tools/time_predict_grad.py [--reps 5] [--rounds 7] [--out profiles/predict_grad_timing.json]"""
+`--mid` times the mid-width path instead (option "input_grad_mid", profiles/predict_grad_mid_timing.json): cglb_predict_grad at N = 50 000, D = 77 and
+90, M = 1024, Matern-3/2 and RBF; cglb_gpr_predict_grad at N = 16 384, D = 77; lengthscales sqrt(D) on standard-normal inputs (kernel values of order 0.1;
+the instruction stream does not depend on them).  The same clocks, the same alternation, the same bar d + 1.
+
+    python tools/time_predict_grad.py [--mid] [--reps 5] [--rounds 7] [--out profiles/predict_grad_timing.json]"""
 import argparse
 import json
 import os
@@ -26,6 +30,9 @@ from cglb_amd.hip_context import HipContext
 
 SPARSE_SHAPES = ((100000, 8, 1024), (60000, 20, 1024))
 GPR_SHAPE = (16384, 8)
+MID_SPARSE_SHAPES = ((50000, 77, 1024), (50000, 90, 1024))
+MID_KINDS = ("matern32", "rbf")
+MID_GPR_SHAPE = (16384, 77)
 N_NEW = 4096
 
 
@@ -64,39 +71,57 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--rounds", type=int, default=7)
-    ap.add_argument("--out", default=os.path.join("profiles", "predict_grad_timing.json"))
+    ap.add_argument("--mid", action="store_true", help="the mid-width path (33 - 96 input dimensions, option input_grad_mid)")
+    ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    if a.out is None:
+        a.out = os.path.join("profiles", "predict_grad_mid_timing.json" if a.mid else "predict_grad_timing.json")
     out = dict(dtype="fp64", kind="matern32", n_new=N_NEW, reps=a.reps, rounds=a.rounds, device=torch.cuda.get_device_name(0), shapes={})
+    if a.mid:
+        out["kind"] = "per shape"
 
     def save():
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
         with open(a.out, "w") as fh:
             json.dump(out, fh, indent=1)
 
-    for n, d, m in SPARSE_SHAPES:
-        X, y, Z = synthetic_problem(n, d, m, seed=0)
+    def hypers(d):
         hyp = trained_like_hypers(d)
-        ctx = HipContext(X, y, m, "matern32")
-        ctx.set_hypers(hyp["lengthscales"], hyp["variance"], hyp["noise"], hyp["mean"], Z)
-        ctx.setup()
-        r = compare(lambda: ctx.time_predict_grad(N_NEW, True, a.reps), lambda: ctx.time_predict_grad(N_NEW, False, a.reps), a.rounds, d)
-        ctx.time_predict_grad(N_NEW, True, 1)
-        r["kernel_ms"] = ctx.get_stat("predict_grad_kernel_ms")
-        out["shapes"][f"cglb_N{n}_D{d}_M{m}"] = r
-        report(f"cglb_predict_grad N={n} D={d} M={m}", r)
-        save()
-        ctx.close()
-    n, d = GPR_SHAPE
+        if a.mid:
+            hyp["lengthscales"] = [float(d) ** 0.5] * d
+        return hyp
+
+    for n, d, m in (MID_SPARSE_SHAPES if a.mid else SPARSE_SHAPES):
+        X, y, Z = synthetic_problem(n, d, m, seed=0)
+        hyp = hypers(d)
+        for kind in (MID_KINDS if a.mid else ("matern32",)):
+            ctx = HipContext(X, y, m, kind)
+            if a.mid:
+                ctx.set_option("input_grad_mid", 1)
+                assert ctx.get_stat("predict_grad_native") == 1.0
+            ctx.set_hypers(hyp["lengthscales"], hyp["variance"], hyp["noise"], hyp["mean"], Z)
+            ctx.setup()
+            r = compare(lambda: ctx.time_predict_grad(N_NEW, True, a.reps), lambda: ctx.time_predict_grad(N_NEW, False, a.reps), a.rounds, d)
+            ctx.time_predict_grad(N_NEW, True, 1)
+            r["kernel_ms"] = ctx.get_stat("predict_grad_kernel_ms")
+            name = f"cglb_N{n}_D{d}_M{m}" + (f"_{kind}" if a.mid else "")
+            out["shapes"][name] = r
+            report(f"cglb_predict_grad N={n} D={d} M={m} {kind}", r)
+            save()
+            ctx.close()
+    n, d = MID_GPR_SHAPE if a.mid else GPR_SHAPE
     X, y, _ = synthetic_problem(n, d, 1, seed=0)
-    hyp = trained_like_hypers(d)
+    hyp = hypers(d)
     ctx = HipContext(X, y, 1, "matern32")
+    if a.mid:
+        ctx.set_option("input_grad_mid", 1)
     ctx.gpr_set_hypers(hyp["lengthscales"], hyp["variance"], hyp["noise"], hyp["mean"])
     xs = torch.as_tensor(X[:N_NEW], dtype=torch.float64, device=ctx.device)
     ctx.gpr_predict(xs)   # factors
     r = compare(lambda: host_timed(lambda: ctx.gpr_predict_grad(xs), a.reps), lambda: host_timed(lambda: ctx.gpr_predict(xs), a.reps), a.rounds, d)
     ctx.gpr_predict_grad(xs)
     r["kernel_ms"] = ctx.get_stat("predict_grad_kernel_ms")
-    out["shapes"][f"gpr_N{n}_D{d}"] = r
+    out["shapes"][f"gpr_N{n}_D{d}" + ("_matern32" if a.mid else "")] = r
     report(f"cglb_gpr_predict_grad N={n} D={d}", r)
     save()
     ctx.close()
