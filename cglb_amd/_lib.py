@@ -127,6 +127,13 @@ SIGNATURES = {
     "cglb_itergp_paths_eval": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p]),
     "cglb_grad_kff_multi": (c_int, [c_void_p, c_void_p, c_void_p, c_int, POINTER(c_double)]),
     "cglb_time_grad_kff_multi": (c_int, [c_void_p, c_int, c_int, POINTER(c_double)]),
+    # gradients with respect to the training inputs (csrc/kernels_train_input_grad.hip)
+    "cglb_grad_x_kff_multi": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
+    "cglb_time_grad_x_kff_multi": (c_int, [c_void_p, c_int, c_int, POINTER(c_double)]),
+    "cglb_itergp_objective_and_grad_x": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_double, c_int, c_int, POINTER(c_double), POINTER(c_double),
+                                                 POINTER(c_int), POINTER(c_double), c_void_p]),
+    "cglb_gpr_objective_and_grad_x": (c_int, [c_void_p, POINTER(c_double), POINTER(c_double), c_void_p]),
+    "cglb_set_inputs": (c_int, [c_void_p, c_void_p]),
 }
 
 _lib = None

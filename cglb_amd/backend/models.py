@@ -330,6 +330,21 @@ class _NoInducingGPR(GPR):
                 self.mean_module.constant.reshape(()))
 
 
+    def set_train_inputs(self, x) -> None:
+        """Replaces the training inputs ([N, d], any device; the targets stay): the model's `train_inputs`, the remembered pair of `check_same_data`
+        and the library's copy.  The library forgets its hyper-parameters with the inputs (its scaled operand sets are made from both), so whatever
+        the class remembers as pushed is void; a warm start (`v_vec`) is kept."""
+        x = torch.as_tensor(x).detach()
+        x = x.reshape(x.shape[0], -1)
+        if tuple(x.shape) != tuple(self.train_inputs[0].shape):
+            raise ValueError(f"set_train_inputs was given inputs of shape {tuple(x.shape)} but the model holds {tuple(self.train_inputs[0].shape)}")
+        self.train_inputs = (x,)
+        self._accepted_data = None
+        if hasattr(self, "_pushed"):   # IterGPR: the key of the last set_hypers
+            self._pushed = None
+        self.hip.set_inputs(x)
+
+
 class ExactGPR(_NoInducingGPR):
     """Exact GP regression (GPRConfig: tensorflow/interface.py:200-206 builds gpflow's GPR with a constant mean; pytorch/interface.py:561-604
     trains it on ExactMarginalLogLikelihood times n).  The N x N kernel matrix is factored on the GPU (cglb_gpr_*: fp64, one rank, one
@@ -588,6 +603,84 @@ class StochasticLogMarginalLikelihood(_Objective):
         model.last_bound = float(res.lml)
         model.cg_stats = ConjugateGradientStats(steps=res.steps, residual_error=res.residual_error)
         return res.lml, res.grad, None
+
+
+class _InputEvaluation(torch.autograd.Function):
+    """value(x, *hypers) with the analytic gradients from the GPU: `_Evaluation` with the training inputs as one more differentiable argument.
+    `evaluate(x, need_x, needs)` sets the model's inputs, makes the library call and returns (value, gradient dict or None, gx or None)."""
+
+    @staticmethod
+    def forward(ctx, evaluate, x, *inputs):
+        value, ctx.grads, ctx.gx = evaluate(x, ctx.needs_input_grad[1], ctx.needs_input_grad[2:])
+        ctx.x_like = (x.shape, x.dtype, x.device)
+        return torch.tensor(value, dtype=torch.float64)
+
+    @staticmethod
+    def backward(ctx, gout):
+        g = ctx.grads
+        if g is None:
+            raise RuntimeError("gradient was not requested in forward")
+        gout = gout.to(torch.float64)
+        shape, dtype, device = ctx.x_like
+        gx = None if ctx.gx is None else (gout.to(ctx.gx.device) * ctx.gx).reshape(shape).to(device=device, dtype=dtype)
+        grads = [gout * (torch.from_numpy(g[key]) if key == "lengthscales" else g[key]) for key in ("lengthscales", "variance", "noise", "mean")]
+        return (None, gx, *grads)
+
+
+class _InputGradObjective(nn.Module):
+    """`Objective(model)(x)`: the model class's training objective as a function of the training INPUTS as well - what a learned feature map in
+    front of the kernel (deep kernel learning, input warping, latent inputs) back-propagates through.  `x` [N, d] on any device replaces the
+    model's training inputs (`set_train_inputs`), the hyper-parameters are pushed, and one evaluation returns the scalar; its backward delivers
+    the hyper-parameter gradients as the plain objective does, plus d value / d x to `x`, computed only when `x` requires grad."""
+
+    MODEL: type = GPR
+    EXPECTED = "GPR"
+
+    def __init__(self, model):
+        if not isinstance(model, self.MODEL):
+            raise ValueError(f"{self.EXPECTED} model expected in the constructor of the {self.__class__}")
+        super().__init__()
+        object.__setattr__(self, "model", model)  # not a sub-module: parameters stay owned by the model
+
+    def evaluate(self, x, need_x, needs):
+        raise NotImplementedError()
+
+    def forward(self, x: Tensor) -> Tensor:
+        return _InputEvaluation.apply(self.evaluate, x, *self.model.hyper_tensors())
+
+
+class InputGradLogMarginalLikelihood(_InputGradObjective):
+    """`InputGradLogMarginalLikelihood(model)(x)`: the exact log marginal likelihood of an ExactGPR model at the training inputs `x`, differentiable
+    in `x` and the hyper-parameters (fp64, one target column, up to 32 input dimensions)."""
+
+    MODEL, EXPECTED = ExactGPR, "ExactGPR"
+
+    def evaluate(self, x, need_x, needs):
+        model = self.model
+        model.set_train_inputs(x)
+        model.push_hypers()
+        res = model.hip.gpr_objective_and_grad(with_grad=need_x or any(needs), with_input_grad=need_x)
+        model.last_bound = float(res.lml)
+        return res.lml, res.grad, res.grad_x
+
+
+class InputGradStochasticLogMarginalLikelihood(_InputGradObjective):
+    """`InputGradStochasticLogMarginalLikelihood(model)(x)`: the iterative estimate of the log marginal likelihood of an IterGPR model at the
+    training inputs `x`, with the library's unbiased gradient estimate with respect to the hyper-parameters AND `x`.  As for
+    StochasticLogMarginalLikelihood, the backward is NOT the derivative of the forward value (the log-determinant estimate and its gradient use
+    the same probes in different estimators): it is the estimator's gradient, in `x` as in the hyper-parameters.  `v_vec` stays as the warm start."""
+
+    MODEL, EXPECTED = IterGPR, "IterGPR"
+
+    def evaluate(self, x, need_x, needs):
+        model = self.model
+        model.set_train_inputs(x)
+        model.push_hypers(get_cholesky_jitter())
+        res = model.hip.itergp_objective_and_grad(model.probes(), model.v_vec, model.max_error, model.max_cg_iter, model.lanczos_iter,
+                                                  with_grad=need_x or any(needs), with_input_grad=need_x)
+        model.last_bound = float(res.lml)
+        model.cg_stats = ConjugateGradientStats(steps=res.steps, residual_error=res.residual_error)
+        return res.lml, res.grad, res.grad_x
 
 
 def _refuse_full_cov(full_cov: bool):

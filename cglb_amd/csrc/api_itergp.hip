@@ -335,6 +335,19 @@ int input_grad_rows(cglb_ctx* c, StagedPoints& pts, const void** rows) {
     return CGLB_OK;
 }
 
+// cglb_grad_x_kff_multi, its timer, cglb_itergp_objective_and_grad_x: fp64, one rank, one target column, at most 32 input dimensions
+// (kernels_train_input_grad.hip)
+int require_train_input_grad_ok(cglb_ctx* c) {
+    CGLB_TRY(require_multi_ok(c));
+    if (c->dtype != CGLB_F64) return cglb_fail(c, CGLB_ERR_BAD_ARG, "the training-input gradient needs an fp64 context (-t fp64): it has no fp32 path yet");
+    if (c->p != 1) return cglb_fail(c, CGLB_ERR_BAD_ARG, "the training-input gradient takes one target column");
+    if (is_wide(c))
+        return cglb_fail(c, CGLB_ERR_BAD_ARG, "the training-input gradient has no wide path yet: it is available up to 32 input dimensions");
+    if (!train_input_grad_native(c)) return cglb_fail(c, CGLB_ERR_BAD_ARG, "the training-input gradient needs a single shard covering all rows on one rank");
+    if (!c->have_data || !c->have_hypers) return cglb_fail(c, CGLB_ERR_STATE, "set_data and set_hypers must precede the training-input gradient");
+    return CGLB_OK;
+}
+
 // ---- what the value entries and their input-gradient twins share ----
 // the columns of the variance cache rounded up to the group width of the cross product
 int cache_cols_padded(const cglb_ctx* c) {
@@ -419,11 +432,14 @@ int itergp_stat(cglb_ctx* c, const char* name, double* value) {
 extern "C" {
 
 // ---- iterative exact GP (include/cglb_hip.h) -----------------------------------------------------------------------------
-int cglb_itergp_objective_and_grad(cglb_ctx* c, const void* eps, int t, void* v_inout, double max_error, int max_cg_iter, int lanczos_iter, double* out4,
-                                   double* grad, int* steps, double* half_rz) {
+// the one implementation of cglb_itergp_objective_and_grad (gx_out NULL) and cglb_itergp_objective_and_grad_x: gx_out, dev [N][D], comes from one
+// further pass over the vectors of the kernel gradient, inside the "itergp_grad_ms" bracket; nothing else of the evaluation knows of it
+static int itergp_objective(cglb_ctx* c, const void* eps, int t, void* v_inout, double max_error, int max_cg_iter, int lanczos_iter, double* out4, double* grad,
+                            int* steps, double* half_rz, void* gx_out) {
     if (c) c->obj_valid = false;
     if (!c || !eps || !v_inout || !out4 || t < 1 || max_cg_iter < 0 || lanczos_iter < 0) return c ? cglb_fail(c, CGLB_ERR_BAD_ARG, "bad argument") : CGLB_ERR_BAD_ARG;
     CGLB_TRY(require_itergp_ok(c));
+    if (gx_out) CGLB_TRY(require_train_input_grad_ok(c));
     HIP_CHECK(c, hipSetDevice(c->device));
     c->it_valid = false;
     c->it_ev_last = 0;
@@ -474,6 +490,7 @@ int cglb_itergp_objective_and_grad(cglb_ctx* c, const void* eps, int t, void* v_
         CGLB_TRY(launch_dot(c, w.p, w.z, N, sc + D + 1, s));
         hipLaunchKernelGGL(vec_sum_kernel, dim3(1), dim3(256), 0, c->stream, (const double*)c->it_V, N, sc + D + 2 + s);
         CGLB_LAUNCH_CHECK(c);
+        if (gx_out) CGLB_TRY(launch_grad_x_kff_multi(c, w.p, w.z, s, (double*)gx_out));  // the same pairs, differentiated in x_i
         CGLB_TRY(itergp_mark(c, 3));
     }
     std::vector<double> host((size_t)nsc);
@@ -501,6 +518,17 @@ int cglb_itergp_objective_and_grad(cglb_ctx* c, const void* eps, int t, void* v_
     c->it_t = t;
     c->it_valid = true;
     return CGLB_OK;
+}
+
+int cglb_itergp_objective_and_grad(cglb_ctx* c, const void* eps, int t, void* v_inout, double max_error, int max_cg_iter, int lanczos_iter, double* out4,
+                                   double* grad, int* steps, double* half_rz) {
+    return itergp_objective(c, eps, t, v_inout, max_error, max_cg_iter, lanczos_iter, out4, grad, steps, half_rz, nullptr);
+}
+
+int cglb_itergp_objective_and_grad_x(cglb_ctx* c, const void* eps, int t, void* v_inout, double max_error, int max_cg_iter, int lanczos_iter, double* out4,
+                                     double* grad, int* steps, double* half_rz, void* gx_out) {
+    if (c && (!grad || !gx_out)) return cglb_fail(c, CGLB_ERR_BAD_ARG, "the training-input gradient comes with the hyper-parameter gradient: grad and gx_out must be set");
+    return itergp_objective(c, eps, t, v_inout, max_error, max_cg_iter, lanczos_iter, out4, grad, steps, half_rz, gx_out);
 }
 
 int cglb_itergp_get_coefficients(cglb_ctx* c, double* rz_log, double* pap_log) {
@@ -873,6 +901,32 @@ int cglb_grad_kff_multi(cglb_ctx* c, const void* U, const void* V, int S, double
     CGLB_TRY(c->mem.reserve(c, &c->it_scal, &c->it_scal_cap, (size_t)(c->D + 1) * sizeof(double)));
     CGLB_TRY(launch_grad_kff_multi(c, U, V, S, c->it_scal));
     return read_scalars(c, c->it_scal, out, c->D + 1);
+}
+
+int cglb_grad_x_kff_multi(cglb_ctx* c, const void* U, const void* V, int S, void* gx_out) {
+    if (c) c->obj_valid = false;
+    if (!c || !U || !V || !gx_out || S < 1) return c ? cglb_fail(c, CGLB_ERR_BAD_ARG, "bad argument") : CGLB_ERR_BAD_ARG;
+    CGLB_TRY(require_train_input_grad_ok(c));
+    HIP_CHECK(c, hipSetDevice(c->device));
+    CGLB_TRY(launch_grad_x_kff_multi(c, U, V, S, (double*)gx_out));
+    HIP_CHECK(c, hipStreamSynchronize(c->stream));
+    return CGLB_OK;
+}
+
+int cglb_time_grad_x_kff_multi(cglb_ctx* c, int S, int reps, double* ms_avg) {
+    if (c) c->obj_valid = false;
+    if (!c || !ms_avg || reps <= 0 || S < 1) return c ? cglb_fail(c, CGLB_ERR_BAD_ARG, "bad argument") : CGLB_ERR_BAD_ARG;
+    CGLB_TRY(require_train_input_grad_ok(c));
+    HIP_CHECK(c, hipSetDevice(c->device));
+    multi_work w;
+    CGLB_TRY(multi_reserve(c, S, &w));
+    void* gx = nullptr;
+    DevTemps tmp;
+    CGLB_TRY(tmp.alloc(c, &gx, (size_t)c->N * c->D * sizeof(double)));
+    CGLB_TRY(fill_y_columns(c, w.p, S));  // operands: S copies of y on both sides, as cglb_time_grad_kff_multi
+    const int rc = time_repeated(c, reps, [&]() -> int { return launch_grad_x_kff_multi(c, w.p, w.p, S, (double*)gx); }, ms_avg);
+    (void)hipStreamSynchronize(c->stream);  // before `tmp` frees
+    return rc;
 }
 
 int cglb_time_grad_kff_multi(cglb_ctx* c, int S, int reps, double* ms_avg) {

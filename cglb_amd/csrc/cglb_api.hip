@@ -1185,6 +1185,45 @@ int cglb_set_data(cglb_ctx* c, const void* X, const void* y) {
     return CGLB_OK;
 }
 
+// New training inputs under the targets the context holds.  Everything cglb_set_data invalidates, and both hyper-parameter flags: the scaled and hot
+// operand sets are made from X by cglb_set_hypers, so an evaluation without a new push would run on the old ones
+int cglb_set_inputs(cglb_ctx* c, const void* X) {
+    if (c) c->obj_valid = false;
+    if (!c || !X) return c ? cglb_fail(c, CGLB_ERR_BAD_ARG, "NULL argument") : CGLB_ERR_BAD_ARG;
+    if (!c->have_data) return cglb_fail(c, CGLB_ERR_STATE, "set_data must precede set_inputs: the targets are kept");
+    HIP_CHECK(c, hipSetDevice(c->device));
+    const size_t nx = (size_t)c->N * c->D;
+    HIP_CHECK(c, hipMemcpyAsync(c->X, X, nx * c->esz, hipMemcpyDefault, c->stream));
+    // centre, ranges and radius as cglb_set_data forms them
+    std::vector<char> host(nx * c->esz);
+    HIP_CHECK(c, hipMemcpyAsync(host.data(), c->X, nx * c->esz, hipMemcpyDeviceToHost, c->stream));
+    HIP_CHECK(c, hipStreamSynchronize(c->stream));
+    auto at = [&](int64_t i, int d) { return c->dtype == CGLB_F64 ? ((const double*)host.data())[i * c->D + d] : (double)((const float*)host.data())[i * c->D + d]; };
+    for (int d = 0; d < c->D; ++d) c->xmean[d] = 0.0;
+    for (int64_t i = 0; i < c->N; ++i)
+        for (int d = 0; d < c->D; ++d) c->xmean[d] += at(i, d);
+    for (int d = 0; d < c->D; ++d) c->xmean[d] /= (double)c->N;
+    for (int d = 0; d < c->D; ++d) c->xrange[d] = 0.0;
+    c->xradius2 = 0.0;
+    for (int64_t i = 0; i < c->N; ++i) {
+        double r2 = 0.0;
+        for (int d = 0; d < c->D; ++d) {
+            const double x = at(i, d);
+            c->xrange[d] = std::fmax(c->xrange[d], std::fabs(x - c->xmean[d]));
+            r2 += (x - c->xmean[d]) * (x - c->xmean[d]);
+        }
+        c->xradius2 = std::fmax(c->xradius2, r2);
+    }
+    c->gpr_factored = false;
+    c->gpr_hot_valid = false;
+    c->it_valid = false;
+    c->it_cache_rank = c->it_cache_request = 0;
+    c->Zhm_valid = false;
+    c->have_local = c->have_terms = false;
+    c->have_hypers = c->gpr_have_hypers = false;
+    return CGLB_OK;
+}
+
 int cglb_set_hypers(cglb_ctx* c, const double* lengthscales, double variance, double noise, double mean, const void* Z, double jitter) {
     if (c) c->obj_valid = false;
     if (!c || !lengthscales || !Z) return c ? cglb_fail(c, CGLB_ERR_BAD_ARG, "NULL argument") : CGLB_ERR_BAD_ARG;
@@ -1947,6 +1986,10 @@ int cglb_get_stat(cglb_ctx* c, const char* name, double* value) {
     }
     if (!strcmp(name, "matmat_native")) { *value = (c->have_data && kff_multi_native(c)) ? 1.0 : 0.0; return CGLB_OK; }  // shared-kernel instance or single mat-vecs
     if (!strcmp(name, "grad_multi_native")) { *value = (c->have_data && grad_multi_native(c)) ? 1.0 : 0.0; return CGLB_OK; }  // multi-pair gradient instance or single passes
+    if (!strcmp(name, "train_input_grad_native")) {  // the next training-input gradient runs (fp64, one rank, one target column, at most 32 input dimensions) or is refused
+        *value = (train_input_grad_native(c) && c->p == 1) ? 1.0 : 0.0;
+        return CGLB_OK;
+    }
     if (!strcmp(name, "predict_grad_native")) {  // the next cglb_predict_grad runs (fp64, one rank, one target column; narrow, or mid under "input_grad_mid") or is refused
         *value = (c->dtype == CGLB_F64 && c->par_world == 1 && !c->comm && c->p == 1 && (!is_wide(c) || input_grad_mid_on(c))) ? 1.0 : 0.0;
         return CGLB_OK;

@@ -225,6 +225,8 @@ struct cglb_ctx {
     size_t gpr_Ks_cap = 0, gpr_xnew_cap = 0;
     double *gpr_Xh = nullptr, *gpr_xh = nullptr, *gpr_Ct = nullptr;  // input gradients: X and the batch in hot units at gpr_ls, C = K^-1 K_f* as [N][ld]
     size_t gpr_xh_cap = 0, gpr_Ct_cap = 0;
+    double* gpr_Wt = nullptr;                           // training-input gradient: a block column of alpha alpha^T - K^-1 as [N][ld]
+    size_t gpr_Wt_cap = 0;
     bool gpr_hot_valid = false;                         // gpr_Xh holds X at the current data and lengthscales
     double* gpr_cs = nullptr;                           // mid widths: device [centre (D) | ks / gpr_ls (D)], scales of gpr_Xh / gpr_xh and of their gradient constants
     size_t gpr_bytes = 0;                               // device bytes the pool holds (cglb_get_stat "gpr_bytes")
@@ -440,6 +442,13 @@ bool grad_multi_native(const cglb_ctx* c);
 int launch_grad_kff_multi(cglb_ctx* c, const void* U, const void* V, int S, double* out);
 // kernels_grad_multi_mid.hip: out (+)= the same sums of one group of 2 .. grad_multi_mid_group(Dh) pairs of a context with mid_reg(c), both exponent ranges
 int launch_grad_kff_multi_mid(cglb_ctx* c, const double* U, const double* V, int sg, double* out, int accumulate);
+// kernels_train_input_grad.hip: gx[i * D + k] = sum_j w_ij d kappa(x_i, x_j) / d x_ik, w_ij = sum_b (u_bi v_bj + v_bi u_bj), with respect to the raw training
+// inputs; U, V [S][N] as above; gx dev [N][D], overwritten.  Where !train_input_grad_native(c) (fp32, more than 32 dimensions, N ranks) it is refused.
+// Bitwise repeatable.
+bool train_input_grad_native(const cglb_ctx* c);
+int launch_grad_x_kff_multi(cglb_ctx* c, const void* U, const void* V, int S, double* gx);
+int train_input_grad_rows_per_block(const cglb_ctx* c);  // rows per workgroup at the context's width
+int train_input_grad_width(const cglb_ctx* c);           // vector pairs per group at the context's width (8 or 4)
 // The row-slab products (decomposition, chunk rules, layout constants and the shared value finish kernel: row_slab.h), one file each:
 // kernels_cross_multi.hip: out[i * ldo + s] = var * sum_j kappa(row_i, x_j) Vi[j * ldv + s], s < S; Vi dev [N][ldv] row-major (ldv a multiple of 8, zero
 // padded), rows hot-scaled; every kernel value evaluated once per group of 8 columns.  fp64, Dp <= 32.  Bitwise repeatable.

@@ -376,6 +376,67 @@ int gpr_evaluate(cglb_ctx* c, double* out3, double* grad) {
     return CGLB_OK;
 }
 
+// c->gpr_Xh <- X in the pair kernel's hot units at gpr_ls, once per evaluation (gpr_evaluate voids it); mid widths: [N][Dh] by launch_hot_points_mid with
+// the scales in the device copy gpr_cs
+int gpr_stage_training_hot(cglb_ctx* c, bool mid) {
+    const int64_t N = c->N;
+    const int D = c->D;
+    CGLB_TRY(gpr_alloc(c, &c->gpr_Xh, (size_t)N * (size_t)predict_grad_row_stride(c)));
+    if (mid) CGLB_TRY(gpr_alloc(c, &c->gpr_cs, (size_t)2 * D));
+    if (c->gpr_hot_valid) return CGLB_OK;
+    if (mid) {
+        std::vector<double> cs((size_t)2 * D);
+        for (int d = 0; d < D; ++d) { cs[d] = c->xmean[d]; cs[D + d] = cglb_kscale(c) / c->gpr_ls[d]; }
+        HIP_CHECK(c, hipMemcpyAsync(c->gpr_cs, cs.data(), cs.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
+        HIP_CHECK(c, hipStreamSynchronize(c->stream));  // `cs` is pageable host memory
+        CGLB_TRY(launch_hot_points_mid(c, c->gpr_cs, (const double*)c->X, N, c->gpr_Xh));
+    } else {
+        CGLB_TRY(launch_hot_points(c, c->gpr_ls.data(), (const double*)c->X, N, c->gpr_Xh));
+    }
+    c->gpr_hot_valid = true;
+    return CGLB_OK;
+}
+
+// Wt[m * ldw + i] = alpha_m alpha_{i0 + i} - K^-1(m, i0 + i), m < n, i < nb: the block column of the symmetrised weight of the training-input gradient, K^-1
+// read from its lower triangle (column-major, ld n)
+__global__ __launch_bounds__(256) void gpr_weight_block_kernel(const double* __restrict__ alpha, const double* __restrict__ Kinv, int64_t n, int64_t i0, int64_t nb,
+                                                               int64_t ldw, double* __restrict__ Wt) {
+    const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= n * nb) return;
+    const int64_t m = idx / nb, i = i0 + (idx - m * nb);
+    const int64_t r = m > i ? m : i, q = m > i ? i : m;
+    Wt[m * ldw + (i - i0)] = alpha[m] * alpha[i] - Kinv[r + q * n];
+}
+
+// gx[i, k] = sum_j (alpha_i alpha_j - K^-1_ij) d k(x_i, x_j) / d x_ik after an evaluation with gradients (gpr_alpha, gpr_Kinv): one row-weighted
+// gradient product (kernels_predict_grad.hip) per row block of the factorisation's block edge, rows = points = X
+int gpr_input_grad(cglb_ctx* c, double* gx) {
+    const int64_t N = c->N;
+    const int64_t nb = std::min<int64_t>(c->gpr_block, (N + 63) & ~(int64_t)63);
+    const int64_t ldw = (std::min(nb, N) + 7) & ~(int64_t)7;
+    size_t need = 0;
+    if (!c->gpr_Xh) need += (size_t)N * c->Dp * sizeof(double);
+    if (c->gpr_Wt_cap < (size_t)N * ldw * sizeof(double)) need += (size_t)N * ldw * sizeof(double);
+    if (need > 0) {
+        size_t free_b = 0, total_b = 0;
+        HIP_CHECK(c, hipMemGetInfo(&free_b, &total_b));
+        if (need > free_b)
+            return cglb_fail(c, CGLB_ERR_HIP, "the exact GPR training-input gradient at N = " + std::to_string(N) + " needs " + std::to_string(need >> 20) +
+                                                  " MiB for the weights of a row block but only " + std::to_string(free_b >> 20) + " MiB of device memory are free");
+    }
+    CGLB_TRY(gpr_reserve(c, &c->gpr_Wt, &c->gpr_Wt_cap, (size_t)N * ldw));
+    CGLB_TRY(gpr_stage_training_hot(c, false));
+    for (int64_t i0 = 0; i0 < N; i0 += nb) {
+        const int64_t nbi = std::min(nb, N - i0);
+        hipLaunchKernelGGL(gpr_weight_block_kernel, dim3((unsigned)((N * nbi + 255) / 256)), dim3(256), 0, c->stream, (const double*)c->gpr_alpha,
+                           (const double*)c->gpr_Kinv, N, i0, nbi, ldw, c->gpr_Wt);
+        CGLB_LAUNCH_CHECK(c);
+        CGLB_TRY(launch_weighted_grad(c, c->gpr_ls.data(), c->gpr_var, c->gpr_Xh + i0 * c->Dp, nbi, c->gpr_Xh, N, nullptr, c->gpr_Wt, ldw, nullptr, nullptr, false,
+                                      nullptr, gx + i0 * c->D, 1.0, nullptr));
+    }
+    return CGLB_OK;
+}
+
 // cglb_gpr_predict, and with g_mean set cglb_gpr_predict_grad (var_out / g_var NULL: the mean and its gradient alone), batch by batch
 int gpr_predict_batches(cglb_ctx* c, const void* xnew, int64_t n_new, double* mean_out, double* g_mean, double* var_out, double* g_var) {
     CGLB_TRY(gpr_require(c));
@@ -400,22 +461,9 @@ int gpr_predict_batches(cglb_ctx* c, const void* xnew, int64_t n_new, double* me
                 return cglb_fail(c, CGLB_ERR_HIP, "the exact GPR input gradients at N = " + std::to_string(N) + " need " + std::to_string(need >> 20) +
                                                       " MiB for the panels of a batch but only " + std::to_string(free_b >> 20) + " MiB of device memory are free");
         }
-        CGLB_TRY(gpr_alloc(c, &c->gpr_Xh, (size_t)N * hw));
         CGLB_TRY(gpr_reserve(c, &c->gpr_xh, &c->gpr_xh_cap, (size_t)bmax * hw));
         if (g_var) CGLB_TRY(gpr_reserve(c, &c->gpr_Ct, &c->gpr_Ct_cap, (size_t)N * ldc));
-        if (mid) CGLB_TRY(gpr_alloc(c, &c->gpr_cs, (size_t)2 * D));
-        if (!c->gpr_hot_valid) {  // once per hyper-parameter set
-            if (mid) {
-                std::vector<double> cs((size_t)2 * D);
-                for (int d = 0; d < D; ++d) { cs[d] = c->xmean[d]; cs[D + d] = cglb_kscale(c) / c->gpr_ls[d]; }
-                HIP_CHECK(c, hipMemcpyAsync(c->gpr_cs, cs.data(), cs.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
-                HIP_CHECK(c, hipStreamSynchronize(c->stream));  // `cs` is pageable host memory
-                CGLB_TRY(launch_hot_points_mid(c, c->gpr_cs, (const double*)c->X, N, c->gpr_Xh));
-            } else {
-                CGLB_TRY(launch_hot_points(c, c->gpr_ls.data(), (const double*)c->X, N, c->gpr_Xh));
-            }
-            c->gpr_hot_valid = true;
-        }
+        CGLB_TRY(gpr_stage_training_hot(c, mid));
     }
     CGLB_TRY(gpr_reserve(c, &c->gpr_Ks, &c->gpr_Ks_cap, (size_t)N * bmax));
     CGLB_TRY(gpr_reserve(c, &c->gpr_xnew, &c->gpr_xnew_cap, (size_t)2 * bmax * D));
@@ -508,6 +556,15 @@ int cglb_gpr_set_hypers(cglb_ctx* c, const double* lengthscales, double variance
 int cglb_gpr_objective_and_grad(cglb_ctx* c, double* out3, double* grad) {
     if (!c || !out3) return c ? cglb_fail(c, CGLB_ERR_BAD_ARG, "NULL argument") : CGLB_ERR_BAD_ARG;
     return gpr_evaluate(c, out3, grad);
+}
+
+int cglb_gpr_objective_and_grad_x(cglb_ctx* c, double* out3, double* grad, void* gx_out) {
+    if (!c || !out3 || !grad || !gx_out) return c ? cglb_fail(c, CGLB_ERR_BAD_ARG, "NULL argument") : CGLB_ERR_BAD_ARG;
+    CGLB_TRY(gpr_require(c));
+    if (is_wide(c))
+        return cglb_fail(c, CGLB_ERR_BAD_ARG, "the training-input gradient has no wide path yet: it is available up to 32 input dimensions");
+    CGLB_TRY(gpr_evaluate(c, out3, grad));
+    return gpr_input_grad(c, (double*)gx_out);
 }
 
 int cglb_gpr_predict(cglb_ctx* c, const void* xnew, int64_t n_new, void* f_mean, void* f_var) {

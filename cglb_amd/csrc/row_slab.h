@@ -33,6 +33,12 @@
 // (200 of the 256 VGPRs of two waves per SIMD): 2 x 8 up to width 4 (88 + 4), 1 x 8 up to 8 (80 + 8), 1 x 4 up to 16 (84 + 16), 1 x 2 beyond (98 + 32)
 static constexpr int input_grad_rows_per_lane(int dp) { return dp <= 4 ? 2 : 1; }
 static constexpr int input_grad_group_width(int dp) { return dp <= 8 ? 8 : (dp <= 16 ? 4 : 2); }
+// The pair-weighted training-input gradient (kernels_train_input_grad.hip; mirrored by tests/train_input_grad_ref.py): rows per lane and vector pairs per
+// group.  The column side is wave-uniform, 2 DP + 4 G SGPRs (x_j and the record u_.j | v_.j) of the 102 a wave has: 80 at width 32 with G = 4 (G = 8
+// would need 96 and leave none for addresses and the loop), 64 at width 16 with G = 8.  Row-resident doubles R (2 DP + 2 G) + DP (coordinates,
+// accumulators, both row-side vectors, the differences in flight): 2 x 8 up to width 8 (72 at 8), 1 x 8 up to 16 (64), 1 x 4 beyond (104 at 32)
+static constexpr int train_input_grad_rows_per_lane(int dp) { return dp <= 8 ? 2 : 1; }
+static constexpr int train_input_grad_group_width(int dp) { return dp <= 16 ? 8 : 4; }
 // Mid widths (kernels_input_grad_mid.hip, hot width dh in 48, 64, 80, 96): a new point is shared by SPLIT lanes of HD = dh / SPLIT coordinates each;
 // (2 + G) HD + G row-resident doubles per lane (coordinates, differences, G x HD gradient sums, G values): 76, 100, 82, 98.  256 / SPLIT rows per workgroup
 static constexpr int input_grad_mid_split(int dh) { return dh > 0 ? 4 : 0; }

@@ -40,6 +40,7 @@ class GPRResult:
     quad: float     # -1/2 e^T K^-1 e
     logdet: float   # -sum log diag chol(K) = -1/2 log|K|
     grad: Optional[dict]  # d lml / d {lengthscales, variance, noise, mean}
+    grad_x: Optional[torch.Tensor] = None  # d lml / d X, device [N, D] (with_input_grad)
 
 
 @dataclass
@@ -51,6 +52,7 @@ class IterGPResult:
     steps: int
     residual_error: float
     grad: Optional[dict]  # the unbiased gradient estimate {lengthscales, variance, noise, mean}: not the derivative of `lml`
+    grad_x: Optional[torch.Tensor] = None  # the same estimator's gradient with respect to the training inputs, device [N, D] (with_input_grad)
 
 
 @dataclass
@@ -321,12 +323,20 @@ class HipContext:
         rc = self.lib.cglb_gpr_set_hypers(self._ctx, ls.ctypes.data_as(ctypes.POINTER(c_double)), float(variance), float(noise), float(mean))
         _lib.check(rc, self._ctx)
 
-    def gpr_objective_and_grad(self, with_grad=True) -> GPRResult:
+    def gpr_objective_and_grad(self, with_grad=True, with_input_grad=False) -> GPRResult:
+        """with_input_grad: `grad_x`, d lml / d X with respect to the raw training inputs, besides (needs with_grad)."""
+        if with_input_grad and not with_grad:
+            raise ValueError("with_input_grad needs with_grad: the input gradient is formed from the inverse the hyper-parameter gradient computes")
         out3 = (c_double * 3)()
         g = np.empty(self.D + 3, dtype=np.float64) if with_grad else None
-        rc = self.lib.cglb_gpr_objective_and_grad(self._ctx, out3, g.ctypes.data_as(ctypes.POINTER(c_double)) if with_grad else None)
+        gp = g.ctypes.data_as(ctypes.POINTER(c_double)) if with_grad else None
+        gx = self._nan_rows() if with_input_grad else None
+        if with_input_grad:
+            rc = self.lib.cglb_gpr_objective_and_grad_x(self._ctx, out3, gp, _ptr(gx))
+        else:
+            rc = self.lib.cglb_gpr_objective_and_grad(self._ctx, out3, gp)
         _lib.check(rc, self._ctx)
-        return GPRResult(out3[0], out3[1], out3[2], None if g is None else unpack_grad(g, self.D))
+        return GPRResult(out3[0], out3[1], out3[2], None if g is None else unpack_grad(g, self.D), gx)
 
     def gpr_predict(self, xnew) -> Tuple[torch.Tensor, torch.Tensor]:
         """predict_f mean and variance at xnew [n_new, D] from the factor of the last evaluation (factored first if there is none)."""
@@ -337,20 +347,29 @@ class HipContext:
 
     # -- iterative exact GP (cglb_itergp_*): batched CG with Lanczos log-det, fp64, one rank, one target column; num_inducing is the rank of
     #    the pivoted-Cholesky preconditioner, re-selected at every evaluation ----
-    def itergp_objective_and_grad(self, eps, v_inout: torch.Tensor, max_error=1.0, max_cg_iter=1000, lanczos_iter=20, with_grad=True) -> IterGPResult:
+    def itergp_objective_and_grad(self, eps, v_inout: torch.Tensor, max_error=1.0, max_cg_iter=1000, lanczos_iter=20, with_grad=True,
+                                  with_input_grad=False) -> IterGPResult:
         """eps [t, M + N]: the probes' standard-normal draws (the library draws none).  v_inout (device, length N) is the persistent warm start of
-        the data column, updated in place."""
+        the data column, updated in place.  with_input_grad: `grad_x`, the estimator's gradient with respect to the raw training inputs, from one
+        further pass over the vectors of the kernel gradient (needs with_grad); everything else is bitwise what it is without."""
         check_v_inout(v_inout, self)
+        if with_input_grad and not with_grad:
+            raise ValueError("with_input_grad needs with_grad: the input gradient is formed from the vectors of the hyper-parameter gradient")
         e = torch.as_tensor(eps, dtype=torch.float64).reshape(-1, self.M + self.N).contiguous().to(self.device)
         out4 = (c_double * 4)()
         g = np.empty(self.D + 3, dtype=np.float64) if with_grad else None
+        gp = g.ctypes.data_as(ctypes.POINTER(c_double)) if with_grad else None
         steps, half = c_int(), c_double()
-        rc = self.lib.cglb_itergp_objective_and_grad(self._ctx, _ptr(e), int(e.shape[0]), _ptr(v_inout), float(max_error), int(max_cg_iter),
-                                                     int(lanczos_iter), out4, g.ctypes.data_as(ctypes.POINTER(c_double)) if with_grad else None,
-                                                     byref(steps), byref(half))
+        gx = self._nan_rows() if with_input_grad else None
+        if with_input_grad:
+            rc = self.lib.cglb_itergp_objective_and_grad_x(self._ctx, _ptr(e), int(e.shape[0]), _ptr(v_inout), float(max_error), int(max_cg_iter),
+                                                           int(lanczos_iter), out4, gp, byref(steps), byref(half), _ptr(gx))
+        else:
+            rc = self.lib.cglb_itergp_objective_and_grad(self._ctx, _ptr(e), int(e.shape[0]), _ptr(v_inout), float(max_error), int(max_cg_iter),
+                                                         int(lanczos_iter), out4, gp, byref(steps), byref(half))
         _lib.check(rc, self._ctx)
         self._itergp_shape = (steps.value, 1 + int(e.shape[0]))
-        return IterGPResult(out4[0], out4[1], out4[2], out4[3], steps.value, half.value, None if g is None else unpack_grad(g, self.D))
+        return IterGPResult(out4[0], out4[1], out4[2], out4[3], steps.value, half.value, None if g is None else unpack_grad(g, self.D), gx)
 
     def itergp_coefficients(self) -> Tuple[np.ndarray, np.ndarray]:
         """(rz [steps + 1, 1 + t], pAp [steps, 1 + t]) of the last itergp_objective_and_grad."""
@@ -610,6 +629,34 @@ class HipContext:
         ms = c_double()
         _lib.check(self.lib.cglb_time_grad_kff_multi(self._ctx, int(s), int(reps), byref(ms)), self._ctx)
         return ms.value
+
+    def grad_x_kff_multi(self, U, V) -> torch.Tensor:
+        """gx [N, D] (device): gx[i, k] = sum_j w_ij d K_ff[i, j] / d x_ik with w_ij = sum_b (u_bi v_bj + v_bi u_bj) for U, V [N, S], with respect to
+        the raw training inputs: the pairs of grad_kff_multi differentiated in x_i.  Bitwise repeatable."""
+        Ut = self._cols(U)
+        Vt = self._cols(V, Ut.shape[0])
+        gx = self._nan_rows()
+        _lib.check(self.lib.cglb_grad_x_kff_multi(self._ctx, _ptr(Ut), _ptr(Vt), int(Ut.shape[0]), _ptr(gx)), self._ctx)
+        return gx
+
+    def time_grad_x_kff_multi(self, s: int, reps: int) -> float:
+        ms = c_double()
+        _lib.check(self.lib.cglb_time_grad_x_kff_multi(self._ctx, int(s), int(reps), byref(ms)), self._ctx)
+        return ms.value
+
+    def set_inputs(self, X):
+        """Replaces the training inputs ([N, D], any device) and keeps the targets.  The hyper-parameters of set_hypers AND gpr_set_hypers are void
+        afterwards: push them again before the next evaluation (RuntimeError otherwise)."""
+        Xd = torch.as_tensor(X, dtype=self.dtype).reshape(-1, self.D).contiguous().to(self.device)
+        if Xd.shape[0] != self.N:
+            raise ValueError(f"expected {self.N} rows of training inputs, got {Xd.shape[0]}")
+        _lib.check(self.lib.cglb_set_inputs(self._ctx, _ptr(Xd)), self._ctx)
+        torch.cuda.synchronize(self.device)
+        self.state_version += 1
+
+    def _nan_rows(self) -> torch.Tensor:
+        """[N, D] device buffer of an input gradient: NaN until the library has written it"""
+        return torch.full((self.N, self.D), float("nan"), dtype=torch.float64, device=self.device)
 
     def get_stat(self, name: str) -> float:
         out = c_double()

@@ -469,6 +469,38 @@ int cglb_grad_kff_multi(cglb_ctx* ctx, const void* U, const void* V, int S, doub
  * stream, no read-back), in the style of cglb_time_kernel(which = 2), which times one single pass */
 int cglb_time_grad_kff_multi(cglb_ctx* ctx, int S, int reps, double* ms_avg);
 
+/* ---- gradients with respect to the TRAINING inputs (csrc/kernels_train_input_grad.hip; no counterpart in the reference) ------------------
+ * What a learned feature map in front of the kernel needs: X = g(raw), trained by back-propagating d objective / d X into g.
+ *   d kappa(x_i, x_j) / d x_ik = -h_ij delta_ijk / l_k, delta_ijk = (x_ik - x_jk) / l_k         (the convention of cglb_cross_grad_matmat)
+ *   gx[i, k] = sum_j w_ij variance d kappa(x_i, x_j) / d x_ik
+ * with respect to the RAW coordinates.  A coincident pair (i = j, a duplicated row) has delta = 0 exactly and adds exactly zero.
+ * Scope of all four entries: fp64, one rank, one target column, d <= 32, every kernel kind; elsewhere CGLB_ERR_BAD_ARG with a message
+ * (cglb_get_stat "train_input_grad_native" tells which).
+ *
+ * cglb_grad_x_kff_multi: the standalone product of the bilinear forms of cglb_grad_kff_multi, w_ij = sum_b (u_bi v_bj + v_bi u_bj), b < S.
+ * U, V: as in cglb_grad_kff_multi; gx_out: dev [n_total, d], k fastest.  The full square is swept in groups of 8 pairs (4 above 16 dimensions),
+ * the groups added in order: no atomics, bitwise reproducible.  With out = cglb_grad_kff_multi(U, V):
+ * sum_i x_ik gx[i, k] = -l_k out[k] and sum_i gx[i, k] = 0, both to round-off. */
+int cglb_grad_x_kff_multi(cglb_ctx* ctx, const void* U, const void* V, int S, void* gx_out);
+/* average duration (ms) of `reps` back-to-back passes with S pairs (operand records, pair kernel and finish of every group and row block, on the
+ * context stream), beside cglb_time_grad_kff_multi */
+int cglb_time_grad_x_kff_multi(cglb_ctx* ctx, int S, int reps, double* ms_avg);
+/* cglb_itergp_objective_and_grad with the estimator's gradient with respect to the training inputs besides: the same evaluation - out4, grad,
+ * steps, half_rz and the state left behind are bitwise those of that entry, which is the gx_out = NULL case of one implementation - then ONE further
+ * pass over the 1 + t vector pairs the kernel gradient already holds, inside the "itergp_grad_ms" bracket.  grad and gx_out (dev [n_total, d]) must
+ * both be set.  As grad, gx is the gradient of the ESTIMATOR (P treated as constant), not the derivative of the value in out4. */
+int cglb_itergp_objective_and_grad_x(cglb_ctx* ctx, const void* eps, int t, void* v_inout, double max_error, int max_cg_iter, int lanczos_iter,
+                                     double* out4, double* grad, int* steps, double* half_rz, void* gx_out);
+/* cglb_gpr_objective_and_grad with the exact gradient with respect to the training inputs besides: out3 and grad are bitwise those of that entry;
+ * gx_out: dev [n_total, d], w_ij = alpha_i alpha_j - K^-1_ij (half of alpha alpha^T - K^-1, counted for K_ij and K_ji), through the row-weighted
+ * gradient product of cglb_gpr_predict_grad with rows = points = X, one row block of the option "gpr_block" at a time: n_total x gpr_block further
+ * doubles, checked against the free device memory first. */
+int cglb_gpr_objective_and_grad_x(cglb_ctx* ctx, double* out3, double* grad, void* gx_out);
+/* Replace the training inputs (X: [n_total, d], host or device, the context's element type) and keep the targets.  Invalidates everything
+ * cglb_set_data invalidates AND the hyper-parameters of both cglb_set_hypers and cglb_gpr_set_hypers: the scaled operand sets are made from X by
+ * cglb_set_hypers, so an evaluation without a new push is CGLB_ERR_STATE instead of an evaluation on the old inputs.  Needs cglb_set_data first. */
+int cglb_set_inputs(cglb_ctx* ctx, const void* X);
+
 /* ---- inducing-point initialisation: InducingVariableConfig.init, config.py:55-65 ------------------------
  * The reference calls robustgp.ConditionalVariance(sample=False) (third-party): greedy maximisation of the conditional
  * variance under the INITIAL kernel (pivoted Cholesky of K_ff, lowest index on ties).  Needs set_data only; works on all n rows
@@ -504,6 +536,8 @@ int cglb_time_kernel(cglb_ctx* ctx, int which, int reps, double* ms_avg);
  * register-resident instance (fp64 up to 32 dimensions; 33 ... 96 under "input_grad_mid"), 0 if it is refused;
  * "predict_grad_native": 1 if the next cglb_predict_grad on this context in its current state - dtype, ranks, target columns, width, "wide_reg",
  * "input_grad_mid" - runs (fp64, one rank, one target column, up to 32 dimensions; 33 ... 96 under "input_grad_mid"), 0 if it is refused;
+ * "train_input_grad_native": 1 if the next training-input gradient (cglb_grad_x_kff_multi, cglb_itergp_objective_and_grad_x,
+ * cglb_gpr_objective_and_grad_x) on this context in its current state - dtype, width, ranks, shard, target columns - runs, 0 if it is refused;
  * "exp_clamp" | "m32_bias": the exponent-range regime the last cglb_set_hypers chose from the data's per-column range and the lengthscales
  * (CGLB_ERR_STATE before one) - 1 if the pair kernels run their range-clamped instances (kernel values below 2^-1000 come out as that floor,
  * not 0), 0 for the unclamped ones | the positivity bias of the Matern squared distance in hot units^2 (0 for RBF; above 2e-8 the clamped
