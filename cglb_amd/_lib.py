@@ -134,6 +134,13 @@ SIGNATURES = {
                                                  POINTER(c_int), POINTER(c_double), c_void_p]),
     "cglb_gpr_objective_and_grad_x": (c_int, [c_void_p, POINTER(c_double), POINTER(c_double), c_void_p]),
     "cglb_set_inputs": (c_int, [c_void_p, c_void_p]),
+    # training-input gradient of the CGLB / SGPR bounds: the evaluation, the transposed panel pass and the single-pair K_ff pass
+    "cglb_objective_and_grad_x": (c_int, [c_void_p, c_void_p, c_int, c_double, c_int, c_int, POINTER(c_double), POINTER(c_double),
+                                          POINTER(c_int), POINTER(c_double), c_void_p]),
+    "cglb_grad_x_kuf": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
+    "cglb_time_grad_x_kuf": (c_int, [c_void_p, c_int, POINTER(c_double)]),
+    "cglb_grad_x_kff_pair": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
+    "cglb_time_grad_x_kff_pair": (c_int, [c_void_p, c_int, POINTER(c_double)]),
 }
 
 _lib = None

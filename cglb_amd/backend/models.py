@@ -186,6 +186,23 @@ class GPR(nn.Module):
         except TypeError:  # lists / scalars cannot be weakly referenced: compared in full every time
             self._accepted_data = None
 
+    def set_train_inputs(self, x) -> None:
+        """Replaces the training inputs ([N, d], any device; the targets stay): the model's `train_inputs`, the remembered pair of `check_same_data`
+        and the library's copy (every class whose context is one `HipContext`: SGPR, CGLB and its log-det variants, ExactGPR, IterGPR).  The
+        library forgets its hyper-parameters with the inputs (its scaled operand sets are made from both), so whatever the class remembers as
+        pushed is void; a warm start (`v_vec`) is kept."""
+        x = torch.as_tensor(x).detach()
+        x = x.reshape(x.shape[0], -1)
+        if tuple(x.shape) != tuple(self.train_inputs[0].shape):
+            raise ValueError(f"set_train_inputs was given inputs of shape {tuple(x.shape)} but the model holds {tuple(self.train_inputs[0].shape)}")
+        if not hasattr(self.hip, "set_inputs"):
+            raise NotImplementedError(f"{type(self).__name__}: the training inputs can be replaced on one rank only")
+        self.train_inputs = (x,)
+        self._accepted_data = None
+        if hasattr(self, "_pushed"):   # IterGPR: the key of the last set_hypers
+            self._pushed = None
+        self.hip.set_inputs(x)
+
 
 _ONE_RANK = "{name} is not available on more than one rank (only CGLB runs row-sharded)"
 
@@ -328,21 +345,6 @@ class _NoInducingGPR(GPR):
         k = self.covar_module
         return (k.base_kernel.lengthscale.reshape(-1), k.outputscale.reshape(()), self.likelihood.noise.reshape(()),
                 self.mean_module.constant.reshape(()))
-
-
-    def set_train_inputs(self, x) -> None:
-        """Replaces the training inputs ([N, d], any device; the targets stay): the model's `train_inputs`, the remembered pair of `check_same_data`
-        and the library's copy.  The library forgets its hyper-parameters with the inputs (its scaled operand sets are made from both), so whatever
-        the class remembers as pushed is void; a warm start (`v_vec`) is kept."""
-        x = torch.as_tensor(x).detach()
-        x = x.reshape(x.shape[0], -1)
-        if tuple(x.shape) != tuple(self.train_inputs[0].shape):
-            raise ValueError(f"set_train_inputs was given inputs of shape {tuple(x.shape)} but the model holds {tuple(self.train_inputs[0].shape)}")
-        self.train_inputs = (x,)
-        self._accepted_data = None
-        if hasattr(self, "_pushed"):   # IterGPR: the key of the last set_hypers
-            self._pushed = None
-        self.hip.set_inputs(x)
 
 
 class ExactGPR(_NoInducingGPR):
@@ -623,7 +625,8 @@ class _InputEvaluation(torch.autograd.Function):
         gout = gout.to(torch.float64)
         shape, dtype, device = ctx.x_like
         gx = None if ctx.gx is None else (gout.to(ctx.gx.device) * ctx.gx).reshape(shape).to(device=device, dtype=dtype)
-        grads = [gout * (torch.from_numpy(g[key]) if key == "lengthscales" else g[key]) for key in ("lengthscales", "variance", "noise", "mean")]
+        grads = [gout * (torch.from_numpy(g[key]) if key in ("lengthscales", "Z") else g[key])
+                 for key in ("lengthscales", "variance", "noise", "mean", "Z") if key in g]   # "Z": the classes with inducing points, as _Evaluation
         return (None, gx, *grads)
 
 
@@ -681,6 +684,65 @@ class InputGradStochasticLogMarginalLikelihood(_InputGradObjective):
         model.last_bound = float(res.lml)
         model.cg_stats = ConjugateGradientStats(steps=res.steps, residual_error=res.residual_error)
         return res.lml, res.grad, res.grad_x
+
+
+class InputGradLowerBoundCG(_InputGradObjective):
+    """`InputGradLowerBoundCG(model)(x)`: the CGLB bound (CGLB, CGLBNM2) at the training inputs `x`, differentiable in `x`, the hyper-parameters
+    and Z: the exact derivative of the value at the v of the evaluation, v detached as LowerBoundCG has it.  `model.v_vec` is the warm start of the
+    solve; `run_cg` follows the rules of LowerBoundCG.evaluate (`use_cache` / `cached_v_vec`, `vzero`).  fp64, one rank, one target column, up to
+    32 input dimensions; a plug-in solver, `joint_optimization` and the N^2M log-det class are refused."""
+
+    MODEL, EXPECTED = CGLB, "CGLB"
+
+    def __init__(self, model: CGLB, cg_opt: Optional[ConjugateGradient] = None, use_cache: bool = False, cached_v_vec_initial: bool = False):
+        super().__init__(model)
+        if cg_opt is None:
+            tol = getattr(model, "max_error", None)
+            cg_opt = ConjugateGradient() if tol is None else ConjugateGradient(max_error=float(tol))
+        if type(cg_opt) is not ConjugateGradient:
+            raise NotImplementedError("a plug-in solver is not available with the training-input gradient (the solve runs in the library)")
+        if model.joint_optimization and not model.vzero:
+            raise NotImplementedError("joint optimisation of v is not available with the training-input gradient")
+        if model.num_outputs > 1:
+            raise NotImplementedError("the training-input gradient of the bound takes one target column")
+        self.cg_opt = cg_opt
+        self.cached_v_vec = cached_v_vec_initial
+        self._use_cache = use_cache
+        self.last_bounds: Optional[Bounds] = None
+
+    def evaluate(self, x, need_x, needs):
+        model, hip, cg = self.model, self.model.hip, self.cg_opt
+        model.set_train_inputs(x)
+        model.push_hypers(get_cholesky_jitter())
+        run_cg = not (self._use_cache and self.cached_v_vec) and not model.vzero
+        res = hip.objective_and_grad(model.v_vec.detach().reshape(-1), run_cg, cg.max_error, cg.max_cg_iter, cg.restart_cg_iter,
+                                     with_grad=need_x or any(needs), with_input_grad=need_x)
+        if run_cg:
+            model.cg_stats = ConjugateGradientStats(res.steps, torch.tensor(res.residual_error, dtype=torch.float64))
+            self.cached_v_vec = self._use_cache
+        self.last_bounds = Bounds(upper_bound=torch.tensor(-res.upper), lower_bound=torch.tensor(-res.lower))
+        model.last_bound = float(res.bound)
+        return res.bound, res.grad, res.grad_x
+
+
+class InputGradLowerBoundSGPR(_InputGradObjective):
+    """`InputGradLowerBoundSGPR(model)(x)`: the collapsed bound of an SGPR model at the training inputs `x`, differentiable in `x`, the
+    hyper-parameters and Z (fp64, up to 32 input dimensions; SGPRN2M is refused by the library)."""
+
+    MODEL, EXPECTED = SGPR, "SGPR"
+
+    def __init__(self, model: SGPR):
+        if isinstance(model, CGLB):
+            raise ValueError(f"SGPR model expected in the constructor of the {self.__class__}")
+        super().__init__(model)
+
+    def evaluate(self, x, need_x, needs):
+        model = self.model
+        model.set_train_inputs(x)
+        model.push_hypers(get_cholesky_jitter())
+        res = model.hip.objective_and_grad(model._zero_v, False, with_grad=need_x or any(needs), with_input_grad=need_x)
+        model.last_bound = float(res.bound)
+        return res.bound, res.grad, res.grad_x
 
 
 def _refuse_full_cov(full_cov: bool):

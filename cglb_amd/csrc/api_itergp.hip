@@ -929,6 +929,61 @@ int cglb_time_grad_x_kff_multi(cglb_ctx* c, int S, int reps, double* ms_avg) {
     return rc;
 }
 
+int cglb_grad_x_kff_pair(cglb_ctx* c, const void* u, const void* v, void* gx_out) {
+    if (c) c->obj_valid = false;
+    if (!c || !u || !v || !gx_out) return c ? cglb_fail(c, CGLB_ERR_BAD_ARG, "bad argument") : CGLB_ERR_BAD_ARG;
+    CGLB_TRY(require_train_input_grad_ok(c));
+    HIP_CHECK(c, hipSetDevice(c->device));
+    CGLB_TRY(launch_grad_x_kff_pair(c, u, v, (double*)gx_out, 0));
+    HIP_CHECK(c, hipStreamSynchronize(c->stream));
+    return CGLB_OK;
+}
+
+int cglb_time_grad_x_kff_pair(cglb_ctx* c, int reps, double* ms_avg) {
+    if (c) c->obj_valid = false;
+    if (!c || !ms_avg || reps <= 0) return c ? cglb_fail(c, CGLB_ERR_BAD_ARG, "bad argument") : CGLB_ERR_BAD_ARG;
+    CGLB_TRY(require_train_input_grad_ok(c));
+    HIP_CHECK(c, hipSetDevice(c->device));
+    multi_work w;
+    CGLB_TRY(multi_reserve(c, 1, &w));
+    void* gx = nullptr;
+    DevTemps tmp;
+    CGLB_TRY(tmp.alloc(c, &gx, (size_t)c->N * c->D * sizeof(double)));
+    CGLB_TRY(fill_y_columns(c, w.p, 1));  // operands: y on both sides, as cglb_time_grad_x_kff_multi(S = 1)
+    const int rc = time_repeated(c, reps, [&]() -> int { return launch_grad_x_kff_pair(c, w.p, w.p, (double*)gx, 0); }, ms_avg);
+    (void)hipStreamSynchronize(c->stream);  // before `tmp` frees
+    return rc;
+}
+
+// the standalone transposed panel pass: the operand sets of the last set_hypers (the inducing points and lengthscales it was given), no common terms
+int cglb_grad_x_kuf(cglb_ctx* c, const void* G, int64_t ldg, const void* cvec, const void* wvec, void* gx_out) {
+    if (c) c->obj_valid = false;
+    if (!c || !G || !gx_out) return c ? cglb_fail(c, CGLB_ERR_BAD_ARG, "bad argument") : CGLB_ERR_BAD_ARG;
+    CGLB_TRY(require_train_input_grad_ok(c));
+    HIP_CHECK(c, hipSetDevice(c->device));
+    CGLB_TRY(launch_grad_x_kuf(c, G, ldg, cvec, wvec, (double*)gx_out));
+    HIP_CHECK(c, hipStreamSynchronize(c->stream));
+    return CGLB_OK;
+}
+
+int cglb_time_grad_x_kuf(cglb_ctx* c, int reps, double* ms_avg) {
+    if (c) c->obj_valid = false;
+    if (!c || !ms_avg || reps <= 0) return c ? cglb_fail(c, CGLB_ERR_BAD_ARG, "bad argument") : CGLB_ERR_BAD_ARG;
+    CGLB_TRY(require_train_input_grad_ok(c));
+    HIP_CHECK(c, hipSetDevice(c->device));
+    const int64_t ld = (c->N + 31) & ~(int64_t)31;
+    void *G = nullptr, *cv = nullptr, *gx = nullptr;
+    DevTemps tmp;
+    CGLB_TRY(tmp.alloc(c, &G, (size_t)c->M * ld * sizeof(double)));  // operands: a panel of zeros with the rank-one term 0 y^T (values do not change the instruction stream)
+    CGLB_TRY(tmp.alloc(c, &cv, (size_t)c->M * sizeof(double)));
+    CGLB_TRY(tmp.alloc(c, &gx, (size_t)c->N * c->D * sizeof(double)));
+    HIP_CHECK(c, hipMemsetAsync(G, 0, (size_t)c->M * ld * sizeof(double), c->stream));
+    HIP_CHECK(c, hipMemsetAsync(cv, 0, (size_t)c->M * sizeof(double), c->stream));
+    const int rc = time_repeated(c, reps, [&]() -> int { return launch_grad_x_kuf(c, G, ld, cv, c->y, (double*)gx); }, ms_avg);
+    (void)hipStreamSynchronize(c->stream);  // before `tmp` frees
+    return rc;
+}
+
 int cglb_time_grad_kff_multi(cglb_ctx* c, int S, int reps, double* ms_avg) {
     if (c) c->obj_valid = false;
     if (!c || !ms_avg || reps <= 0 || S < 1) return c ? cglb_fail(c, CGLB_ERR_BAD_ARG, "bad argument") : CGLB_ERR_BAD_ARG;

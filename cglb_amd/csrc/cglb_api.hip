@@ -1078,6 +1078,7 @@ int cglb_set_option(cglb_ctx* c, const char* name, int64_t value) {
     if (!c || !name) return CGLB_ERR_BAD_ARG;
     if (!strcmp(name, "kff_variant")) c->kff_variant = (int)value;
     else if (!strcmp(name, "kff_jsplit")) c->kff_jsplit = (int)value;
+    else if (!strcmp(name, "kuf_msplit")) c->kuf_msplit = (int)value;  // > 0: forced chunk count of the transposed panel pass (0: the rule)
     else if (!strcmp(name, "kff_rows")) c->kff_rows = (int)value;
     else if (!strcmp(name, "sym_chunk")) {
         // the launcher rounds the value up to the 16-column batch before it clamps it to SYM_CHUNK_MAX: a value next to INT64_MAX would
@@ -1522,12 +1523,33 @@ int cglb_shard_obj_finish(cglb_ctx* c, const void* sc, double* out4) {
     return obj_finish(c, (const double*)sc, out4);
 }
 
-int cglb_objective_and_grad(cglb_ctx* c, void* v_inout, int run_cg, double max_error, int max_cg_iter, int restart_cg_iter, double* out4,
-                            double* grad, int* steps, double* half_rz) {
+// The scope of the bound's training-input gradient (cglb_objective_and_grad_x; cglb_get_stat "bound_input_grad_native"): fp64, at most 32 input
+// dimensions, one rank and one shard, one target column, the Jensen and NM^2 log-det terms, the stored panel.  The message of the first reason
+// it is refused for, nullptr where it runs.
+static const char* bound_input_grad_refusal(const cglb_ctx* c) {
+    if (c->dtype != CGLB_F64) return "the training-input gradient of the bound needs an fp64 context (-t fp64): it has no fp32 path yet";
+    if (is_wide(c)) return "the training-input gradient of the bound has no wide path yet: it is available up to 32 input dimensions";
+    if (c->par_world > 1 || c->comm || c->r0 != 0 || c->r1 != c->N)
+        return "the training-input gradient of the bound needs a single shard covering all rows on one rank";
+    if (c->p != 1) return "the training-input gradient of the bound takes one target column";
+    if (c->logdet_bound == 2)
+        return "the training-input gradient of the bound is not available for the N^2M log-det term (logdet_bound 2): its K_ff trace terms have no input gradient yet";
+    if (c->precond_mode != 0) return "the training-input gradient of the bound needs the stored panel A (precond_mode 0)";
+    return nullptr;
+}
+
+// cglb_objective_and_grad (gx_out == nullptr) and cglb_objective_and_grad_x: one evaluation; the input gradient is two further passes over what
+// phase 3 leaves on the device, inside the gradient bracket of the phase timing, and touches nothing the evaluation returns or leaves behind
+static int objective_and_grad_impl(cglb_ctx* c, void* v_inout, int run_cg, double max_error, int max_cg_iter, int restart_cg_iter, double* out4, double* grad,
+                                   int* steps, double* half_rz, void* gx_out) {
     if (!c || !v_inout || !out4) return c ? cglb_fail(c, CGLB_ERR_BAD_ARG, "NULL argument") : CGLB_ERR_BAD_ARG;
     c->obj_valid = false;
     CGLB_TRY(require_single(c));
     CGLB_TRY(require_variant_ok(c));
+    if (gx_out) {
+        if (const char* why = bound_input_grad_refusal(c)) return cglb_fail(c, CGLB_ERR_BAD_ARG, why);
+        if (!grad) return cglb_fail(c, CGLB_ERR_BAD_ARG, "the training-input gradient of the bound is formed from the adjoints of the hyper-parameter gradient: grad must be set");
+    }
     const bool exact = c->quad_term == 1;
     if (exact) {  // v = 0 and no solve (the caller's v is left as it is)
         CGLB_TRY(ensure_zero_vec(c));
@@ -1548,11 +1570,28 @@ int cglb_objective_and_grad(cglb_ctx* c, void* v_inout, int run_cg, double max_e
         CGLB_DISPATCH_T(c->dtype, CGLB_TRY(obj_phase3_impl<T>(c, v_eval, sc, c->w_u, c->gradbuf)));
         HIP_CHECK(c, hipMemcpyAsync(grad, c->gradbuf, (size_t)CGLB_GRAD_LEN(c->D, c->M) * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     }
+    if (gx_out) {
+        // d bound / d X at fixed v, Z and hyper-parameters, from what phase 3 left: the K_uf adjoint Guf + c w^T (c = w_t2, w = w_z) reduced over the
+        // inducing points, then - CG quadratic term only - the K_ff term +(w + v/2)^T dK v as the pair (u, v), u = w + v/2 in w_Ap.  K_uu and
+        // tr K_ff do not depend on X.  Before any of these buffers is reused
+        CGLB_TRY(launch_grad_x_kuf(c, c->Guf, c->lda, c->w_t2, c->w_z, (double*)gx_out));
+        if (!exact) CGLB_TRY(launch_grad_x_kff_pair(c, c->w_Ap, v_eval, (double*)gx_out, 1));
+    }
     CGLB_TRY(eval_mark(c));
     CGLB_TRY(obj_finish(c, sc, out4));
     marks.done = true;
     c->obj_valid = true;  // r = e - K v and w = P r of this evaluation stay in the work vectors (cglb_objective_grad_v)
     return CGLB_OK;
+}
+
+int cglb_objective_and_grad(cglb_ctx* c, void* v_inout, int run_cg, double max_error, int max_cg_iter, int restart_cg_iter, double* out4,
+                            double* grad, int* steps, double* half_rz) {
+    return objective_and_grad_impl(c, v_inout, run_cg, max_error, max_cg_iter, restart_cg_iter, out4, grad, steps, half_rz, nullptr);
+}
+
+int cglb_objective_and_grad_x(cglb_ctx* c, void* v_inout, int run_cg, double max_error, int max_cg_iter, int restart_cg_iter, double* out4,
+                              double* grad, int* steps, double* half_rz, void* gx_out) {
+    return objective_and_grad_impl(c, v_inout, run_cg, max_error, max_cg_iter, restart_cg_iter, out4, grad, steps, half_rz, gx_out);
 }
 
 int cglb_objective_grad_v(cglb_ctx* c, void* gv_out) {
@@ -1988,6 +2027,10 @@ int cglb_get_stat(cglb_ctx* c, const char* name, double* value) {
     if (!strcmp(name, "grad_multi_native")) { *value = (c->have_data && grad_multi_native(c)) ? 1.0 : 0.0; return CGLB_OK; }  // multi-pair gradient instance or single passes
     if (!strcmp(name, "train_input_grad_native")) {  // the next training-input gradient runs (fp64, one rank, one target column, at most 32 input dimensions) or is refused
         *value = (train_input_grad_native(c) && c->p == 1) ? 1.0 : 0.0;
+        return CGLB_OK;
+    }
+    if (!strcmp(name, "bound_input_grad_native")) {  // the next cglb_objective_and_grad_x with gx_out runs (bound_input_grad_refusal) or is refused
+        *value = bound_input_grad_refusal(c) ? 0.0 : 1.0;
         return CGLB_OK;
     }
     if (!strcmp(name, "predict_grad_native")) {  // the next cglb_predict_grad runs (fp64, one rank, one target column; narrow, or mid under "input_grad_mid") or is refused

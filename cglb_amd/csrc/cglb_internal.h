@@ -180,6 +180,7 @@ struct cglb_ctx {
     // tunables
     int precision = 1;  // CGLB_PREC_FAST (devmath.h): kernel values to <= 1e-13; 0 = CGLB_PREC_EXACT (~3e-16); 2 = CGLB_PREC_LOW (~1e-10, opt-in)
     int kff_variant = 2, kff_jsplit = 0, kff_rows = 4;  // 0 plain, 1 matrix-pipe Gram (fp64), 2 symmetric (default)
+    int kuf_msplit = 0;             // > 0: forced chunk count over the inducing points of the transposed panel pass (row_slab.h: row_slab_panel_split)
     bool exp_clamp = false;         // scaled operands so large that 2^x needs the range clamp (set by set_hypers)
     double m32_bias = 0.0;          // Matern-3/2 and -5/2: positivity bias of the squared distance in hot units^2 (devmath.h CGLB_M32_BIAS_*; set by set_hypers)
     bool kff_skip_combine = false;  // timing only: launch the pair kernel without the slab combine
@@ -449,6 +450,14 @@ bool train_input_grad_native(const cglb_ctx* c);
 int launch_grad_x_kff_multi(cglb_ctx* c, const void* U, const void* V, int S, double* gx);
 int train_input_grad_rows_per_block(const cglb_ctx* c);  // rows per workgroup at the context's width
 int train_input_grad_width(const cglb_ctx* c);           // vector pairs per group at the context's width (8 or 4)
+// ... its single-pair instance (G = 1): gx (+)= the same sum for ONE pair u, v (dev [N]), w_ij = u_i v_j + v_i u_j; accumulate: added to gx
+int launch_grad_x_kff_pair(cglb_ctx* c, const void* u, const void* v, double* gx, int accumulate);
+int train_input_grad_pair_rows_per_block(const cglb_ctx* c);
+// kernels_bound_input_grad.hip, the transposed panel pass: gx[n * D + k] = sum_m (G[m * ldg + n] + cvec[m] wvec[n]) d k(z_m, x_n) / d x_nk with respect to
+// the raw training inputs; G dev [M][ldg] (row m contiguous), cvec dev [M] and wvec dev [N] or both NULL; gx dev [N][D], overwritten.  The operand sets
+// (Zs, Xs) and the evaluator of launch_grad_kuf.  fp64, one rank, Dp <= 32 (train_input_grad_native).  Bitwise repeatable.
+int launch_grad_x_kuf(cglb_ctx* c, const void* G, int64_t ldg, const void* cvec, const void* wvec, double* gx);
+int grad_x_kuf_rows_per_block(const cglb_ctx* c);
 // The row-slab products (decomposition, chunk rules, layout constants and the shared value finish kernel: row_slab.h), one file each:
 // kernels_cross_multi.hip: out[i * ldo + s] = var * sum_j kappa(row_i, x_j) Vi[j * ldv + s], s < S; Vi dev [N][ldv] row-major (ldv a multiple of 8, zero
 // padded), rows hot-scaled; every kernel value evaluated once per group of 8 columns.  fp64, Dp <= 32.  Bitwise repeatable.

@@ -39,6 +39,16 @@ static constexpr int input_grad_group_width(int dp) { return dp <= 8 ? 8 : (dp <
 // accumulators, both row-side vectors, the differences in flight): 2 x 8 up to width 8 (72 at 8), 1 x 8 up to 16 (64), 1 x 4 beyond (104 at 32)
 static constexpr int train_input_grad_rows_per_lane(int dp) { return dp <= 8 ? 2 : 1; }
 static constexpr int train_input_grad_group_width(int dp) { return dp <= 16 ? 8 : 4; }
+// The single-pair instance of that kernel (G = 1: cglb_grad_x_kff_pair, the K_ff term of cglb_objective_and_grad_x; mirrored by
+// tests/bound_input_grad_ref.py): the two row-side vectors shrink from 2 G to 2 doubles per row, which pays for more rows per lane.  Row-resident
+// doubles R (2 DP + 2) + DP: 4 rows up to width 8 (80 at 8), 2 up to 16 (84), 1 beyond (98 at 32); 2 DP + 2 SGPR pairs on the column side
+static constexpr int train_input_grad_pair_rows_per_lane(int dp) { return dp <= 8 ? 4 : (dp <= 16 ? 2 : 1); }
+// The transposed panel pass (kernels_bound_input_grad.hip: grad_x_kuf_kernel; mirrored by tests/bound_input_grad_ref.py): a lane owns R training points,
+// R (2 DP + 1) + DP row-resident doubles (coordinates, accumulators, w_n, the differences in flight) and R panel loads in flight per inducing point:
+// 2 rows up to width 8 (42 at 8), 1 beyond (97 at 32).  The pass streams the panel once: more rows per lane buy nothing once the loads overlap
+static constexpr int grad_x_kuf_rows_per_lane(int dp) { return dp <= 8 ? 2 : 1; }
+#define GRAD_X_KUF_TARGET_WG 2048  // workgroups a launch of the transposed panel pass aims at: 8 per CU
+#define GRAD_X_KUF_MIN_CHUNK 16    // the rule makes at most ceil(M / 16) chunks: more than 8 inducing points each
 // Mid widths (kernels_input_grad_mid.hip, hot width dh in 48, 64, 80, 96): a new point is shared by SPLIT lanes of HD = dh / SPLIT coordinates each;
 // (2 + G) HD + G row-resident doubles per lane (coordinates, differences, G x HD gradient sums, G values): 76, 100, 82, 98.  256 / SPLIT rows per workgroup
 static constexpr int input_grad_mid_split(int dh) { return dh > 0 ? 4 : 0; }
@@ -143,6 +153,20 @@ static inline void row_slab_feature_split(int64_t rows_per_block, int64_t nrows,
     const int64_t jchunk = (F + jsplit - 1) / jsplit;
     *jchunk_out = jchunk;
     *jsplit_out = (F + jchunk - 1) / jchunk;
+}
+
+// Split of the inducing points of the transposed panel pass: msplit = forced (c->kuf_msplit) or ceil(GRAD_X_KUF_TARGET_WG / row blocks), within
+// 1 .. min(slot_cap, ceil(M / GRAD_X_KUF_MIN_CHUNK)) (a forced count: within 1 .. min(slot_cap, M)); chunks of ceil(M / msplit) inducing points; then the chunk count that length gives.  A large N
+// fills the device with its row blocks alone (one chunk, no slab traffic beyond the result); a small N is split over m.
+static inline void row_slab_panel_split(int64_t forced, int64_t row_blocks, int64_t M, int64_t slot_cap, int64_t* msplit_out, int64_t* mchunk_out) {
+    const int64_t min_chunk = forced > 0 ? 1 : GRAD_X_KUF_MIN_CHUNK;  // a forced count is held to M alone: the tests split a handful of points
+    int64_t msplit = forced > 0 ? forced : (GRAD_X_KUF_TARGET_WG + row_blocks - 1) / row_blocks;
+    if (msplit > slot_cap) msplit = slot_cap;
+    if (msplit > (M + min_chunk - 1) / min_chunk) msplit = (M + min_chunk - 1) / min_chunk;
+    if (msplit < 1) msplit = 1;
+    const int64_t mchunk = (M + msplit - 1) / msplit;
+    *mchunk_out = mchunk;
+    *msplit_out = (M + mchunk - 1) / mchunk;
 }
 
 // most chunks of a gradient launch: ROW_SLAB_SLOTS, fewer where nrows rows of row_doubles partial sums each would exceed the slab

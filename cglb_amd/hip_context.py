@@ -32,6 +32,7 @@ class ObjectiveResult:
     steps: int
     residual_error: float
     grad: Optional[dict]  # constrained-space gradient of `bound`
+    grad_x: Optional[torch.Tensor] = None  # d bound / d X at fixed v, device [N, D] (with_input_grad)
 
 
 @dataclass
@@ -266,10 +267,26 @@ class HipContext:
         return ms.value
 
     def objective_and_grad(self, v_inout: torch.Tensor, run_cg=True, max_error=1.0, max_cg_iter=100, restart_cg_iter=40,
-                           with_grad=True) -> ObjectiveResult:
-        """v_inout (device, length N; [N, P] for P > 1 target columns) is the persistent warm-start vector: updated in place when run_cg."""
+                           with_grad=True, with_input_grad=False) -> ObjectiveResult:
+        """v_inout (device, length N; [N, P] for P > 1 target columns) is the persistent warm-start vector: updated in place when run_cg.
+        with_input_grad: `grad_x`, the exact derivative of `bound` with respect to the raw training inputs at fixed v, besides (needs with_grad;
+        cglb_objective_and_grad_x: fp64, one rank, one target column, up to 32 input dimensions, not the N^2M log-det classes); everything else is
+        bitwise what it is without."""
         if v_inout.device != self.device or v_inout.dtype != self.dtype:
             raise ValueError("v_inout must be a device tensor in the context dtype")
+        if with_input_grad and not with_grad:
+            raise ValueError("with_input_grad needs with_grad: the input gradient is formed from the adjoints of the hyper-parameter gradient")
+        if with_input_grad:
+            if self.P == 1:   # P > 1: the library refuses before it reads v
+                check_v_inout(v_inout, self)
+            out4 = (c_double * 4)()
+            g = np.empty(grad_len(self.D, self.M), dtype=np.float64)
+            steps, half = c_int(), c_double()
+            gx = self._nan_rows()
+            rc = self.lib.cglb_objective_and_grad_x(self._ctx, _ptr(v_inout), int(bool(run_cg)), float(max_error), int(max_cg_iter), int(restart_cg_iter),
+                                                    out4, g.ctypes.data_as(ctypes.POINTER(c_double)), byref(steps), byref(half), _ptr(gx))
+            _lib.check(rc, self._ctx)
+            return ObjectiveResult(out4[0], out4[1], out4[2], out4[3], steps.value, half.value, self.unpack_grad(g), gx)
         if self.P > 1:
             if tuple(v_inout.shape) != (self.N, self.P):
                 raise ValueError("v_inout must be a device tensor of shape [N, P] in the context dtype")
@@ -642,6 +659,40 @@ class HipContext:
     def time_grad_x_kff_multi(self, s: int, reps: int) -> float:
         ms = c_double()
         _lib.check(self.lib.cglb_time_grad_x_kff_multi(self._ctx, int(s), int(reps), byref(ms)), self._ctx)
+        return ms.value
+
+    def grad_x_kff_pair(self, u, v) -> torch.Tensor:
+        """grad_x_kff_multi for ONE pair u, v [N] through the single-pair instance of the pass (cglb_grad_x_kff_pair): the same sums in another
+        order, equal to grad_x_kff_multi(u, v) to round-off.  Bitwise repeatable."""
+        ut, vt = self._dev(u, self.N), self._dev(v, self.N)
+        gx = self._nan_rows()
+        _lib.check(self.lib.cglb_grad_x_kff_pair(self._ctx, _ptr(ut), _ptr(vt), _ptr(gx)), self._ctx)
+        return gx
+
+    def time_grad_x_kff_pair(self, reps: int) -> float:
+        ms = c_double()
+        _lib.check(self.lib.cglb_time_grad_x_kff_pair(self._ctx, int(reps), byref(ms)), self._ctx)
+        return ms.value
+
+    def grad_x_kuf(self, G, cvec=None, wvec=None) -> torch.Tensor:
+        """gx [N, D] (device): gx[n, k] = sum_m (G[m, n] + cvec[m] wvec[n]) d k(z_m, x_n) / d x_nk with respect to the raw training inputs, at the
+        inducing points and hyper-parameters of the last set_hypers (cglb_grad_x_kuf).  G: [M, ldg >= N], row m contiguous (the columns from N on
+        are never read); cvec [M] and wvec [N] together or not at all.  Bitwise repeatable."""
+        Gt = torch.as_tensor(G, dtype=self.dtype, device=self.device)
+        if Gt.dim() != 2 or Gt.shape[0] != self.M or Gt.shape[1] < self.N:
+            raise ValueError(f"G must be [{self.M}, ldg >= {self.N}]")
+        if (cvec is None) != (wvec is None):
+            raise ValueError("cvec and wvec go together")
+        Gt = Gt.contiguous()
+        ct = None if cvec is None else self._dev(cvec, self.M)
+        wt = None if wvec is None else self._dev(wvec, self.N)
+        gx = self._nan_rows()
+        _lib.check(self.lib.cglb_grad_x_kuf(self._ctx, _ptr(Gt), int(Gt.shape[1]), _ptr(ct), _ptr(wt), _ptr(gx)), self._ctx)
+        return gx
+
+    def time_grad_x_kuf(self, reps: int) -> float:
+        ms = c_double()
+        _lib.check(self.lib.cglb_time_grad_x_kuf(self._ctx, int(reps), byref(ms)), self._ctx)
         return ms.value
 
     def set_inputs(self, X):

@@ -496,6 +496,32 @@ int cglb_itergp_objective_and_grad_x(cglb_ctx* ctx, const void* eps, int t, void
  * gradient product of cglb_gpr_predict_grad with rows = points = X, one row block of the option "gpr_block" at a time: n_total x gpr_block further
  * doubles, checked against the free device memory first. */
 int cglb_gpr_objective_and_grad_x(cglb_ctx* ctx, double* out3, double* grad, void* gx_out);
+/* ---- the CGLB / SGPR bounds -------------------------------------------------------------------------------------------------------------
+ * cglb_objective_and_grad with the EXACT derivative of out4[0] with respect to the training inputs besides, at fixed v (detached, as the
+ * hyper-parameter gradient has it), Z and hyper-parameters:
+ *   gx[n, k] = sum_m (Guf[m, n] + c_m w_n) d k(z_m, x_n) / d x_nk                    (log-det, trace and preconditioner terms through K_uf)
+ *            + sum_j (u_n v_j + v_n u_j) d k(x_n, x_j) / d x_nk,  u = w + v / 2       (quad_term 0 only: the term +(w + v/2)^T dK_ff v)
+ * Guf, c and w are the K_uf adjoint, c = K_uu^-1 K_uf w and w = P r the hyper-parameter gradient forms; K_uu and tr K_ff do not depend on X.
+ * One implementation with cglb_objective_and_grad, which is its gx_out = NULL case: out4, grad, steps, half_rz, v and the state left behind are
+ * bitwise the same.  grad must be set with gx_out (dev [n_total, d], overwritten).  Two further passes: the transposed panel pass
+ * (cglb_grad_x_kuf) and, with the CG quadratic term, the single-pair K_ff pass (cglb_grad_x_kff_pair); no atomics, bitwise reproducible.
+ * Scope: fp64, one rank and one shard, one target column, d <= 32, logdet_bound 0 and 1, quad_term 0 and 1, precond_mode 0; elsewhere
+ * CGLB_ERR_BAD_ARG with a message that names the reason (cglb_get_stat "bound_input_grad_native" tells beforehand). */
+int cglb_objective_and_grad_x(cglb_ctx* ctx, void* v_inout, int run_cg, double max_error, int max_cg_iter, int restart_cg_iter, double* out4,
+                              double* grad, int* steps, double* half_rz, void* gx_out);
+/* The transposed panel pass on its own: gx[n, k] = sum_m (G[m * ldg + n] + cvec[m] wvec[n]) d k(z_m, x_n) / d x_nk with respect to the raw training
+ * inputs, at the inducing points and hyper-parameters of the last cglb_set_hypers (no common terms needed).  G: dev [m][ldg], row m contiguous,
+ * ldg >= n_total; cvec: dev [m] and wvec: dev [n_total], or both NULL; gx_out: dev [n_total, d], overwritten.  The operand sets and the evaluator of
+ * the dZ reduction of the same panel; the inducing points are split into chunks (option "kuf_msplit" > 0 forces their count) whose partial sums
+ * are added in fixed order.  A training point equal to an inducing point adds exactly zero.  Scope as cglb_grad_x_kff_multi. */
+int cglb_grad_x_kuf(cglb_ctx* ctx, const void* G, int64_t ldg, const void* cvec, const void* wvec, void* gx_out);
+/* average duration (ms) of `reps` back-to-back transposed panel passes over a panel with ldg = n_total rounded up to 32 */
+int cglb_time_grad_x_kuf(cglb_ctx* ctx, int reps, double* ms_avg);
+/* cglb_grad_x_kff_multi for ONE pair u, v (dev [n_total]): the kernel's G = 1 instance with more rows per lane; the same sums in another order, so
+ * equal to cglb_grad_x_kff_multi(u, v, 1) to round-off, not bitwise.  cglb_grad_x_kff_multi itself is not routed here. */
+int cglb_grad_x_kff_pair(cglb_ctx* ctx, const void* u, const void* v, void* gx_out);
+/* average duration (ms) of `reps` back-to-back single-pair passes, beside cglb_time_grad_x_kff_multi(S = 1) on the same operands */
+int cglb_time_grad_x_kff_pair(cglb_ctx* ctx, int reps, double* ms_avg);
 /* Replace the training inputs (X: [n_total, d], host or device, the context's element type) and keep the targets.  Invalidates everything
  * cglb_set_data invalidates AND the hyper-parameters of both cglb_set_hypers and cglb_gpr_set_hypers: the scaled operand sets are made from X by
  * cglb_set_hypers, so an evaluation without a new push is CGLB_ERR_STATE instead of an evaluation on the old inputs.  Needs cglb_set_data first. */
@@ -538,6 +564,8 @@ int cglb_time_kernel(cglb_ctx* ctx, int which, int reps, double* ms_avg);
  * "input_grad_mid" - runs (fp64, one rank, one target column, up to 32 dimensions; 33 ... 96 under "input_grad_mid"), 0 if it is refused;
  * "train_input_grad_native": 1 if the next training-input gradient (cglb_grad_x_kff_multi, cglb_itergp_objective_and_grad_x,
  * cglb_gpr_objective_and_grad_x) on this context in its current state - dtype, width, ranks, shard, target columns - runs, 0 if it is refused;
+ * "bound_input_grad_native": 1 if the next cglb_objective_and_grad_x with gx_out on this context in its current state - dtype, width, ranks,
+ * shard, target columns, "logdet_bound", "precond_mode" - runs, 0 if it is refused;
  * "exp_clamp" | "m32_bias": the exponent-range regime the last cglb_set_hypers chose from the data's per-column range and the lengthscales
  * (CGLB_ERR_STATE before one) - 1 if the pair kernels run their range-clamped instances (kernel values below 2^-1000 come out as that floor,
  * not 0), 0 for the unclamped ones | the positivity bias of the Matern squared distance in hot units^2 (0 for RBF; above 2e-8 the clamped
@@ -558,7 +586,7 @@ int cglb_time_kernel(cglb_ctx* ctx, int which, int reps, double* ms_avg);
  * cglb_itergp_predict_cached; "itergp_cache_request": the rank the valid variance cache was asked for, 0 without a valid cache;
  * "feature_ms": device time of the last feature product (kernel and slab sums of every group) of cglb_feature_matmat or cglb_itergp_sample. */
 int cglb_get_stat(cglb_ctx* ctx, const char* name, double* value);
-/* Tunables: name = "kff_variant" | "kff_jsplit" | "kff_rows" | "sym_chunk" | "precond_mode" | "chol_mode" | "pcg_lookahead" | "sym_order" | "aat_block" | "grad_gram" | "k1_profile" |
+/* Tunables: name = "kff_variant" | "kff_jsplit" | "kuf_msplit" (chunks over the inducing points of cglb_grad_x_kuf, 0: the rule) | "kff_rows" | "sym_chunk" | "precond_mode" | "chol_mode" | "pcg_lookahead" | "sym_order" | "aat_block" | "grad_gram" | "k1_profile" |
  * "grad_trsm" (gradient algebra against L = chol(K_uu): 0 products with the explicit inverse, 1 backward-stable triangular solves, 2 = default:
  *  the products followed by one step of iterative refinement against L - the accuracy of the solves for about two thirds of their time) |
  * "precision" (the EVALUATOR of a kernel value - 2^x, square root, polynomial factor - given the squared distance it is handed: 1, default:
